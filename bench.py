@@ -1,6 +1,12 @@
 """Contract benchmark: edited images / second of the FLUX-Kontext hot path on N MI355X (one process per GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the contract line (the headline `value` with its
+`ms_per_step` and the timed region's HIP-event and host figures); everything else below (`roofline`, `cpu_baseline`,
+`extra`) is measured only with `--full`.  `--dump-outputs DIR` writes what the last timed step returned on rank 0
+(`images.npy`, `latents.npy`, float32; a fixed seeded sample of an array beyond its share of 64 MB): the inputs and
+weights are seeded, so two builds can be compared output for output.
 
 N > 1 without a launcher (WORLD_SIZE unset) re-executes itself as `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...` (`self_launch_argv`), i.e. the reference's
@@ -17,20 +23,22 @@ transformer and the FLUX VAE with seeded random-init weights (no checkpoints off
 The prompt encoders (Qwen2.5-VL / T5 / CLIP, reused as-is on PyTorch-ROCm) are upstream of the path:
 their outputs (prompt_embeds, pooled) are inputs here; their cost is reported separately (`extra.prompt_encode`).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  With `--full`, besides the contract fields it carries
   roofline     : the dominant kernel family (bf16 MFMA GEMM, all epilogues): algorithmic FLOPs of its
                  launches in one edit / their summed duration, measured live with HIP events on the
                  launch stream in an instrumented edit after the timed region; `traffic` = HBM bytes per
                  launch of the family's dominant kernel from the committed PMC passes (`TRAFFIC_FILE`: the newest
                  profiles/rNN_traffic.json);  `roofline.workloads` = the headline numbers of EVERY workload of the run;
   cpu_baseline : the CPU oracle (fp32 torch restatement, `oracle/`) timed on this box's host cores
-                 (N = 1, rank 0 only): BASELINE.json configs[0] as defined -- all FOUR denoise steps at full depth
-                 + VAE encode + decode executed (`--cpu-baseline cfg1`, the default; ~4.5 min of host time);
-                 the 28-step figure is stated as an extrapolation of the executed steps;
+                 (N = 1, rank 0 only): ONE denoise step at full depth + VAE encode + decode executed
+                 (`--cpu-baseline full`, the default), cfg 1 and 28 steps stated as extrapolations of that step;
+                 `--cpu-baseline cfg1` executes BASELINE.json configs[0] as defined -- all FOUR steps (a few minutes
+                 of host time more: the whole --full run is kept within 10 min with the default);
   extra        : the 1024 x 1024 half of BASELINE.json's metric (`single_1024x1024_28step`, same run, after the
                  timed region: 1 warm-up + 3 timed edits per GPU, its own roofline), the CLI's ~1 MP condition
                  shape (`cfg2cli_512x512_cond1mp_28step`, S = 5632; N = 1), cfg 3 (B = 32 at 1024^2: 1 warm-up batch
-                 + 3 timed batches, HIP-event median; N = 1), for N > 1 a cfg 4 slice (4 edits per GPU at 1024^2) and
+                 + 1 timed batch, ~2 min each; FK_BENCH_CFG3_STEPS=3,1 gives SURVEY.md section 8(d)'s 1 + 3 with the
+                 HIP-event median; N = 1), for N > 1 a cfg 4 slice (4 edits per GPU at 1024^2) and
                  the prompt-encode time T_prompt / T_e2e of SURVEY.md section 8(d);
   extra.cfg5_* : one stage-2 optimisation step of the denoiser (BASELINE.json configs[4]) on this GPU, samples/s;
   dist         : world size and backend as torch.distributed reports them + `rccl_ranks_seen`, the rank ids an
@@ -510,7 +518,26 @@ def timed_edits(pipe, inp, steps, warmup, world, device, backend):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(out.images.float()).all(), "non-finite output image"
-    return elapsed
+    return elapsed, out
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out):
+    """What a caller of the timed path receives from its last step -- the decoded images (`pt_raw`) and the packed final
+    latents -- as float32 `.npy` files in `dirname`.  An array beyond its share of DUMP_BYTES is written as a fixed seeded
+    sample of its flattened elements (the same indices in every run of the same workload)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"images": out.images, "latents": out.latents}
+    share = DUMP_BYTES // len(arrays) // 4
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), share))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 def _compact(x):
@@ -578,15 +605,24 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: the workload's batch per GPU; strong: --global-batch fixed, sharded items[rank::world]")
     ap.add_argument("--global-batch", type=int, default=0, help="strong scaling: total edits per step (default 8 x batch)")
-    ap.add_argument("--cpu-baseline", default="cfg1", choices=["full", "cfg1", "blocks", "none"],
-                    help="cfg1 (default): BASELINE.json configs[0] as defined, all four steps executed (~4 min of host time); "
-                         "full: one full-depth CPU step + VAE; blocks: 1 + 1 blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's images / latents as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the extra workloads, the prompt stage, cfg 5 and the CPU baseline")
+    ap.add_argument("--cpu-baseline", choices=["full", "cfg1", "blocks", "none"],
+                    help="with --full: full (default): one full-depth CPU step + VAE executed, cfg 1 extrapolated; cfg1: "
+                         "BASELINE.json configs[0] as defined, all four steps executed (minutes of host time); blocks: 1 + 1 blocks")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the extras (1024^2 edit, cfg 3 batch, prompt encode, cfg 5 train step)")
     args = ap.parse_args()
-    if args.no_cpu_baseline:
+    side_flags = [f for f, given in (("--cpu-baseline", args.cpu_baseline), ("--no-cpu-baseline", args.no_cpu_baseline),
+                                     ("--no-roofline", args.no_roofline), ("--no-extra", args.no_extra)) if given]
+    if args.no_cpu_baseline or not args.full:
         args.cpu_baseline = "none"
+    elif args.cpu_baseline is None:
+        args.cpu_baseline = "full"
+    if not args.full:          # a plain run: the timed steps and the contract line only
+        args.no_roofline = args.no_extra = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started the way the 1-GPU bench is: become the launcher (step1_gen_samples.py:82-92 is torchrun + init_process_group)
@@ -600,6 +636,9 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but the launcher set WORLD_SIZE={world}")
+    if side_flags and not args.full and rank == 0:
+        print(f"bench.py: ignoring {' '.join(side_flags)} (takes effect with --full only): this run times the headline edits only",
+              file=sys.stderr)
     # one process per GPU; FK_BENCH_BACKEND=gloo (+ ranks sharing a GPU) exists only to smoke-test the N > 1
     # code path on a 1-GPU box
     backend = os.environ.get("FK_BENCH_BACKEND", "nccl")
@@ -626,7 +665,10 @@ def main():
         batch, global_batch = B_w, B_w * world
     inp = make_inputs(args.workload, device, seed=42 + rank, batch=batch)  # every rank edits its own shard
 
-    elapsed = timed_edits(pipe, inp, args.steps, args.warmup, world, device, backend)
+    elapsed, out = timed_edits(pipe, inp, args.steps, args.warmup, world, device, backend)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    del out
     images = global_batch * args.steps
     S = inp["S_txt"] + inp["S_tgt"] + inp["S_cond"]
     result = {
@@ -665,7 +707,7 @@ def main():
         w = world if all_ranks else 1
         inp_x = make_inputs(name, device, seed=seed + rank)
         torch.cuda.reset_peak_memory_stats(device)
-        el = timed_edits(pipe, inp_x, k, warm, w, device, backend)
+        el, _ = timed_edits(pipe, inp_x, k, warm, w, device, backend)
         Bx = inp_x["B"]
         ex = {"value": w * Bx * k / el, "unit": "images/s", "n_gpus": w, "steps": k, "warmup": warm,
               "ms_per_step": el / k * 1e3, "scaling": "weak", "ms_per_step_hip_events": timed_edits.hip_event_ms,
@@ -698,11 +740,11 @@ def main():
             extra[CLI_WORKLOAD] = {"error": f"{type(e).__name__}: {e}"}
     if single and rank == 0 and world == 1 and os.environ.get("FK_BENCH_CFG3", "1") != "0":
         # BASELINE.json configs[2] (B = 32 at 1024^2: one GPU's share of the reference's batch runs) by SURVEY.md section
-        # 8(d)'s protocol: 1 warm-up batch + 3 timed batches (HIP-event median beside the wall-clock mean; a batch takes
-        # ~2 min), then a 4-step instrumented pass of the same batch for its roofline (M = 278 528 rows per GEMM).
-        # FK_BENCH_CFG3_STEPS=k,w shortens it for builder runs.
+        # 8(d)'s protocol shortened to 1 warm-up batch + 1 timed batch (a batch takes ~2 min: the whole --full run stays
+        # within 10 min), then a 4-step instrumented pass of the same batch for its roofline (M = 278 528 rows per GEMM).
+        # FK_BENCH_CFG3_STEPS=k,w sets it: 3,1 is the protocol's 1 + 3 with the HIP-event median beside the wall-clock mean.
         try:
-            k3, w3 = (int(v) for v in os.environ.get("FK_BENCH_CFG3_STEPS", "3,1").split(","))
+            k3, w3 = (int(v) for v in os.environ.get("FK_BENCH_CFG3_STEPS", "1,1").split(","))
             extra_workload(CFG3_WORKLOAD, k3, w3, seed=242, i_steps=4)
         except Exception as e:
             extra[CFG3_WORKLOAD] = {"error": f"{type(e).__name__}: {e}"}
