@@ -74,9 +74,46 @@ int check_ws(const fk_block_ws* ws, Dims& d, const char* who) {
     if (rc_ != FK_OK) return rc_; \
   } while (0)
 
+// MXFP8 form of a block's launch (fk_*_fwd_mx): the quantized-activation workspace and this launch's weight pairs
+struct Mx {
+  const fk_mx_ws* ws;
+  const fk_mx_pair* w;   // one per problem of the launch
+};
+
+// one GEMM launch of a block: the bf16 call as it always was, or (mx) each problem's activation quantized into the workspace,
+// the img rows first, then the mxfp8 GEMM on the pre-quantized weights with the same epilogue fields
+int block_gemm(fk_gemm_args* g, int n, const Mx* mx, fk_stream_t st) {
+  if (!mx) return n == 1 ? fk_gemm_bf16(g, st) : fk_gemm_bf16_grouped(g, n, st);
+  fk_gemm_mxfp8_args a[2] = {};
+  int64_t qo = 0, so = 0;
+  for (int i = 0; i < n; ++i) {
+    const int K = g[i].K;
+    FK_CHECK_ARG(mx->w[i].q && mx->w[i].s, "fk_*_block_fwd_mx: null quantized weight");
+    FK_CHECK_ARG(qo + (int64_t)g[i].M * K <= mx->ws->q_bytes && so + (int64_t)g[i].M * (K / 32) <= mx->ws->s_bytes,
+                 "fk_*_block_fwd_mx: quantized-activation workspace too small (%lld / %lld bytes)", (long long)mx->ws->q_bytes,
+                 (long long)mx->ws->s_bytes);
+    void* q = (char*)mx->ws->q + qo;
+    void* s = (char*)mx->ws->s + so;
+    FK_TRY(fk_quantize_mxfp8(g[i].A, g[i].a, g[i].M, K, q, K, s, K / 32, st));
+    a[i].g = g[i];
+    a[i].g.A = nullptr; a[i].g.W = nullptr;
+    a[i].g.splitk_ws = nullptr; a[i].g.splitk_slots = 0;
+    a[i].g.variant = 0; a[i].g.plan = 0; a[i].g.group_m = 0; a[i].g.mfma = 0;
+    a[i].A8 = q; a[i].lda8 = K; a[i].A_scale = s; a[i].lda_scale = K / 32;
+    a[i].W8 = mx->w[i].q; a[i].ldw8 = K; a[i].W_scale = mx->w[i].s; a[i].ldw_scale = K / 32;
+    qo += (int64_t)g[i].M * K;
+    so += (int64_t)g[i].M * (K / 32);
+  }
+  return fk_gemm_mxfp8_grouped(a, n, st);
+}
+
 int double_block(const fk_block_ws& ws, const Dims& d, const fk_double_block_weights& w, const void* mod, int64_t mod_bs,
-                 fk_stream_t st) {
+                 fk_stream_t st, const fk_mx_ws* mxws = nullptr,
+                 const fk_double_block_weights_mx* wx = nullptr) {
   FK_CHECK_ARG(ws.o && ws.ff && d.S_txt > 0, "fk_double_block_fwd: needs the o / ff buffers and a text stream");
+  // the img / txt weight pairs of a launch are adjacent members of fk_double_block_weights_mx (qkv_img | qkv_txt, out | add_out, ...)
+  Mx mxc;
+  auto mx = [&](const fk_mx_pair* pair) -> const Mx* { if (!pair) return nullptr; mxc = Mx{mxws, pair}; return &mxc; };
   const int D = d.D, B = d.B, Mi = B * d.S_img, Mt = B * d.S_txt;
   const char* mi = (const char*)mod + w.mod_off_img * 2;     // shift, scale, gate, shift_mlp, scale_mlp, gate_mlp: D each
   const char* mt = (const char*)mod + w.mod_off_txt * 2;
@@ -94,7 +131,7 @@ int double_block(const fk_block_ws& ws, const Dims& d, const fk_double_block_wei
     qkv_epi(g[0], ws, d, w.norm_q, w.norm_k, d.S_txt);
     g[1] = gemm(n_txt, w.wqkv_txt, w.bqkv_txt, view(ws.qkv, d, 3 * D, 0, d.S_txt, 0), Mt, 3 * D, D, FK_EPI_QKV);
     qkv_epi(g[1], ws, d, w.norm_added_q, w.norm_added_k, 0);
-    ctl(g[0], ws); FK_TRY(fk_gemm_bf16_grouped(g, 2, st));
+    ctl(g[0], ws); FK_TRY(block_gemm(g, 2, mx(wx ? &wx->qkv_img : nullptr), st));
   }
   FK_TRY(fk_attention_fwd_ws_bf16(ws.q, ws.k, (const char*)ws.qkv + (int64_t)2 * D * 2, ws.o, nullptr, B, d.H, d.S, 3 * D,
                                   (int64_t)d.S * 3 * D, D, (int64_t)d.S * D, 0.08838834764831845f, ws.attn_ws, ws.attn_ws_bytes, ws.attn_grid, st));
@@ -105,7 +142,7 @@ int double_block(const fk_block_ws& ws, const Dims& d, const fk_double_block_wei
     g[1] = gemm(view(ws.o, d, D, 0, d.S_txt, 0), w.w_add_out, w.b_add_out, cx, Mt, D, D, FK_EPI_GATE_RES);
     gate_res(g[1], cx, chunk(mt, 2), mod_bs, d.S_txt);
     set_ws(g[0], ws); set_ws(g[1], ws);
-    ctl(g[0], ws); FK_TRY(fk_gemm_bf16_grouped(g, 2, st));
+    ctl(g[0], ws); FK_TRY(block_gemm(g, 2, mx(wx ? &wx->out : nullptr), st));
   }
   FK_TRY(fk_ln_modulate2_bf16(s_all.p, s_all.r, (void*)n_all.p, n_all.r, chunk(mt, 3), chunk(mt, 4), chunk(mi, 3), chunk(mi, 4),
                               d.S_txt, mod_bs, d.S, M, D, ws.eps, st));
@@ -113,7 +150,7 @@ int double_block(const fk_block_ws& ws, const Dims& d, const fk_double_block_wei
     fk_gemm_args g[2];
     g[0] = gemm(n_img, w.w_ff1, w.b_ff1, view(ws.ff, d, 4 * D, d.S_txt, d.S_img, 0), Mi, 4 * D, D, FK_EPI_GELU_TANH);
     g[1] = gemm(n_txt, w.w_ff1_ctx, w.b_ff1_ctx, view(ws.ff, d, 4 * D, 0, d.S_txt, 0), Mt, 4 * D, D, FK_EPI_GELU_TANH);
-    ctl(g[0], ws); FK_TRY(fk_gemm_bf16_grouped(g, 2, st));
+    ctl(g[0], ws); FK_TRY(block_gemm(g, 2, mx(wx ? &wx->ff1 : nullptr), st));
   }
   {
     fk_gemm_args g[2];
@@ -122,13 +159,15 @@ int double_block(const fk_block_ws& ws, const Dims& d, const fk_double_block_wei
     g[1] = gemm(view(ws.ff, d, 4 * D, 0, d.S_txt, 0), w.w_ff2_ctx, w.b_ff2_ctx, cx, Mt, D, 4 * D, FK_EPI_GATE_RES);
     gate_res(g[1], cx, chunk(mt, 5), mod_bs, d.S_txt);
     set_ws(g[0], ws); set_ws(g[1], ws);
-    ctl(g[0], ws); FK_TRY(fk_gemm_bf16_grouped(g, 2, st));
+    ctl(g[0], ws); FK_TRY(block_gemm(g, 2, mx(wx ? &wx->ff2 : nullptr), st));
   }
   return FK_OK;
 }
 
 int single_block(const fk_block_ws& ws, const Dims& d, const fk_single_block_weights& w, const void* mod, int64_t mod_bs,
-                 fk_stream_t st) {
+                 fk_stream_t st, const fk_mx_ws* mxws = nullptr, const fk_single_block_weights_mx* wx = nullptr) {
+  Mx mxc;
+  auto mx = [&](const fk_mx_pair* pair) -> const Mx* { if (!pair) return nullptr; mxc = Mx{mxws, pair}; return &mxc; };
   FK_CHECK_ARG(ws.cat != nullptr, "fk_single_block_fwd: needs the [attn | mlp] buffer");
   const int D = d.D, B = d.B;
   const int Ms = B * d.S;
@@ -139,7 +178,7 @@ int single_block(const fk_block_ws& ws, const Dims& d, const fk_single_block_wei
   {
     fk_gemm_args g = gemm(n_all, w.wqkv, w.bqkv, view(ws.qkv, d, 3 * D, 0, d.S, 0), Ms, 3 * D, D, FK_EPI_QKV);
     qkv_epi(g, ws, d, w.norm_q, w.norm_k, 0);
-    ctl(g, ws); FK_TRY(fk_gemm_bf16(&g, st));
+    ctl(g, ws); FK_TRY(block_gemm(&g, 1, mx(wx ? &wx->qkv : nullptr), st));
   }
   // attention writes columns [0, D) of the [B, S, 5D] buffer, the MLP-up GEMM columns [D, 5D): proj_out reads one operand
   FK_TRY(fk_attention_fwd_ws_bf16(ws.q, ws.k, (const char*)ws.qkv + (int64_t)2 * D * 2, ws.cat, nullptr, B, d.H, d.S, 3 * D,
@@ -147,13 +186,13 @@ int single_block(const fk_block_ws& ws, const Dims& d, const fk_single_block_wei
                                   ws.attn_ws_bytes, ws.attn_grid, st));
   {
     fk_gemm_args g = gemm(n_all, w.w_mlp, w.b_mlp, view(ws.cat, d, 5 * D, 0, d.S, D), Ms, 4 * D, D, FK_EPI_GELU_TANH);
-    ctl(g, ws); FK_TRY(fk_gemm_bf16(&g, st));
+    ctl(g, ws); FK_TRY(block_gemm(&g, 1, mx(wx ? &wx->mlp : nullptr), st));
   }
   {
     fk_gemm_args g = gemm(view(ws.cat, d, 5 * D, 0, d.S, 0), w.w_out, w.b_out, s_all, Ms, D, 5 * D, FK_EPI_GATE_RES);
     gate_res(g, s_all, chunk(2), mod_bs, d.S);
     set_ws(g, ws);
-    ctl(g, ws); FK_TRY(fk_gemm_bf16(&g, st));
+    ctl(g, ws); FK_TRY(block_gemm(&g, 1, mx(wx ? &wx->out : nullptr), st));
   }
   return FK_OK;
 }
@@ -185,5 +224,48 @@ extern "C" int fk_mmdit_blocks_fwd(const fk_block_ws* ws, const fk_double_block_
                "fk_mmdit_blocks_fwd: null weights / modulation");
   for (int i = 0; i < n_double; ++i) FK_TRY(double_block(*ws, d, dbl[i], mod, mod_batch_stride, stream));
   for (int i = 0; i < n_single; ++i) FK_TRY(single_block(*ws, d, sgl[i], mod, mod_batch_stride, stream));
+  return FK_OK;
+}
+
+// ---- MXFP8 forms: the same launches with every block GEMM as quantize -> fk_gemm_mxfp8 ------------------------------------
+namespace {
+int check_mx(const fk_mx_ws* mx, const char* who) {
+  FK_CHECK_ARG(mx && mx->q && mx->s && (uintptr_t)mx->q % 16 == 0 && (uintptr_t)mx->s % 4 == 0,
+               "%s: null or misaligned quantized-activation workspace", who);
+  return FK_OK;
+}
+}  // namespace
+
+extern "C" int fk_double_block_fwd_mx(const fk_block_ws* ws, const fk_mx_ws* mx, const fk_double_block_weights* w,
+                                      const fk_double_block_weights_mx* wx, const void* mod, int64_t mod_batch_stride,
+                                      fk_stream_t stream) {
+  Dims d;
+  FK_TRY(check_ws(ws, d, "fk_double_block_fwd_mx"));
+  FK_TRY(check_mx(mx, "fk_double_block_fwd_mx"));
+  FK_CHECK_ARG(w && wx && mod, "fk_double_block_fwd_mx: null weights / modulation");
+  return double_block(*ws, d, *w, mod, mod_batch_stride, stream, mx, wx);
+}
+
+extern "C" int fk_single_block_fwd_mx(const fk_block_ws* ws, const fk_mx_ws* mx, const fk_single_block_weights* w,
+                                      const fk_single_block_weights_mx* wx, const void* mod, int64_t mod_batch_stride,
+                                      fk_stream_t stream) {
+  Dims d;
+  FK_TRY(check_ws(ws, d, "fk_single_block_fwd_mx"));
+  FK_TRY(check_mx(mx, "fk_single_block_fwd_mx"));
+  FK_CHECK_ARG(w && wx && mod, "fk_single_block_fwd_mx: null weights / modulation");
+  return single_block(*ws, d, *w, mod, mod_batch_stride, stream, mx, wx);
+}
+
+extern "C" int fk_mmdit_blocks_fwd_mx(const fk_block_ws* ws, const fk_mx_ws* mx, const fk_double_block_weights* dbl,
+                                      const fk_double_block_weights_mx* dblx, int32_t n_double, const fk_single_block_weights* sgl,
+                                      const fk_single_block_weights_mx* sglx, int32_t n_single, const void* mod,
+                                      int64_t mod_batch_stride, fk_stream_t stream) {
+  Dims d;
+  FK_TRY(check_ws(ws, d, "fk_mmdit_blocks_fwd_mx"));
+  FK_TRY(check_mx(mx, "fk_mmdit_blocks_fwd_mx"));
+  FK_CHECK_ARG(mod && n_double >= 0 && n_single >= 0 && (n_double == 0 || (dbl && dblx)) && (n_single == 0 || (sgl && sglx)),
+               "fk_mmdit_blocks_fwd_mx: null weights / modulation");
+  for (int i = 0; i < n_double; ++i) FK_TRY(double_block(*ws, d, dbl[i], mod, mod_batch_stride, stream, mx, &dblx[i]));
+  for (int i = 0; i < n_single; ++i) FK_TRY(single_block(*ws, d, sgl[i], mod, mod_batch_stride, stream, mx, &sglx[i]));
   return FK_OK;
 }

@@ -1,0 +1,288 @@
+// The large-tile GEMMs' shared pieces: 256-row tile addressing, tile order, the accumulator fragment map and the
+// epilogue (store_tile).  Included INSIDE the anonymous namespace of each kernel file: every instantiation stays local
+// to its translation unit, exactly as when these lived in gemm_pingpong_bf16.hip (gemm_mxfp8.hip reuses the epilogue
+// through a config struct that provides NF, MF, M16, NTHREADS, CT_LD, tile_row and tile_col).
+#pragma once
+
+constexpr int BM = 256;
+
+// fk_rows addressing of the (at most BM) rows of one tile without per-row 64-bit divisions: one division per tile
+// for the tile's first row, then a compare per row (a 32-bit division when a batch has fewer rows than a tile).
+// The launcher guarantees that every offset relative to the tile's first row fits 31 bits (in bytes).
+struct TileRows {
+  int ld, wrap, rpb, b0, r0;
+  float inv;    // 1 / rpb when a batch is shorter than a tile
+  bool big;     // rpb >= BM (or no batching): a tile crosses at most one batch boundary
+  FK_DEV TileRows(const fk_rows& r, int m0) {
+    ld = (int)r.ld;
+    if (r.rows_per_batch <= 0) { rpb = 0x7fffffff; wrap = 0; b0 = 0; r0 = 0; big = true; inv = 0.f; }
+    else {
+      rpb = (int)(r.rows_per_batch > 0x7fffffff ? 0x7fffffff : r.rows_per_batch);
+      b0 = (unsigned)m0 / (unsigned)rpb;
+      r0 = m0 - b0 * rpb;
+      wrap = (int)(r.batch_stride - (int64_t)rpb * r.ld);
+      big = rpb >= BM;
+      inv = 1.0f / (float)rpb;
+    }
+  }
+  // batches crossed between the tile's first row and its row ml (branch-free: r0 + ml < rpb + BM, so for short
+  // batches the quotient is a small integer that the float product resolves exactly)
+  FK_DEV int crossed(int ml) const {
+    const int r = r0 + ml;
+    const int one = r >= rpb ? 1 : 0;
+    const int many = (int)(((float)r + 0.5f) * inv);
+    return big ? one : many;
+  }
+  // element offset of row ml of the tile relative to its first row
+  FK_DEV int off(int ml) const { return ml * ld + crossed(ml) * wrap; }
+};
+
+// sum over the 16 lanes of a DPP row, every lane receiving the total: four row-rotate adds on the VALU (no LDS
+// round trips).  Bit-identical to the xor butterfly 8, 4, 2, 1: after the step of distance d the partial sums have
+// period d within the row, so "rotate by d" and "xor d" name the same partner value.
+template <int N>
+FK_DEV float row_ror(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + N, 0xf, 0xf, false));
+}
+FK_DEV float row16_sum(float v) {
+  v += row_ror<8>(v);
+  v += row_ror<4>(v);
+  v += row_ror<2>(v);
+  v += row_ror<1>(v);
+  return v;
+}
+
+// tile selection: XCD chunking over the whole grid (workgroup b runs on XCD b % 8: consecutive tiles of the order
+// below -- which share A rows and W columns -- stay on one XCD's L2), then problem, then grouped (GROUP_M deep) order
+FK_DEV int xcd_chunk_index() {
+  const int nwg = gridDim.x;
+  const int q = nwg >> 3, r = nwg & 7;
+  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// ---- MFMA shape ------------------------------------------------------------------------------------------------------
+// M16 = false: v_mfma_f32_32x32x16_bf16 (8 passes, 16 k per instruction); M16 = true: v_mfma_f32_16x16x32_bf16 (4 passes, 32 k
+// per instruction) on the SAME LDS image, the same accumulator registers and the same number of ds_read_b128 per K-tile.
+// Why both exist (tools/power_probe.hip, profiles/r05_power_probe.txt): under the chip's power limit a pure MFMA stream of
+// the 16 x 16 x 32 form sustains 2 017 TF/s at 1.97 GHz against 1 800 TF/s at 1.76 GHz for the 32 x 32 x 16 form -- half the
+// accumulator register traffic per flop -- and the GEMM main loops are power-bound.  A 32 x 32 accumulator block (nf, mf) of
+// the epilogue holds, as quad q = 2 * n16 + m16 (4 registers = 4 consecutive output columns of one row), the 16 x 16 block
+// (n16, m16) in the M16 form and columns 8 q + 4 (lane >> 5) of row (lane & 31) in the other.
+template <bool M16>
+struct FragMap {
+  static FK_DEV int row(int lane, int q) { return M16 ? (q & 1) * 16 + (lane & 15) : (lane & 31); }
+  static FK_DEV int col(int lane, int q) { return M16 ? (q >> 1) * 16 + (lane >> 4) * 4 : 8 * q + 4 * (lane >> 5); }
+};
+FK_DEV f32x4_t quad_get(const f32x16_t& v, int q) { return f32x4_t{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]}; }
+FK_DEV void quad_set(f32x16_t& v, int q, const f32x4_t& c) {
+  v[4 * q] = c[0]; v[4 * q + 1] = c[1]; v[4 * q + 2] = c[2]; v[4 * q + 3] = c[3];
+}
+
+// epilogue (as gemm_bf16.hip): bias/activation -> bf16 -> LDS tile -> coalesced 16-byte rows.
+// acc[nf][mf] is the 32x32 block (n-block nf, m-block mf) of wave (wm, wn) in MFMA-output layout with the
+// swapped operands: lane l holds row (l & 31) of the m-block, columns 8*q + 4*(l >> 5) + j of the n-block.
+//
+// With one workgroup per CU nothing overlaps the epilogue, so it must not be a chain of load -> wait -> use steps
+// (measured: a bias load in front of every quad and a residual / gate / rope-table load in front of every stored
+// chunk made the epilogue ~15 % of a K = 3072 tile).  All global reads are therefore issued unconditionally with
+// clamped indices, a batch of EPI_BATCH chunks at a time, ahead of the arithmetic of the batch; only the final
+// store is predicated.
+template <int EPI, int BN, class C>
+FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& p, char* smem, int m0, int n0,
+                       int wm, int wn) {
+  int tid = threadIdx.x;
+  // gemm10 (the only 256-thread caller) may run this inside a per-CU tile loop around an asm statement that leaves 36 free
+  // VGPRs: an opaque copy keeps hipcc from hoisting the 32 per-lane row indices below out of that loop and spilling them
+  if constexpr (C::NTHREADS == 256) asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
+  using FM = FragMap<C::M16>;
+  // bias of this lane's 4-column quads (all loads in flight before the barrier below)
+  u32x2_t bw[C::NF][4];
+#pragma unroll
+  for (int nf = 0; nf < C::NF; ++nf)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bw[nf][q] = u32x2_t{0u, 0u};
+  if constexpr (EPI != FK_EPI_SCALE) {
+    if (p.bias) {
+#pragma unroll
+      for (int nf = 0; nf < C::NF; ++nf)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int n = n0 + C::tile_col(wn, nf) + FM::col(lane, q);
+          bw[nf][q] = *(const u32x2_t*)((const bf16_t*)p.bias + min(n, p.N - 4));   // columns >= N are never stored
+        }
+    }
+  }
+  if constexpr (EPI == FK_EPI_F32DBG) {
+    // parity build: fp32(acc + bias) straight from the accumulator registers (a lane owns 4 consecutive columns of a row)
+#pragma unroll
+    for (int nf = 0; nf < C::NF; ++nf)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = n0 + C::tile_col(wn, nf) + FM::col(lane, q);
+        const float b[4] = {bf_lo(bw[nf][q][0]), bf_hi(bw[nf][q][0]), bf_lo(bw[nf][q][1]), bf_hi(bw[nf][q][1])};
+#pragma unroll
+        for (int mf = 0; mf < C::MF; ++mf) {
+          const int m = m0 + C::tile_row(wm, mf) + FM::row(lane, q);
+          if (m < p.M && n < p.N)
+            *(f32x4_t*)((float*)p.C + fk_row_offset(p.c, m) + n) =
+                f32x4_t{acc[nf][mf][4 * q + 0] + b[0], acc[nf][mf][4 * q + 1] + b[1], acc[nf][mf][4 * q + 2] + b[2],
+                        acc[nf][mf][4 * q + 3] + b[3]};
+        }
+      }
+    return;
+  }
+  __syncthreads();  // every wave is done reading the last stage before the C tile aliases it
+  bf16_t* ct = (bf16_t*)smem;
+#pragma unroll
+  for (int nf = 0; nf < C::NF; ++nf) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int nl = C::tile_col(wn, nf) + FM::col(lane, q);
+      const float b[4] = {bf_lo(bw[nf][q][0]), bf_hi(bw[nf][q][0]), bf_lo(bw[nf][q][1]), bf_hi(bw[nf][q][1])};
+#pragma unroll
+      for (int mf = 0; mf < C::MF; ++mf) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float x = acc[nf][mf][q * 4 + j];
+          if constexpr (EPI == FK_EPI_SCALE) v[j] = x * p.alpha;
+          else v[j] = x + b[j];
+        }
+        if constexpr (EPI == FK_EPI_GELU_TANH || EPI == FK_EPI_SILU) {
+          // the reference graph rounds the Linear's output to bf16 before the activation
+          round_bf_pair(v[0], v[1]);
+          round_bf_pair(v[2], v[3]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = EPI == FK_EPI_GELU_TANH ? gelu_tanh_f(v[j]) : silu_f(v[j]);
+        }
+        u32x2_t pk;
+        pk[0] = pack_bf2(v[0], v[1]);
+        pk[1] = pack_bf2(v[2], v[3]);
+        const int ml = C::tile_row(wm, mf) + FM::row(lane, q);
+        *(u32x2_t*)(ct + ml * C::CT_LD + nl) = pk;
+      }
+    }
+  }
+  __syncthreads();
+  constexpr int CPR = BN / 8;  // 16-byte chunks per tile row
+  constexpr int ITERS = BM * CPR / C::NTHREADS;
+  // chunks per batch; the fused QKV epilogue keeps 16 table registers per chunk, so the 4-wave kernel (32 chunks per
+  // thread, VGPRs full) batches 4 and the 8-wave kernel takes all 8 of a thread's chunks at once
+  constexpr int U = (EPI == FK_EPI_QKV && ITERS > 8) ? 4 : 8;
+  static_assert(ITERS % U == 0 && C::NTHREADS % CPR == 0, "epilogue batching");
+  // per-tile (scalar) row addressing of the output, the residual and the gate
+  const TileRows crow(p.c, m0);
+  bf16_t* const cbase = (bf16_t*)p.C + fk_row_offset(p.c, m0);
+  const TileRows rrow = (EPI == FK_EPI_GATE_RES || EPI == FK_EPI_RES) ? TileRows(p.r, m0) : crow;
+  const bf16_t* const rbase =
+      (EPI == FK_EPI_GATE_RES || EPI == FK_EPI_RES) ? (const bf16_t*)p.res + fk_row_offset(p.r, m0) : nullptr;
+  fk_rows gr = {0, 0, 0};
+  if constexpr (EPI == FK_EPI_GATE_RES) gr.rows_per_batch = p.gate_rows_per_batch;
+  const TileRows grow(gr, m0);   // b0 + crossed(ml) = the gate row of tile row ml
+  const int D = EPI == FK_EPI_QKV ? p.qkv_heads * 128 : 1;
+  const int which = EPI == FK_EPI_QKV ? n0 / D : 0;   // 0 = q, 1 = k, 2 = v: a tile never straddles q | k | v
+  // a thread keeps its chunk column over the iterations (NTHREADS % CPR == 0): only the row advances
+  const int cc = tid % CPR, ml0 = tid / CPR;
+  constexpr int ML_STEP = C::NTHREADS / CPR;
+  const int n = n0 + cc * 8;
+  const int nc = min(n, p.N - 8);          // clamped column for the unconditional loads
+  const int mlast = p.M - 1 - m0;          // last valid tile row
+
+  if (EPI == FK_EPI_QKV && which < 2) {
+    // 16 consecutive lanes hold one 128-wide head row of the tile: RMSNorm (weight) + interleaved-pair RoPE, then
+    // the head-major [B, H, S_total, 128] layout
+    const int hn = n - which * D;              // column inside q or k
+    const int head = hn >> 7, dch = hn & 127;  // dch = 8 * chunk-in-head
+    const u32x4_t ww = *(const u32x4_t*)((const bf16_t*)(which == 0 ? p.wq : p.wk) + dch);
+    bf16_t* const dst = (bf16_t*)(which == 0 ? p.q_out : p.k_out);
+#pragma unroll
+    for (int j0 = 0; j0 < ITERS; j0 += U) {
+      u32x4_t y[U];
+      f32x4_t t0[U], t1[U];   // (cos, sin) of the chunk's four rotary pairs
+      int srow[U], bidx[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int ml = ml0 + ML_STEP * (j0 + u);
+        y[u] = *(const u32x4_t*)(ct + ml * C::CT_LD + cc * 8);
+        // token of row m: batch = m / rows_per_batch (one batch when c.rows_per_batch <= 0), s = s_offset + m % rows_per_batch
+        const int mlc = min(ml, mlast);
+        const int nb = crow.crossed(mlc);
+        bidx[u] = crow.b0 + nb;
+        srow[u] = p.qkv_s_offset + crow.r0 + mlc - nb * crow.rpb;
+        const float* tp = p.rope_cs + (int64_t)srow[u] * 128 + dch;   // pair dch/2 + e at floats 2e, 2e + 1
+        t0[u] = *(const f32x4_t*)tp;
+        t1[u] = *(const f32x4_t*)(tp + 4);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int ml = ml0 + ML_STEP * (j0 + u);
+        float xv[8];
+        float ss = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          xv[2 * e] = bf_lo(y[u][e]);
+          xv[2 * e + 1] = bf_hi(y[u][e]);
+          ss += xv[2 * e] * xv[2 * e] + xv[2 * e + 1] * xv[2 * e + 1];
+        }
+        ss = row16_sum(ss);
+        const float rs = __builtin_amdgcn_rsqf(ss * (1.0f / 128) + 1e-6f);   // argument >= 1e-6: no denormal scaling
+        const float cs[4] = {t0[u][0], t0[u][2], t1[u][0], t1[u][2]};
+        const float sn[4] = {t0[u][1], t0[u][3], t1[u][1], t1[u][3]};
+        u32x4_t ow;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float re = xv[2 * e] * rs, im = xv[2 * e + 1] * rs;
+          round_bf_pair(re, im);
+          re *= bf_lo(ww[e]);
+          im *= bf_hi(ww[e]);
+          round_bf_pair(re, im);
+          const float o0 = __fadd_rn(__fmul_rn(re, cs[e]), __fmul_rn(-im, sn[e]));
+          const float o1 = __fadd_rn(__fmul_rn(im, cs[e]), __fmul_rn(re, sn[e]));
+          ow[e] = pack_bf2(o0, o1);
+        }
+        // head-major row index in 32 bits (the launcher checks batches * heads * s_total < 2^31)
+        const int hrow = (bidx[u] * p.qkv_heads + head) * p.qkv_s_total + srow[u];
+        if (ml <= mlast && n < p.N) *(u32x4_t*)(dst + (int64_t)hrow * 128 + dch) = ow;
+      }
+    }
+    return;
+  }
+
+#pragma unroll
+  for (int j0 = 0; j0 < ITERS; j0 += U) {
+    u32x4_t y[U], rv[U], gv[U];
+    int coff[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int ml = ml0 + ML_STEP * (j0 + u);
+      const int mlc = min(ml, mlast);
+      y[u] = *(const u32x4_t*)(ct + ml * C::CT_LD + cc * 8);
+      coff[u] = crow.off(mlc) + n;
+      if constexpr (EPI == FK_EPI_GATE_RES || EPI == FK_EPI_RES) rv[u] = *(const u32x4_t*)(rbase + rrow.off(mlc) + nc);
+      if constexpr (EPI == FK_EPI_GATE_RES) {
+        const int64_t b = grow.b0 + grow.crossed(mlc);
+        gv[u] = *(const u32x4_t*)((const bf16_t*)p.gate + b * p.gate_batch_stride + nc);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int ml = ml0 + ML_STEP * (j0 + u);
+      u32x4_t o = y[u];
+      if constexpr (EPI == FK_EPI_GATE_RES || EPI == FK_EPI_RES) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float y0 = bf_lo(o[e]), y1 = bf_hi(o[e]);
+          if constexpr (EPI == FK_EPI_GATE_RES) {
+            y0 *= bf_lo(gv[u][e]);
+            y1 *= bf_hi(gv[u][e]);
+            round_bf_pair(y0, y1);
+          }
+          o[e] = pack_bf2(bf_lo(rv[u][e]) + y0, bf_hi(rv[u][e]) + y1);
+        }
+      }
+      if (ml <= mlast && n < p.N) *(u32x4_t*)(cbase + coff[u]) = o;
+    }
+  }
+}

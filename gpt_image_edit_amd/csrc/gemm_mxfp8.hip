@@ -1,0 +1,406 @@
+// MXFP8 (OCP MX v1.0: e4m3fn elements, one E8M0 scale per 32 consecutive k) path of the block GEMMs -- opt-in, inference only.
+//
+//   fk_quantize_mxfp8   bf16 rows (fk_rows addressing) -> e4m3 [M, K] + E8M0 [M, K / 32], one pass, one thread per block of 32
+//   gemm_mxfp8_kernel   C = epilogue(deq(A) . deq(W)^T + bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (both operands e4m3)
+//
+// The GEMM keeps the bf16 kernels' conventions so that their epilogue (gemm_epilogue.h: store_tile) takes its accumulators
+// unchanged: operands swapped (W rows -> MFMA src0, activation rows -> src1), 8 waves as 2 (M) x 4 (N), a wave's output the
+// 32 x 32 blocks (nf, mf) of CfgMx::tile_row / tile_col, and inside a block the 16 x 16 quad q = 2 * n16 + m16 -- the
+// 16 x 16 C/D layout does not depend on the operand type on gfx950, so FragMap<true> describes these accumulators as it
+// describes v_mfma_f32_16x16x32_bf16's.
+//
+// Operand / scale lane maps of the 16 x 16 x 128 form with 8-bit operands (measured on the GPU with random small-integer data
+// and random scales against every candidate map; tests/test_hip_mxfp8.py holds the GEMM to exact results on such data): lane l
+// holds row (l & 15) of its operand, with g = l >> 4, k = 16 g + j in byte j of registers 0-3 and k = 64 + 16 g + j in byte j
+// of registers 4-7 (two 16-byte chunks, g and 4 + g, of a 128-byte K-tile row); byte 0 of its scale register is the E8M0
+// scale of block g (k = 32 g .. 32 g + 31) of that row -- NOT the block its own bytes lie in.
+//
+// Main loop (plain HIP, two LDS stages): a K-tile is 128 k = one MFMA k-step.  Each K-tile's operand rows (128 B) and the
+// dword of 4 scale bytes of every row are requested as LDS-DMA pieces one K-tile ahead (fk_common.h: opaque form, counted
+// vmcnt, then a barrier); the 16-byte chunk c of row r sits at slot c ^ (r & 7) (swizzle applied on the DMA source address).
+#include <stdlib.h>
+
+#include "fk_common.h"
+
+namespace {
+
+#include "gemm_epilogue.h"   // BM, TileRows, row16_sum, xcd_chunk_index, FragMap, store_tile
+
+typedef __attribute__((ext_vector_type(8))) int i32x8_t;   // 32 e4m3 bytes: the 16 x 16 x 128 operand of one lane
+
+// ---- quantizer ----------------------------------------------------------------------------------------------------------
+// |v| < 512 (v = x / 2^e with e >= floor(log2 amax) - 8) -> e4m3fn magnitude code, round-to-nearest-even, saturated to 448
+FK_DEV uint32_t e4m3_mag(float a) {
+  a = fminf(a, 448.0f);
+  if (a < 0.015625f) return (uint32_t)__builtin_rintf(a * 512.0f);   // subnormal: k * 2^-9, k = 0..8 (8 = the smallest normal)
+  uint32_t u = __float_as_uint(a);
+  u += 0x7ffffu + ((u >> 20) & 1u);      // round the fp32 mantissa to 3 bits (a carry moves into the exponent)
+  return (u >> 20) - (120u << 3);        // (biased exp - 127 + 7) << 3 | mantissa
+}
+
+__global__ __launch_bounds__(256) void quantize_mxfp8_kernel(const bf16_t* __restrict__ x, fk_rows xr, int64_t M, int K,
+                                                             uint8_t* __restrict__ q, int64_t ldq, uint8_t* __restrict__ sc,
+                                                             int64_t ld_scale) {
+  const int nb = K >> 5;
+  const int64_t bi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (bi >= M * nb) return;
+  const int64_t m = bi / nb;
+  const int j = (int)(bi - m * nb);
+  const u32x4_t* src = (const u32x4_t*)(x + fk_row_offset(xr, m) + j * 32);
+  uint32_t w[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u32x4_t v = src[i];
+    w[4 * i] = v[0]; w[4 * i + 1] = v[1]; w[4 * i + 2] = v[2]; w[4 * i + 3] = v[3];
+  }
+  // amax as bf16 magnitude bits: they order like the values, Inf = 0x7f80, NaN above
+  uint32_t amax = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) amax = max(amax, max(w[i] & 0x7fffu, (w[i] >> 16) & 0x7fffu));
+  uint32_t sbyte, out[8];
+  if (amax >= 0x7f80u) {   // Inf / NaN: NaN scale and NaN elements
+    sbyte = 0xffu;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out[i] = 0x7f7f7f7fu;
+  } else {
+    // e = max(floor(log2 amax) - 8, -127); byte = e + 127 (bf16 exponent field E: floor(log2) = E - 127; subnormal: clamped)
+    const int E = (int)(amax >> 7);
+    sbyte = amax == 0 ? 127u : (uint32_t)max(E - 8, 0);
+    const float inv = __uint_as_float((254u - sbyte) << 23);   // 2^-e, exact (254 - byte in [8, 254] for finite blocks)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      uint32_t o = 0;
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        const uint32_t b = (h & 1) ? (w[2 * i + (h >> 1)] >> 16) : (w[2 * i + (h >> 1)] & 0xffffu);
+        const float v = __uint_as_float((b & 0x7fffu) << 16) * inv;
+        o |= (e4m3_mag(v) | ((b >> 8) & 0x80u)) << (8 * h);
+      }
+      out[i] = o;
+    }
+  }
+  u32x4_t* dst = (u32x4_t*)(q + m * ldq + j * 32);
+  dst[0] = u32x4_t{out[0], out[1], out[2], out[3]};
+  dst[1] = u32x4_t{out[4], out[5], out[6], out[7]};
+  sc[m * ld_scale + j] = (uint8_t)sbyte;
+}
+
+// ---- GEMM ---------------------------------------------------------------------------------------------------------------
+template <int BN>
+struct CfgMx {
+  static_assert(BN == 256 || BN == 128, "256 x 256 and 256 x 128 tiles");
+  static constexpr bool M16 = true;
+  static constexpr int NTHREADS = 512;
+  static constexpr int BK = 128;                       // k per K-tile = bytes of a tile row = one MFMA k-step
+  static constexpr int MF = 4, NF = BN / 128;
+  static constexpr int A_BYTES = BM * BK, W_BYTES = BN * BK;
+  static constexpr int AS_OFF = A_BYTES + W_BYTES;     // dword of 4 scale bytes per row, A rows then W rows
+  static constexpr int WS_OFF = AS_OFF + BM * 4;
+  static constexpr int STAGE_BYTES = WS_OFF + BN * 4;
+  static constexpr int W_PIECES = BN / 64;             // 1 KiB DMA pieces (8 rows) of the W tile per wave
+  static constexpr int CT_LD = BN + 8;
+  static constexpr int CT_BYTES = BM * CT_LD * 2;
+  static constexpr int SMEM_BYTES = 2 * STAGE_BYTES > CT_BYTES ? 2 * STAGE_BYTES : CT_BYTES;
+  static FK_DEV int tile_row(int wm, int mf) { return (mf >> 1) * 128 + wm * 64 + (mf & 1) * 32; }
+  static FK_DEV int tile_col(int wn, int nf) { return nf * 128 + wn * 32; }
+};
+
+struct MxGroup {
+  fk_gemm_mxfp8_args p[FK_MAX_GROUP];
+  int tiles_before[FK_MAX_GROUP + 1];
+  int n;
+};
+constexpr int MX_GROUP_M = 8;   // depth (row tiles) of the grouped tile order
+
+template <int N>
+FK_DEV void wait_vm() {
+  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+  else static_assert(N == 0, "add the vmcnt literal");
+}
+
+template <int EPI, int BN>
+__global__ __launch_bounds__(512, 2) void gemm_mxfp8_kernel(const MxGroup ga) {
+  using C = CfgMx<BN>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int t = xcd_chunk_index();
+  int pi = 0;
+#pragma unroll
+  for (int i = 1; i < FK_MAX_GROUP; ++i)
+    if (i < ga.n && t >= ga.tiles_before[i]) pi = i;
+  const fk_gemm_mxfp8_args& P = ga.p[pi];
+  const fk_gemm_args& p = P.g;
+  int m0, n0;
+  {
+    const int tl = t - ga.tiles_before[pi];
+    const int nbm = (p.M + BM - 1) / BM, nbn = p.N / BN;
+    const int per_group = MX_GROUP_M * nbn;
+    const int g = tl / per_group, first_m = g * MX_GROUP_M;
+    const int gm = min(nbm - first_m, MX_GROUP_M), rem = tl - g * per_group;
+    m0 = (first_m + rem % gm) * BM;
+    n0 = (rem / gm) * BN;
+  }
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  const int nk = p.K / C::BK;
+  const int mlast = p.M - 1 - m0;   // rows past M are read as row M - 1 (never stored)
+
+  // ---- LDS-DMA sources.  Tile piece = 8 rows x 128 B, lane -> (row lane >> 3, slot lane & 7), source chunk slot ^ (row & 7);
+  // waves 0-3 fetch the A scale dwords of rows 64 w + lane, waves 4 .. 4 + BN / 64 - 1 those of W
+  const BufDesc da = make_buf_desc((const char*)P.A8 + (int64_t)m0 * P.lda8, 0x7fffffffu);
+  const BufDesc dw = make_buf_desc((const char*)P.W8 + (int64_t)n0 * P.ldw8, 0x7fffffffu);
+  const BufDesc dsa = make_buf_desc((const uint8_t*)P.A_scale + (int64_t)m0 * P.lda_scale, 0x7fffffffu);
+  const BufDesc dsw = make_buf_desc((const uint8_t*)P.W_scale + (int64_t)n0 * P.ldw_scale, 0x7fffffffu);
+  const int lrow = lane >> 3, slot = lane & 7;
+  int a_voff[4], w_voff[C::W_PIECES];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int r = (wave * 4 + j) * 8 + lrow;
+    a_voff[j] = min(r, mlast) * (int)P.lda8 + ((slot ^ (r & 7)) << 4);
+  }
+#pragma unroll
+  for (int j = 0; j < C::W_PIECES; ++j) {
+    const int r = (wave * C::W_PIECES + j) * 8 + lrow;
+    w_voff[j] = r * (int)P.ldw8 + ((slot ^ (r & 7)) << 4);
+  }
+  const bool sc_a = wave < 4, sc_w = !sc_a && wave < 4 + C::W_PIECES;
+  const int sc_voff = sc_a ? min(wave * 64 + lane, mlast) * (int)P.lda_scale : (wave - 4) * 64 * (int)P.ldw_scale + lane * (int)P.ldw_scale;
+  auto issue = [&](int stage, int kt) {
+    char* base = smem + stage * C::STAGE_BYTES;
+    // the scale piece first: the wait below counts only the tile pieces of the NEXT K-tile as still in flight
+    if (sc_a) buffer_lds_opaque<4>(dsa, lds_addr_of(base + C::AS_OFF + wave * 256), sc_voff, kt * 4);
+    else if (sc_w) buffer_lds_opaque<4>(dsw, lds_addr_of(base + C::WS_OFF + (wave - 4) * 256), sc_voff, kt * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) buffer_lds_opaque<16>(da, lds_addr_of(base + (wave * 4 + j) * 1024), a_voff[j], kt * C::BK);
+#pragma unroll
+    for (int j = 0; j < C::W_PIECES; ++j)
+      buffer_lds_opaque<16>(dw, lds_addr_of(base + C::A_BYTES + (wave * C::W_PIECES + j) * 1024), w_voff[j], kt * C::BK);
+  };
+
+  // ---- fragments: row (lane & 15) of a 16-row block, chunks g and 4 + g (g = lane >> 4); scale: byte g of the row's dword
+  const int frow = lane & 15, g = lane >> 4;
+  const int c0 = (g ^ (frow & 7)) << 4, c1 = ((4 + g) ^ (frow & 7)) << 4;
+  auto frag = [&](const char* tile, int row0) {
+    const char* rp = tile + (row0 + frow) * C::BK;
+    const u32x4_t lo = *(const u32x4_t*)(rp + c0), hi = *(const u32x4_t*)(rp + c1);
+    return i32x8_t{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+  };
+  auto scale = [&](const char* s, int row0) { return (int)(*(const uint32_t*)(s + (row0 + frow) * 4) >> (8 * g)); };
+
+  f32x16_t acc[C::NF][C::MF];
+#pragma unroll
+  for (int i = 0; i < C::NF; ++i)
+#pragma unroll
+    for (int j = 0; j < C::MF; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  issue(0, 0);
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt + 1 < nk) {
+      issue((kt + 1) & 1, kt + 1);   // its stage was last read before the trailing barrier of iteration kt - 1
+      wait_vm<4 + C::W_PIECES>();
+    } else {
+      wait_vm<0>();
+    }
+    __syncthreads();
+    const char* st = smem + (kt & 1) * C::STAGE_BYTES;
+    i32x8_t wf[C::NF][2];
+    int wsc[C::NF][2];
+#pragma unroll
+    for (int nf = 0; nf < C::NF; ++nf)
+#pragma unroll
+      for (int n16 = 0; n16 < 2; ++n16) {
+        const int r0 = C::tile_col(wn, nf) + 16 * n16;
+        wf[nf][n16] = frag(st + C::A_BYTES, r0);
+        wsc[nf][n16] = scale(st + C::WS_OFF, r0);
+      }
+#pragma unroll
+    for (int mf = 0; mf < C::MF; ++mf) {
+      i32x8_t af[2];
+      int asc[2];
+#pragma unroll
+      for (int m16 = 0; m16 < 2; ++m16) {
+        const int r0 = C::tile_row(wm, mf) + 16 * m16;
+        af[m16] = frag(st, r0);
+        asc[m16] = scale(st + C::AS_OFF, r0);
+      }
+#pragma unroll
+      for (int nf = 0; nf < C::NF; ++nf)
+#pragma unroll
+        for (int n16 = 0; n16 < 2; ++n16)
+#pragma unroll
+          for (int m16 = 0; m16 < 2; ++m16) {
+            const int q = 2 * n16 + m16;
+            // formats 0 / 0 = e4m3 x e4m3; scale byte 0 of each lane's scale register
+            quad_set(acc[nf][mf], q,
+                     __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[nf][n16], af[m16], quad_get(acc[nf][mf], q), 0, 0,
+                                                                       0, wsc[nf][n16], 0, asc[m16]));
+          }
+    }
+    __syncthreads();
+  }
+  store_tile<EPI, BN, C>(acc, p, smem, m0, n0, wm, wn);
+}
+
+int cu_count_mx() {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+    else return 256;
+  }
+  return cus;
+}
+
+template <int EPI, int BN>
+int launch_mx(MxGroup& ga, int tiles, hipStream_t stream) {
+  using C = CfgMx<BN>;
+  auto kern = gemm_mxfp8_kernel<EPI, BN>;
+  FK_ENSURE_MAX_LDS(kern, C::SMEM_BYTES, "fk_gemm_mxfp8");
+  hipLaunchKernelGGL(kern, dim3(tiles), dim3(C::NTHREADS), C::SMEM_BYTES, stream, ga);
+  FK_CHECK_LAUNCH("fk_gemm_mxfp8");
+  return FK_OK;
+}
+
+template <int EPI>
+int launch_mx_bn(MxGroup& ga, int tiles, int bn, hipStream_t stream) {
+  return bn == 256 ? launch_mx<EPI, 256>(ga, tiles, stream) : launch_mx<EPI, 128>(ga, tiles, stream);
+}
+
+// a 256-row tile's rows addressable with 32-bit byte offsets from its first row (what TileRows / the DMA offsets assume)
+bool rows32(const fk_rows& r, int elem) {
+  const long long ld = r.ld < 0 ? -r.ld : r.ld, bs = r.batch_stride < 0 ? -r.batch_stride : r.batch_stride;
+  if (r.ld < 0 || (BM * ld + (r.rows_per_batch > 0 ? bs : 0)) * elem >= (1ll << 31)) return false;
+  return !(r.rows_per_batch > 0 && r.batch_stride < r.rows_per_batch * r.ld);
+}
+
+int validate_mx(const fk_gemm_mxfp8_args& a, const char* fn) {
+  const fk_gemm_args& p = a.g;
+  FK_CHECK_ARG(a.A8 && a.A_scale && a.W8 && a.W_scale && p.C, "%s: null operand, scale or output pointer", fn);
+  FK_CHECK_ARG(p.M >= 0 && p.N > 0 && p.K > 0, "%s: M %d N %d K %d", fn, p.M, p.N, p.K);
+  if (p.K % 128 != 0 || p.N % 256 != 0) {
+    fk_set_error("%s: needs K %% 128 == 0 and N %% 256 == 0 (M %d N %d K %d)", fn, p.M, p.N, p.K);
+    return FK_EUNSUPPORTED;
+  }
+  if (!(p.out_fp32 == 0 || p.out_fp32 == 2) || p.layout != 0 || p.f32_flags != 0 ||
+      !(p.epilogue == FK_EPI_NONE || (p.out_fp32 == 0 && (p.epilogue == FK_EPI_GELU_TANH || p.epilogue == FK_EPI_GATE_RES ||
+                                                           p.epilogue == FK_EPI_QKV)))) {
+    fk_set_error("%s: epilogue %d / out_fp32 %d / layout %d: supported are FK_EPI_NONE, GELU_TANH, GATE_RES, QKV (bf16 out) "
+                 "and FK_EPI_NONE with out_fp32 = 2, layout 0", fn, p.epilogue, p.out_fp32, p.layout);
+    return FK_EUNSUPPORTED;
+  }
+  // the output / bias / residual / gate / QKV fields as fk_gemm_bf16 checks them (the epilogue is the same code)
+  FK_CHECK_ARG((uintptr_t)p.C % 16 == 0, "%s: C must be 16-byte aligned", fn);
+  if (p.out_fp32 == 2)
+    FK_CHECK_ARG(p.c.ld % 4 == 0 && (p.c.rows_per_batch <= 0 || p.c.batch_stride % 4 == 0) && (!p.bias || (uintptr_t)p.bias % 8 == 0),
+                 "%s: out_fp32 = 2 needs ldc %% 4 == 0 and an 8-byte aligned bias", fn);
+  else
+    FK_CHECK_ARG(p.c.ld % 8 == 0 && (p.c.rows_per_batch <= 0 || p.c.batch_stride % 8 == 0) && (!p.bias || (uintptr_t)p.bias % 8 == 0),
+                 "%s: ldc / C batch stride must be multiples of 8, bias 8-byte aligned", fn);
+  if (p.epilogue == FK_EPI_GATE_RES) {
+    FK_CHECK_ARG(p.res && (uintptr_t)p.res % 16 == 0 && p.r.ld % 8 == 0 && (p.r.rows_per_batch <= 0 || p.r.batch_stride % 8 == 0),
+                 "%s: residual pointer/stride invalid", fn);
+    FK_CHECK_ARG(p.gate && (uintptr_t)p.gate % 16 == 0 && p.gate_batch_stride % 8 == 0 && p.gate_rows_per_batch > 0,
+                 "%s: gate pointer/stride invalid", fn);
+  }
+  if (p.epilogue == FK_EPI_QKV) {
+    FK_CHECK_ARG(p.q_out && p.k_out && p.wq && p.wk && p.rope_cs, "%s: FK_EPI_QKV needs q_out, k_out, wq, wk and rope_cs", fn);
+    FK_CHECK_ARG(p.qkv_heads > 0 && (p.N == 3 * p.qkv_heads * 128 || p.N == 2 * p.qkv_heads * 128) && p.qkv_s_total > 0 &&
+                     p.qkv_s_offset >= 0,
+                 "%s: FK_EPI_QKV needs N = 3*H*128 (q | k | v) or 2*H*128 (q | k)", fn);
+    const int64_t rpb = p.c.rows_per_batch > 0 ? p.c.rows_per_batch : p.M;
+    const int64_t nb = p.c.rows_per_batch > 0 ? (p.M + p.c.rows_per_batch - 1) / p.c.rows_per_batch : 1;
+    FK_CHECK_ARG((int64_t)p.qkv_s_offset + rpb <= p.qkv_s_total, "%s: FK_EPI_QKV token rows s_offset %d + %lld exceed S_total %d",
+                 fn, p.qkv_s_offset, (long long)rpb, p.qkv_s_total);
+    FK_CHECK_ARG(nb * p.qkv_heads * p.qkv_s_total < (int64_t)1 << 31, "%s: FK_EPI_QKV head-major outputs are limited to 2^31 rows", fn);
+    FK_CHECK_ARG(((uintptr_t)p.q_out | (uintptr_t)p.k_out | (uintptr_t)p.wq | (uintptr_t)p.wk | (uintptr_t)p.rope_cs) % 16 == 0,
+                 "%s: FK_EPI_QKV pointers must be 16-byte aligned", fn);
+  }
+  FK_CHECK_ARG(a.lda8 >= p.K && a.lda8 % 16 == 0 && a.ldw8 >= p.K && a.ldw8 % 16 == 0 &&
+               a.lda_scale >= p.K / 32 && a.lda_scale % 4 == 0 && a.ldw_scale >= p.K / 32 && a.ldw_scale % 4 == 0,
+               "%s: operand rows need ld >= K, ld %% 16 == 0; scale rows ld >= K / 32, ld %% 4 == 0 (lda8 %lld ldw8 %lld "
+               "lda_scale %lld ldw_scale %lld)", fn, (long long)a.lda8, (long long)a.ldw8, (long long)a.lda_scale,
+               (long long)a.ldw_scale);
+  FK_CHECK_ARG(((uintptr_t)a.A8 | (uintptr_t)a.W8) % 16 == 0 && ((uintptr_t)a.A_scale | (uintptr_t)a.W_scale) % 4 == 0,
+               "%s: operands must be 16-byte, scales 4-byte aligned", fn);
+  const bool res = p.epilogue == FK_EPI_GATE_RES;
+  if ((long long)BM * a.lda8 >= (1ll << 31) || (long long)BM * a.ldw8 >= (1ll << 31) || (long long)BM * a.lda_scale >= (1ll << 31) ||
+      (long long)BM * a.ldw_scale >= (1ll << 31) || !rows32(p.c, p.out_fp32 == 2 ? 4 : 2) || (res && !rows32(p.r, 2))) {
+    fk_set_error("%s: row strides must keep a 256-row tile within 2 GiB", fn);
+    return FK_EUNSUPPORTED;
+  }
+  return FK_OK;
+}
+}  // namespace
+
+extern "C" int fk_quantize_mxfp8(const void* x, fk_rows xr, int64_t M, int32_t K, void* q, int64_t ldq, void* scales,
+                                 int64_t ld_scale, fk_stream_t stream) {
+  FK_CHECK_ARG(x && q && scales, "fk_quantize_mxfp8: null pointer");
+  FK_CHECK_ARG(M >= 0 && K > 0, "fk_quantize_mxfp8: M %lld K %d", (long long)M, K);
+  if (K % 32 != 0) {
+    fk_set_error("fk_quantize_mxfp8: K %% 32 == 0 needed (K %d)", K);
+    return FK_EUNSUPPORTED;
+  }
+  FK_CHECK_ARG(xr.ld >= K && xr.ld % 8 == 0 && (uintptr_t)x % 16 == 0 && (xr.rows_per_batch <= 0 || xr.batch_stride % 8 == 0),
+               "fk_quantize_mxfp8: x rows must be 16-byte aligned with ld >= K");
+  FK_CHECK_ARG(ldq >= K && ldq % 16 == 0 && (uintptr_t)q % 16 == 0 && ld_scale >= K / 32,
+               "fk_quantize_mxfp8: q rows 16-byte aligned with ldq >= K, ld_scale >= K / 32");
+  if (M == 0) return FK_OK;
+  const int64_t blocks = M * (K / 32);
+  const int64_t grid = (blocks + 255) / 256;
+  FK_CHECK_ARG(grid < (1ll << 31), "fk_quantize_mxfp8: too many rows");
+  hipLaunchKernelGGL(quantize_mxfp8_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, xr, M, K,
+                     (uint8_t*)q, ldq, (uint8_t*)scales, ld_scale);
+  FK_CHECK_LAUNCH("fk_quantize_mxfp8");
+  return FK_OK;
+}
+
+// fk_gemm_args.variant_used: 128 / 256 = the 256 x 128 / 256 x 256 tile
+extern "C" int fk_gemm_mxfp8_grouped(const fk_gemm_mxfp8_args* args, int32_t n, fk_stream_t stream_) {
+  FK_CHECK_ARG(args != nullptr && n >= 1 && n <= FK_MAX_GROUP, "fk_gemm_mxfp8_grouped: 1 <= n <= %d", FK_MAX_GROUP);
+  const fk_gemm_args& c0 = args[0].g;
+  for (int i = 0; i < n; ++i) {
+    const int rc = validate_mx(args[i], n == 1 ? "fk_gemm_mxfp8" : "fk_gemm_mxfp8_grouped");
+    if (rc != FK_OK) return rc;
+    FK_CHECK_ARG(args[i].g.N == c0.N && args[i].g.K == c0.K && args[i].g.epilogue == c0.epilogue &&
+                 args[i].g.out_fp32 == c0.out_fp32, "fk_gemm_mxfp8_grouped: all problems must share N, K, epilogue and out_fp32");
+  }
+  FK_CHECK_ARG(c0.variant == 0 || c0.variant == 128 || c0.variant == 256, "fk_gemm_mxfp8: variant %d is not 0, 128 or 256",
+               c0.variant);
+  MxGroup ga;
+  ga.n = n;
+  long nbm = 0;
+  ga.tiles_before[0] = 0;
+  for (int i = 0; i < FK_MAX_GROUP; ++i) ga.p[i] = args[i < n ? i : 0];
+  for (int i = 0; i < n; ++i) nbm += (args[i].g.M + BM - 1) / BM;
+  // launch plan: 256 x 256 tiles unless they leave part of the chip idle in a single round (then twice as many 256 x 128 ones)
+  const long t256 = nbm * (c0.N / 256);
+  const int bn = c0.variant ? c0.variant : (t256 < cu_count_mx() ? 128 : 256);
+  long tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    ga.tiles_before[i] = (int)tiles;
+    tiles += (long)((args[i].g.M + BM - 1) / BM) * (c0.N / bn);
+  }
+  for (int i = n; i <= FK_MAX_GROUP; ++i) ga.tiles_before[i] = (int)tiles;
+  if (c0.variant_used) *c0.variant_used = bn;
+  if (tiles == 0) return FK_OK;
+  FK_CHECK_ARG(tiles < (1l << 31), "fk_gemm_mxfp8: too many tiles");
+  hipStream_t stream = (hipStream_t)stream_;
+  switch (c0.out_fp32 == 2 ? FK_EPI_F32DBG : c0.epilogue) {
+    case FK_EPI_F32DBG: return launch_mx_bn<FK_EPI_F32DBG>(ga, (int)tiles, bn, stream);
+    case FK_EPI_NONE: return launch_mx_bn<FK_EPI_NONE>(ga, (int)tiles, bn, stream);
+    case FK_EPI_GELU_TANH: return launch_mx_bn<FK_EPI_GELU_TANH>(ga, (int)tiles, bn, stream);
+    case FK_EPI_GATE_RES: return launch_mx_bn<FK_EPI_GATE_RES>(ga, (int)tiles, bn, stream);
+    case FK_EPI_QKV: return launch_mx_bn<FK_EPI_QKV>(ga, (int)tiles, bn, stream);
+    default: fk_set_error("fk_gemm_mxfp8: unknown epilogue %d", c0.epilogue); return FK_EUNSUPPORTED;
+  }
+}
+
+extern "C" int fk_gemm_mxfp8(const fk_gemm_mxfp8_args* args, fk_stream_t stream) {
+  FK_CHECK_ARG(args != nullptr, "fk_gemm_mxfp8: null args");
+  return fk_gemm_mxfp8_grouped(args, 1, stream);
+}

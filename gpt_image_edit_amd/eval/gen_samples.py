@@ -118,6 +118,8 @@ def build_parser():
                    help="all-gather the finished packed latents (one collective); re-edits items whose output already exists, "
                         "since their latents are not on disk")
     p.add_argument("--latents_out", type=str, default=None)
+    p.add_argument("--weight_format", choices=("bf16", "mxfp8"), default="bf16",
+                   help="block GEMM weights: bf16, or opt-in OCP MXFP8 (inference only)")
     return p
 
 
@@ -156,7 +158,8 @@ def main(args):
     torch.cuda.set_device(device)
     set_seed(args.seed, rank)
     from ..serve import cli
-    pipe, tokenizers, text_encoders = cli.load_pipe(args.model_path, args.flux_path, device)
+    pipe, tokenizers, text_encoders = cli.load_pipe(args.model_path, args.flux_path, device,
+                                                    weight_format=getattr(args, "weight_format", "bf16"))
     if args.t5_only:
         def edit_fn(prompt, image_path):
             return cli.run_t5_only(pipe, text_encoders, tokenizers, prompt, image1=image_path, args=args)[0], None

@@ -38,6 +38,14 @@ class GemmArgs(ctypes.Structure):
     ]
 
 
+class GemmMxfp8Args(ctypes.Structure):   # fk_gemm_mxfp8_args
+    _fields_ = [
+        ("g", GemmArgs),
+        ("A8", c_vp), ("lda8", c_i64), ("A_scale", c_vp), ("lda_scale", c_i64),
+        ("W8", c_vp), ("ldw8", c_i64), ("W_scale", c_vp), ("ldw_scale", c_i64),
+    ]
+
+
 class AttnView(ctypes.Structure):
     _fields_ = [("p", c_vp), ("ld", c_i64), ("head_stride", c_i64), ("batch_stride", c_i64)]
 
@@ -98,10 +106,33 @@ class SingleBlockWeights(ctypes.Structure):   # fk_single_block_weights
     _fields_ = [(n, c_vp) for n in SINGLE_BLOCK_FIELDS] + [("mod_off", c_i64)]
 
 
+class MxPair(ctypes.Structure):               # fk_mx_pair: e4m3 [N, K] + E8M0 [N, K / 32], dense
+    _fields_ = [("q", c_vp), ("s", c_vp)]
+
+
+DOUBLE_BLOCK_MX_FIELDS = ("qkv_img", "qkv_txt", "out", "add_out", "ff1", "ff1_ctx", "ff2", "ff2_ctx")
+SINGLE_BLOCK_MX_FIELDS = ("qkv", "mlp", "out")
+
+
+class DoubleBlockWeightsMx(ctypes.Structure):   # fk_double_block_weights_mx
+    _fields_ = [(n, MxPair) for n in DOUBLE_BLOCK_MX_FIELDS]
+
+
+class SingleBlockWeightsMx(ctypes.Structure):   # fk_single_block_weights_mx
+    _fields_ = [(n, MxPair) for n in SINGLE_BLOCK_MX_FIELDS]
+
+
+class MxWs(ctypes.Structure):                 # fk_mx_ws
+    _fields_ = [("q", c_vp), ("s", c_vp), ("q_bytes", c_i64), ("s_bytes", c_i64)]
+
+
 # symbol -> (restype, argtypes); must list every entry point of include/fk.h
 SIGNATURES = {
     "fk_gemm_bf16": (c_i32, [ctypes.POINTER(GemmArgs), c_vp]),
     "fk_gemm_bf16_grouped": (c_i32, [ctypes.POINTER(GemmArgs), c_i32, c_vp]),
+    "fk_quantize_mxfp8": (c_i32, [c_vp, Rows, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "fk_gemm_mxfp8": (c_i32, [ctypes.POINTER(GemmMxfp8Args), c_vp]),
+    "fk_gemm_mxfp8_grouped": (c_i32, [ctypes.POINTER(GemmMxfp8Args), c_i32, c_vp]),
     "fk_ln_modulate_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_f32, c_vp]),
     "fk_ln_modulate2_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_f32, c_vp]),
     "fk_qkv_post_bf16": (c_i32, [c_vp] * 9 + [c_i32] * 4 + [c_f32, c_vp]),
@@ -161,6 +192,13 @@ SIGNATURES = {
                                     ctypes.POINTER(SingleBlockGrads), c_vp]),
     "fk_double_block_bwd": (c_i32, [ctypes.POINTER(BwdWs), ctypes.POINTER(BlockSaved), ctypes.POINTER(DoubleBlockWeights),
                                     ctypes.POINTER(DoubleBlockGrads), c_vp]),
+    "fk_double_block_fwd_mx": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(MxWs), ctypes.POINTER(DoubleBlockWeights),
+                                       ctypes.POINTER(DoubleBlockWeightsMx), c_vp, c_i64, c_vp]),
+    "fk_single_block_fwd_mx": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(MxWs), ctypes.POINTER(SingleBlockWeights),
+                                       ctypes.POINTER(SingleBlockWeightsMx), c_vp, c_i64, c_vp]),
+    "fk_mmdit_blocks_fwd_mx": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(MxWs), ctypes.POINTER(DoubleBlockWeights),
+                                       ctypes.POINTER(DoubleBlockWeightsMx), c_i32, ctypes.POINTER(SingleBlockWeights),
+                                       ctypes.POINTER(SingleBlockWeightsMx), c_i32, c_vp, c_i64, c_vp]),
     "fk_mmdit_blocks_fwd": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(DoubleBlockWeights), c_i32,
                                     ctypes.POINTER(SingleBlockWeights), c_i32, c_vp, c_i64, c_vp]),
     "fk_last_error": (ctypes.c_char_p, []),

@@ -12,7 +12,7 @@ import torch
 
 from . import libfk, param_tree
 from .libfk import (FK_EPI_GATE_RES, FK_EPI_GELU_TANH, FK_EPI_NONE, FK_EPI_QKV, FK_EPI_RES, FK_EPI_SCALE,  # noqa: F401
-                    FK_EPI_SILU, GemmArgs, Rows)
+                    FK_EPI_SILU, GemmArgs, GemmMxfp8Args, Rows)
 
 BF16 = torch.bfloat16
 
@@ -149,15 +149,20 @@ def _gemm_args(a, w, bias, out, epilogue, res, gate, out_fp32, alpha, qkv=None, 
         ws, slots = splitk_workspace(a.device)
         args.splitk_ws, args.splitk_slots = ws.data_ptr(), slots
     if epilogue == FK_EPI_QKV:
-        cs = qkv["cs"] if "cs" in qkv else pack_rope(qkv["cos"], qkv["sin"])
-        _need_cuda(qkv["q_out"], qkv["k_out"], qkv["wq"], qkv["wk"], cs)
-        if cs.dtype != torch.float32 or not cs.is_contiguous() or tuple(cs.shape) != (qkv["q_out"].shape[2], 64, 2):
-            raise ValueError("cs must be a contiguous fp32 [S_total, 64, 2] table (see pack_rope)")
-        args.q_out, args.k_out = qkv["q_out"].data_ptr(), qkv["k_out"].data_ptr()
-        args.wq, args.wk = qkv["wq"].data_ptr(), qkv["wk"].data_ptr()
-        args.rope_cs = cs.data_ptr()
-        args.qkv_s_offset, args.qkv_s_total, args.qkv_heads = qkv["s_offset"], qkv["q_out"].shape[2], qkv["q_out"].shape[1]
+        _set_qkv(args, qkv)
     return args, out
+
+
+def _set_qkv(args, qkv):
+    """The FK_EPI_QKV fields of a GemmArgs from gemm()'s ``qkv`` dict."""
+    cs = qkv["cs"] if "cs" in qkv else pack_rope(qkv["cos"], qkv["sin"])
+    _need_cuda(qkv["q_out"], qkv["k_out"], qkv["wq"], qkv["wk"], cs)
+    if cs.dtype != torch.float32 or not cs.is_contiguous() or tuple(cs.shape) != (qkv["q_out"].shape[2], 64, 2):
+        raise ValueError("cs must be a contiguous fp32 [S_total, 64, 2] table (see pack_rope)")
+    args.q_out, args.k_out = qkv["q_out"].data_ptr(), qkv["k_out"].data_ptr()
+    args.wq, args.wk = qkv["wq"].data_ptr(), qkv["wk"].data_ptr()
+    args.rope_cs = cs.data_ptr()
+    args.qkv_s_offset, args.qkv_s_total, args.qkv_heads = qkv["s_offset"], qkv["q_out"].shape[2], qkv["q_out"].shape[1]
 
 
 def gemm(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=None, out_fp32=False, alpha=1.0, qkv=None, layout=0):
@@ -266,6 +271,98 @@ def gemm_grouped(problems, epilogue=FK_EPI_NONE):
         arr[i] = args
         outs.append(out)
     libfk.check(libfk.load().fk_gemm_bf16_grouped(arr, n, _stream()), "fk_gemm_bf16_grouped")
+    return outs
+
+
+# ---- MXFP8 (opt-in inference format of the block GEMMs; include/fk.h) --------------------------------------------------------
+MXFP8_BLOCK = 32
+
+
+def quantize_mxfp8(x, q=None, scales=None):
+    """OCP MXFP8 of a bf16 [M, K] / [B, R, K] view (last dimension contiguous, K % 32 == 0): returns (q, scales), q uint8
+    [M, K] holding e4m3fn codes of x / 2^e (round-to-nearest-even, saturated to +-448) and scales uint8 [M, K / 32] holding
+    the E8M0 byte e + 127 of every block of 32 consecutive elements, e = max(floor(log2(amax)) - 8, -127).  An all-zero block
+    has scale byte 127; a block holding Inf / NaN has scale 0xFF and elements 0x7F (NaN).  Weights [N, K] go through the
+    same call once at pack time."""
+    _need_cuda(x, q, scales)
+    if x.dtype != BF16:
+        raise TypeError("quantize_mxfp8 takes a bf16 tensor")
+    M, rx = rows_of(x)
+    K = x.shape[-1]
+    if q is None:
+        q = torch.empty((M, K), device=x.device, dtype=torch.uint8)
+    if scales is None:
+        scales = torch.empty((M, K // MXFP8_BLOCK), device=x.device, dtype=torch.uint8)
+    if (q.dtype != torch.uint8 or scales.dtype != torch.uint8 or q.dim() != 2 or scales.dim() != 2 or tuple(q.shape) != (M, K)
+            or tuple(scales.shape) != (M, K // MXFP8_BLOCK) or q.stride(1) != 1 or scales.stride(1) != 1):
+        raise ValueError(f"quantize_mxfp8: q must be uint8 [{M}, {K}] and scales uint8 [{M}, {K // MXFP8_BLOCK}], rows contiguous")
+    libfk.check(libfk.load().fk_quantize_mxfp8(x.data_ptr(), rx, M, K, q.data_ptr(), q.stride(0), scales.data_ptr(),
+                                                scales.stride(0), _stream()), "fk_quantize_mxfp8")
+    return q, scales
+
+
+def _mx_args(a, w, bias, out, epilogue, res, gate, out_fp32, qkv, variant):
+    (aq, asc), (wq, wsc) = a, w
+    _need_cuda(aq, asc, wq, wsc, bias, out, res, gate)
+    for t in (aq, asc, wq, wsc):
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.stride(1) != 1:
+            raise TypeError("gemm_mxfp8 operands are (uint8 e4m3 [rows, K], uint8 E8M0 [rows, K / 32]) pairs (quantize_mxfp8)")
+    M, K = aq.shape
+    N = wq.shape[0]
+    if wq.shape[1] != K or tuple(asc.shape) != (M, K // MXFP8_BLOCK) or tuple(wsc.shape) != (N, K // MXFP8_BLOCK):
+        raise ValueError(f"gemm_mxfp8: a {tuple(aq.shape)} / {tuple(asc.shape)} vs w {tuple(wq.shape)} / {tuple(wsc.shape)}")
+    if out is None:
+        out = torch.empty((M, N), device=aq.device, dtype=torch.float32 if out_fp32 else BF16)
+    Mo, rc = rows_of(out)
+    if Mo != M or out.shape[-1] != N:
+        raise ValueError(f"output shape {tuple(out.shape)} does not match M={M}, N={N}")
+    args = GemmMxfp8Args()
+    g = args.g
+    g.bias = bias.data_ptr() if bias is not None else None
+    g.C, g.c = out.data_ptr(), rc
+    if res is not None:
+        Mr, rr = rows_of(res)
+        if Mr != M:
+            raise ValueError("residual rows mismatch")
+        g.res, g.r = res.data_ptr(), rr
+    if gate is not None:
+        if out.dim() != 3 or gate.dim() != 2 or gate.shape[0] != out.shape[0] or gate.stride(1) != 1:
+            raise ValueError("gate must be a [B, N] view matching a 3-D output")
+        g.gate, g.gate_batch_stride, g.gate_rows_per_batch = gate.data_ptr(), gate.stride(0), out.shape[1]
+    g.M, g.N, g.K = M, N, K
+    g.epilogue, g.out_fp32 = epilogue, 2 if out_fp32 else 0
+    g.variant = int(variant)
+    g.variant_used = ctypes.pointer(_variant_slot())
+    if epilogue == FK_EPI_QKV:
+        _set_qkv(g, qkv)
+    args.A8, args.lda8, args.A_scale, args.lda_scale = aq.data_ptr(), aq.stride(0), asc.data_ptr(), asc.stride(0)
+    args.W8, args.ldw8, args.W_scale, args.ldw_scale = wq.data_ptr(), wq.stride(0), wsc.data_ptr(), wsc.stride(0)
+    return args, out
+
+
+def gemm_mxfp8(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=None, out_fp32=False, qkv=None, variant=0):
+    """out = epilogue(deq(a) @ deq(w).T + bias) on the block-scaled MFMA, fp32 accumulation; the epilogues (FK_EPI_NONE,
+    GELU_TANH, GATE_RES, QKV) round exactly like :func:`gemm`'s.  ``a`` / ``w``: the (q, scales) pairs of
+    :func:`quantize_mxfp8` ([M, K] / [N, K]); out [M, N] or a [B, R, N] view (may alias res; with ``gate`` it must be 3-D).
+    out_fp32: fp32(acc + bias) from the same main loop (parity build).  variant: 0 = launch plan, 128 / 256 = 256 x 128 /
+    256 x 256 tiles.  K % 128 == 0, N % 256 == 0."""
+    args, out = _mx_args(a, w, bias, out, epilogue, res, gate, out_fp32, qkv, variant)
+    libfk.check(libfk.load().fk_gemm_mxfp8(ctypes.byref(args), _stream()), "fk_gemm_mxfp8")
+    return out
+
+
+def gemm_mxfp8_grouped(problems, epilogue=FK_EPI_NONE, out_fp32=False, variant=0):
+    """Up to 4 MXFP8 GEMMs sharing (N, K, epilogue) in ONE launch; ``problems``: dicts with the keyword arguments of
+    :func:`gemm_mxfp8` (a, w, bias, out, res, gate, qkv).  Returns the outputs."""
+    n = len(problems)
+    arr = (GemmMxfp8Args * n)()
+    outs = []
+    for i, pr in enumerate(problems):
+        args, out = _mx_args(pr["a"], pr["w"], pr.get("bias"), pr.get("out"), epilogue, pr.get("res"), pr.get("gate"),
+                             out_fp32, pr.get("qkv"), variant)
+        arr[i] = args
+        outs.append(out)
+    libfk.check(libfk.load().fk_gemm_mxfp8_grouped(arr, n, _stream()), "fk_gemm_mxfp8_grouped")
     return outs
 
 

@@ -28,19 +28,21 @@ seed = 42  # cli.py:20-26 seeds everything with 42 and draws the edit's noise fr
 generate_image_temp = "./generate_image_{}.png"
 
 
-def load_pipe(denoiser, flux_path, device):
+def load_pipe(denoiser, flux_path, device, weight_format="bf16"):
     """``FluxKontextPipeline.from_pretrained(flux_path, transformer=denoiser, torch_dtype=bf16).to(device)``.
 
     ``denoiser``: a ``HipFluxTransformer2DModel``, or a checkpoint directory (a UniWorld model directory with
     ``denoise_tower.denoiser.*`` keys, cli.py:127, or a diffusers FLUX directory), or None = ``flux_path``'s own
     transformer.  Returns (pipe, tokenizers, text_encoders) like the reference; the T5/CLIP encoders are loaded
-    with ``transformers`` when ``flux_path`` holds them, else the two lists contain None."""
+    with ``transformers`` when ``flux_path`` holds them, else the two lists contain None.  ``weight_format``: "bf16" or
+    "mxfp8" (``HipFluxTransformer2DModel.set_weight_format``: opt-in MXFP8 block GEMMs, inference only)."""
     if not isinstance(denoiser, HipFluxTransformer2DModel):
         src = denoiser or flux_path
         cfg = checkpoint.flux_transformer_config(flux_path) if os.path.isdir(os.path.join(flux_path, "transformer")) else None
         model = HipFluxTransformer2DModel(cfg, device=device)
         checkpoint.load_flux_transformer(model, src)
         denoiser = model
+    denoiser.set_weight_format(weight_format)
     vae = HipAutoencoderKL(device=device)
     checkpoint.load_vae(vae, flux_path)
     sched = FlowMatchEulerDiscreteScheduler(**checkpoint.scheduler_config(flux_path))
@@ -156,12 +158,15 @@ def build_parser():
     parser.add_argument("--output", type=str, default=generate_image_temp.format(0))
     parser.add_argument("--t5_only", type=str, default=None, metavar="INSTRUCTION",
                         help="one edit from T5 + CLIP embeddings of INSTRUCTION only (no VLM), with --images")
+    parser.add_argument("--weight_format", choices=("bf16", "mxfp8"), default="bf16",
+                        help="block GEMM weights: bf16, or opt-in OCP MXFP8 (e4m3 + E8M0 per 32; inference only)")
     return parser
 
 
 def main(args):
     device = torch.device("cuda")
-    pipe, tokenizers, text_encoders = load_pipe(args.model_path, args.flux_path, device)
+    pipe, tokenizers, text_encoders = load_pipe(args.model_path, args.flux_path, device,
+                                                weight_format=getattr(args, "weight_format", "bf16"))
     if args.prompt_embeds:
         blob = torch.load(args.prompt_embeds, map_location="cpu", weights_only=True)
         urls = [u.strip() for u in args.images.split(",") if u.strip()]

@@ -66,7 +66,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
     parameter-holding sub-modules (``param_tree.ParamNode``), so the reference's ``named_modules()`` selection
     (``train_denoiser.py:538-543``), ``named_parameters()`` and ``state_dict()`` see the names of Appendix C."""
 
-    def __init__(self, config=None, device="cuda", dtype=BF16, init="empty", seed=0):
+    def __init__(self, config=None, device="cuda", dtype=BF16, init="empty", seed=0, weight_format="bf16"):
         super().__init__()
         if dtype != BF16:
             raise ValueError("the HIP path computes in bf16 (fp32 accumulate); dtype must be torch.bfloat16")
@@ -91,6 +91,23 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         self._rope_cache = {}
         self._freqs = None
         self._cond = None
+        self.weight_format = "bf16"
+        self.set_weight_format(weight_format)
+
+    # ---- weight format of the block GEMMs (a model attribute: config.json and save_pretrained stay bf16) -------------------
+    WEIGHT_FORMATS = ("bf16", "mxfp8")
+
+    def set_weight_format(self, weight_format):
+        """``"bf16"`` (default) or ``"mxfp8"``: the inference forward's block Linears (fused QKV, to_out / to_add_out,
+        ff / ff_context, proj_mlp, proj_out) run as OCP MXFP8 GEMMs -- weights quantized once at pack time, activations per
+        launch (``fk_quantize_mxfp8``), fp32 accumulation, the bf16 epilogues unchanged.  Everything else (embedders,
+        modulation, attention, norms, output head) stays bf16.  MXFP8 is an inference format: grad-enabled calls
+        (``_forward_train``) compute in bf16 whatever the format.  The stored parameters stay bf16."""
+        if weight_format not in self.WEIGHT_FORMATS:
+            raise ValueError(f"weight_format must be one of {self.WEIGHT_FORMATS}, got {weight_format!r}")
+        if weight_format != self.weight_format:
+            self.weight_format = weight_format
+            self._packed = None          # the next forward re-packs (and bumps _pack_serial: a captured loop graph is re-made)
 
     # ---- state dict: the module tree carries the diffusers key names (no mangling) ----------------------------
     def load_state_dict(self, state_dict, strict=True, **kwargs):
@@ -118,7 +135,8 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         """The fused operands, rebuilt when a source parameter of a fused COPY was rewritten since it was made (an optimiser
         step, ``param.data = ...``) or an aliased source moved: the check is one (data_ptr, version) tuple."""
         pk = self._packed
-        if pk is None or pk.versions != self.param_versions(pk.sources) or pk.alias_ptrs != self._ptrs(pk.aliased):
+        if (pk is None or pk.format != self._pack_format() or pk.versions != self.param_versions(pk.sources)
+                or pk.alias_ptrs != self._ptrs(pk.aliased)):
             pk = self.pack_weights()
         return pk
 
@@ -156,9 +174,37 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
                 torch.cat([self.p(n).data for n in names], out=t)
         pk.versions = self.param_versions(pk.sources)        # `changed` is everything that was rewritten: current again
 
+    def _pack_format(self):
+        # training packs (optimiser-owned parameters) never carry quantized copies: the training forward is bf16
+        return "bf16" if self._train_packs else self.weight_format
+
+    # the block Linears of the MXFP8 format that are not part of a fused QKV operand, per block
+    MX_DOUBLE = (("out", "attn.to_out.0.weight"), ("add_out", "attn.to_add_out.weight"), ("ff1", "ff.net.0.proj.weight"),
+                 ("ff1_ctx", "ff_context.net.0.proj.weight"), ("ff2", "ff.net.2.weight"), ("ff2_ctx", "ff_context.net.2.weight"))
+    MX_SINGLE = (("mlp", "proj_mlp.weight"), ("out", "proj_out.weight"))
+
+    def _pack_mx(self, pk):
+        """Quantize every block GEMM weight once (fk_quantize_mxfp8): (e4m3 [N, K], E8M0 [N, K / 32]) pairs.  Their bf16
+        sources join the version check, so an in-place write (``param.data.copy_``, ``load_state_dict``) re-quantizes."""
+        pk.mx_double, pk.mx_single = [], []
+        for i, blk in enumerate(pk.double):
+            p = f"transformer_blocks.{i}."
+            m = SimpleNamespace(qkv_img=ops.quantize_mxfp8(blk.wqkv_img), qkv_txt=ops.quantize_mxfp8(blk.wqkv_txt))
+            for f, n in self.MX_DOUBLE:
+                setattr(m, f, ops.quantize_mxfp8(self.p(p + n).data))
+                pk.sources.append(p + n)
+            pk.mx_double.append(m)
+        for i, blk in enumerate(pk.single):
+            p = f"single_transformer_blocks.{i}."
+            m = SimpleNamespace(qkv=ops.quantize_mxfp8(blk.wqkv))
+            for f, n in self.MX_SINGLE:
+                setattr(m, f, ops.quantize_mxfp8(self.p(p + n).data))
+                pk.sources.append(p + n)
+            pk.mx_single.append(m)
+
     def pack_weights(self):
         c, D = self.config, self.inner_dim
-        pk = SimpleNamespace(double=[], single=[], sources=[], aliased=[], copies=[])
+        pk = SimpleNamespace(double=[], single=[], sources=[], aliased=[], copies=[], format=self._pack_format())
         mod_w, mod_b, mod_names, off = [], [], [], 0
         qkv = lambda p, trio, wb: [p + f"attn.{n}.{wb}" for n in trio]  # noqa: E731
         for i in range(c.num_layers):
@@ -200,6 +246,8 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
             pk.mod_w = torch.cat([self.p(n + ".weight") for n in mod_names]).contiguous()
             pk.mod_b = torch.cat([self.p(n + ".bias") for n in mod_names]).contiguous()
             pk.sources += pk.mod_sources
+        if pk.format == "mxfp8":
+            self._pack_mx(pk)
         pk.versions, pk.alias_ptrs = self.param_versions(pk.sources), self._ptrs(pk.aliased)
         self.__dict__["_pack_serial"] = pk.serial = self.__dict__.get("_pack_serial", 0) + 1
         self._packed = pk
@@ -220,7 +268,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
             s=e(B, S, D), n=e(B, S, D), qkv=e(B, S, 3 * D), q=e(B, H, S, 128), k=e(B, H, S, 128),
             o=e(B, S, D), ff=e(B, S, 4 * D), cat=e(B, S, 5 * D),
             mod=e(B, self._packed.mod_total), temb=e(B, D), act=e(B, D), tproj=e(B, 256), e1=e(B, D),
-            t_emb=e(B, D), g_emb=e(B, D), p_emb=e(B, D),
+            t_emb=e(B, D), g_emb=e(B, D), p_emb=e(B, D), mxq=None, mxs=None,
         )
         self._ws = {key: ws}  # keep only the latest shape
         return ws
@@ -334,7 +382,8 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         records ONE autograd node (``_FluxTrainFunction``): its forward is ``backward.FluxBackward.forward`` (the HIP
         training forward), its backward ``FluxBackward.backward`` -- so the reference's ``accelerator.backward(loss)``
         (``train_denoiser.py:1172``) fills ``.grad`` of exactly the parameters it un-froze and any stock optimiser
-        can step them.  Otherwise (inference) nothing is recorded."""
+        can step them.  Otherwise (inference) nothing is recorded.  The training path computes in bf16 whatever
+        ``weight_format`` says: MXFP8 is an inference format."""
         if not hidden_states.is_cuda:
             raise RuntimeError("HipFluxTransformer2DModel needs GPU tensors: there is no CPU fallback")
         if joint_attention_kwargs and joint_attention_kwargs.get("attention_mask") is not None:
@@ -402,7 +451,17 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
 
         block_api = BLOCK_API if (FUSE_QKV and not MLP_FIRST and not (OVERLAP_MLP and (OVERLAP_MLP != "auto" or self._overlap_pays(B, ws.S)))
                                   and S_txt > 0) else 0
-        if block_api:
+        if pk.format == "mxfp8":
+            if ws.mxq is None:   # quantized activations of one launch: at most B * S rows of K = 5D
+                ws.mxq = torch.empty(B * ws.S * 5 * D, device=s.device, dtype=torch.uint8)
+                ws.mxs = torch.empty(B * ws.S * 5 * D // 32, device=s.device, dtype=torch.uint8)
+            if S_txt == 0:
+                raise ValueError("the mxfp8 weight format needs a text stream (S_txt > 0)")
+            if BLOCK_API:
+                self._blocks_by_c_entry(ws, pk, mod, cs, B, S_txt, S_img, BLOCK_API)
+            else:
+                self._blocks_by_kernel_calls_mx(ws, pk, mod, cs, S_txt)
+        elif block_api:
             self._blocks_by_c_entry(ws, pk, mod, cs, B, S_txt, S_img, block_api)
         else:
             self._blocks_by_kernel_calls(ws, pk, mod, cos, sin, cs, B, S_txt)
@@ -506,6 +565,69 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
                      epilogue=ops.FK_EPI_GATE_RES, res=s, gate=chunk(m0, 2))
 
 
+    def _blocks_by_kernel_calls_mx(self, ws, pk, mod, cs, S_txt):
+        """MXFP8 blocks as one ctypes call per launch (FK_BLOCK_API=0): the launches of fk_double_block_fwd_mx /
+        fk_single_block_fwd_mx in their order -- each block GEMM as quantize (activation) + gemm_mxfp8 -- hence their bits."""
+        P, D = self.p, self.inner_dim
+        s, n = ws.s, ws.n
+        h, cx = s[:, S_txt:], s[:, :S_txt]
+        n_img, n_txt = n[:, S_txt:], n[:, :S_txt]
+
+        def chunk(off, j):
+            return mod[:, off + j * D: off + (j + 1) * D]
+
+        def mm(problems, epilogue):
+            for pr in problems:
+                pr["a"] = ops.quantize_mxfp8(pr["a"])
+            ops.gemm_mxfp8_grouped(problems, epilogue=epilogue)
+
+        for i, (blk, w) in enumerate(zip(pk.double, pk.mx_double)):
+            p = f"transformer_blocks.{i}."
+            mi, mt = blk.mod_img, blk.mod_txt
+            ops.ln_modulate2(s, chunk(mt, 0), chunk(mt, 1), chunk(mi, 0), chunk(mi, 1), S_txt, out=n)
+            mm([dict(a=n_img, w=w.qkv_img, bias=blk.bqkv_img, out=ws.qkv[:, S_txt:],
+                     qkv=dict(q_out=ws.q, k_out=ws.k, wq=P(p + "attn.norm_q.weight"), wk=P(p + "attn.norm_k.weight"), cs=cs,
+                              s_offset=S_txt)),
+                dict(a=n_txt, w=w.qkv_txt, bias=blk.bqkv_txt, out=ws.qkv[:, :S_txt],
+                     qkv=dict(q_out=ws.q, k_out=ws.k, wq=P(p + "attn.norm_added_q.weight"), wk=P(p + "attn.norm_added_k.weight"),
+                              cs=cs, s_offset=0))], ops.FK_EPI_QKV)
+            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.o)
+            mm([dict(a=ws.o[:, S_txt:], w=w.out, bias=P(p + "attn.to_out.0.bias"), out=h, res=h, gate=chunk(mi, 2)),
+                dict(a=ws.o[:, :S_txt], w=w.add_out, bias=P(p + "attn.to_add_out.bias"), out=cx, res=cx, gate=chunk(mt, 2))],
+               ops.FK_EPI_GATE_RES)
+            ops.ln_modulate2(s, chunk(mt, 3), chunk(mt, 4), chunk(mi, 3), chunk(mi, 4), S_txt, out=n)
+            mm([dict(a=n_img, w=w.ff1, bias=P(p + "ff.net.0.proj.bias"), out=ws.ff[:, S_txt:]),
+                dict(a=n_txt, w=w.ff1_ctx, bias=P(p + "ff_context.net.0.proj.bias"), out=ws.ff[:, :S_txt])], ops.FK_EPI_GELU_TANH)
+            mm([dict(a=ws.ff[:, S_txt:], w=w.ff2, bias=P(p + "ff.net.2.bias"), out=h, res=h, gate=chunk(mi, 5)),
+                dict(a=ws.ff[:, :S_txt], w=w.ff2_ctx, bias=P(p + "ff_context.net.2.bias"), out=cx, res=cx, gate=chunk(mt, 5))],
+               ops.FK_EPI_GATE_RES)
+        for i, (blk, w) in enumerate(zip(pk.single, pk.mx_single)):
+            p = f"single_transformer_blocks.{i}."
+            m0 = blk.mod
+            ops.ln_modulate(s, chunk(m0, 0), chunk(m0, 1), out=n)
+            mm([dict(a=n, w=w.qkv, bias=blk.bqkv, out=ws.qkv,
+                     qkv=dict(q_out=ws.q, k_out=ws.k, wq=P(p + "attn.norm_q.weight"), wk=P(p + "attn.norm_k.weight"), cs=cs,
+                              s_offset=0))], ops.FK_EPI_QKV)
+            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.cat[:, :, :D])
+            mm([dict(a=n, w=w.mlp, bias=P(p + "proj_mlp.bias"), out=ws.cat[:, :, D:])], ops.FK_EPI_GELU_TANH)
+            mm([dict(a=ws.cat, w=w.out, bias=P(p + "proj_out.bias"), out=s, res=s, gate=chunk(m0, 2))], ops.FK_EPI_GATE_RES)
+
+    def _block_mx_structs(self, pk):
+        """fk_double_block_weights_mx / fk_single_block_weights_mx of every block, built once per set of quantized weights."""
+        from . import libfk
+        st = self.__dict__.get("_block_structs_mx")
+        if st is None or st.serial != pk.serial:
+            nd, ns = len(pk.mx_double), len(pk.mx_single)
+            dbl, sgl = (libfk.DoubleBlockWeightsMx * max(nd, 1))(), (libfk.SingleBlockWeightsMx * max(ns, 1))()
+            for arr, blocks, fields in ((dbl, pk.mx_double, libfk.DOUBLE_BLOCK_MX_FIELDS), (sgl, pk.mx_single, libfk.SINGLE_BLOCK_MX_FIELDS)):
+                for i, m in enumerate(blocks):
+                    for f in fields:
+                        q, sc = getattr(m, f)
+                        setattr(arr[i], f, libfk.MxPair(q.data_ptr(), sc.data_ptr()))
+            st = SimpleNamespace(serial=pk.serial, dbl=dbl, sgl=sgl)
+            self.__dict__["_block_structs_mx"] = st
+        return st
+
     def _block_weight_structs(self, pk):
         """fk_double_block_weights / fk_single_block_weights of every block (arrays, built once per set of weight pointers): shared
         by the forward's and the backward's block-level entry points."""
@@ -550,7 +672,8 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         sk, slots = ops.splitk_workspace(ws.s.device)
         aw = ops.attention_workspace(ws.s.device)
         key = tuple(getattr(ws, f).data_ptr() for f in ("s", "n", "qkv", "q", "k", "o", "ff", "cat")) + (
-            cs.data_ptr(), sk.data_ptr(), aw.data_ptr(), B, S_txt, S_img)
+            cs.data_ptr(), sk.data_ptr(), aw.data_ptr(), B, S_txt, S_img, pk.format,
+            ws.mxq.data_ptr() if pk.format == "mxfp8" else 0)
         bw = self.__dict__.get("_block_ws")
         if bw is None or bw[0] != key:
             c = libfk.BlockWs()
@@ -558,7 +681,10 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
                 setattr(c, f, getattr(ws, f).data_ptr())
             c.rope_cs, c.splitk_ws, c.attn_ws, c.attn_ws_bytes, c.splitk_slots = cs.data_ptr(), sk.data_ptr(), aw.data_ptr(), aw.numel(), slots
             c.B, c.S_txt, c.S_img, c.H, c.eps = B, S_txt, S_img, self.num_heads, 1e-6
-            bw = (key, c, (cs, sk, aw))            # strong references keep the buffers the struct points into alive
+            mxw = None
+            if pk.format == "mxfp8":
+                mxw = libfk.MxWs(ws.mxq.data_ptr(), ws.mxs.data_ptr(), ws.mxq.numel(), ws.mxs.numel())
+            bw = (key, c, (cs, sk, aw, ws.mxq, ws.mxs), mxw)   # strong references keep the buffers the structs point into alive
             self.__dict__["_block_ws"] = bw
         c = bw[1]
         L = ops.LAUNCH       # the host's launch defaults travel with the call (the library keeps no launch state)
@@ -567,6 +693,19 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         c.gemm_variant_used = ctypes.pointer(ops._variant_slot())
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         mp, mbs = ctypes.c_void_p(mod.data_ptr()), mod.stride(0)
+        if pk.format == "mxfp8":
+            sx, mxw = self._block_mx_structs(pk), bw[3]
+            if api >= 2:
+                libfk.check(lib.fk_mmdit_blocks_fwd_mx(ctypes.byref(c), ctypes.byref(mxw), st.dbl, sx.dbl, st.nd, st.sgl, sx.sgl,
+                                                       st.ns, mp, mbs, stream), "fk_mmdit_blocks_fwd_mx")
+                return
+            for i in range(st.nd):
+                libfk.check(lib.fk_double_block_fwd_mx(ctypes.byref(c), ctypes.byref(mxw), ctypes.byref(st.dbl[i]),
+                                                       ctypes.byref(sx.dbl[i]), mp, mbs, stream), "fk_double_block_fwd_mx")
+            for i in range(st.ns):
+                libfk.check(lib.fk_single_block_fwd_mx(ctypes.byref(c), ctypes.byref(mxw), ctypes.byref(st.sgl[i]),
+                                                       ctypes.byref(sx.sgl[i]), mp, mbs, stream), "fk_single_block_fwd_mx")
+            return
         if api >= 2:
             libfk.check(lib.fk_mmdit_blocks_fwd(ctypes.byref(c), st.dbl, st.nd, st.sgl, st.ns, mp, mbs, stream), "fk_mmdit_blocks_fwd")
             return
@@ -605,7 +744,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         return save_directory
 
     @classmethod
-    def from_pretrained(cls, directory, device="cuda", subfolder=None, torch_dtype=BF16, **unused):
+    def from_pretrained(cls, directory, device="cuda", subfolder=None, torch_dtype=BF16, weight_format="bf16", **unused):
         """Load a transformer directory written by diffusers' / this class's ``save_pretrained`` (or a FLUX pipeline
         directory with ``subfolder='transformer'``)."""
         import os as _os
@@ -616,4 +755,5 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         state = checkpoint.read_state_dict(d, dtype=BF16)
         checkpoint.check_against(flux_spec.flux_param_shapes(cfg), state, f"FLUX transformer at {d}")
         model.load_state_dict(state, strict=True)
+        model.set_weight_format(weight_format)
         return model

@@ -140,6 +140,36 @@ int fk_gemm_bf16(const fk_gemm_args* args, fk_stream_t stream);
 #define FK_MAX_GROUP 4
 int fk_gemm_bf16_grouped(const fk_gemm_args* args, int32_t n, fk_stream_t stream);
 
+/* ---- MXFP8 (OCP MX v1.0, E4M3 elements, E8M0 block scales) -- opt-in inference format of the block GEMMs ---------------
+ * A row of K elements is stored as K e4m3fn bytes (x / 2^e, round-to-nearest-even, saturated to +-448) plus K / 32 E8M0
+ * scale bytes (2^(byte - 127)), one per block of 32 consecutive elements:  e = max(floor(log2(amax)) - 8, -127);  an all-zero
+ * block has scale byte 127 (2^0); a block holding Inf / NaN has scale byte 0xFF and every element 0x7F (both NaN), so a bad
+ * activation surfaces as NaN rows.
+ *
+ * fk_quantize_mxfp8: x bf16 (rows m of M through xr, K contiguous) -> q [M, K] bytes (row m at q + m * ldq) and scales
+ * [M, K / 32] bytes (row m at scales + m * ld_scale).  K % 32 == 0, x rows 16-byte aligned, ldq % 16 == 0.  One pass, the
+ * same entry point quantizes weights ([N, K], K-contiguous) once at pack time. */
+int fk_quantize_mxfp8(const void* x, fk_rows xr, int64_t M, int32_t K, void* q, int64_t ldq, void* scales,
+                      int64_t ld_scale, fk_stream_t stream);
+
+/* C = epilogue(sum_k deq(A)[m, k] * deq(W)[n, k] + bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 x e4m3), fp32
+ * accumulation.  g carries everything of fk_gemm_args except the operands: shapes, bias, C / res / gate / QKV fields,
+ * epilogue (FK_EPI_NONE, GELU_TANH, GATE_RES, QKV; g.out_fp32 = 2: fp32(acc + bias), the parity build), g.variant
+ * (0 = launch plan, 128 = 256 x 128 tiles, 256 = 256 x 256 tiles) and g.variant_used; g.A / g.W / g.a / g.ldw are unused.
+ * The epilogue arithmetic and rounding points are those of fk_gemm_bf16.  K % 128 == 0, N % 256 == 0, any M; operand rows
+ * 16-byte aligned (lda8, ldw8 % 16 == 0), scale rows 4-byte aligned (ld scales % 4 == 0). */
+typedef struct fk_gemm_mxfp8_args {
+  fk_gemm_args g;
+  const void* A8; int64_t lda8;            /* e4m3 [M, K]: row m at A8 + m * lda8 bytes */
+  const void* A_scale; int64_t lda_scale;  /* E8M0 [M, K / 32] */
+  const void* W8; int64_t ldw8;            /* e4m3 [N, K] */
+  const void* W_scale; int64_t ldw_scale;  /* E8M0 [N, K / 32] */
+} fk_gemm_mxfp8_args;
+
+int fk_gemm_mxfp8(const fk_gemm_mxfp8_args* args, fk_stream_t stream);
+/* n (<= FK_MAX_GROUP) problems with identical N, K and epilogue in one launch (the img + txt pairs of a double block). */
+int fk_gemm_mxfp8_grouped(const fk_gemm_mxfp8_args* args, int32_t n, fk_stream_t stream);
+
 /* out = LN(x; eps, no affine) * (1 + scale[b]) + shift[b], rows of width D (=3072), bf16 in/out.
  * Rounds like the reference graph: LN -> bf16, (1+scale) -> bf16, product -> bf16, sum -> bf16.
  * Replaces AdaLayerNormZero / AdaLayerNormZeroSingle / AdaLayerNormContinuous / norm2 (+modulate)
@@ -247,6 +277,36 @@ int fk_single_block_fwd(const fk_block_ws* ws, const fk_single_block_weights* w,
 int fk_mmdit_blocks_fwd(const fk_block_ws* ws, const fk_double_block_weights* dbl, int32_t n_double,
                         const fk_single_block_weights* sgl, int32_t n_single, const void* mod, int64_t mod_batch_stride,
                         fk_stream_t stream);
+
+/* ---- MXFP8 block forward (opt-in inference format; fk_quantize_mxfp8 / fk_gemm_mxfp8 above) -------------------------------
+ * The same launches, in the same order, as fk_double_block_fwd / fk_single_block_fwd / fk_mmdit_blocks_fwd, except that every
+ * block GEMM becomes fk_quantize_mxfp8 of its activation operand (into the caller's fk_mx_ws) followed by fk_gemm_mxfp8(_grouped)
+ * on the pre-quantized weight; biases, RMSNorm weights and the modulation offsets still come from the bf16 weight structs.
+ * Weight pairs: e4m3 [N, K] and E8M0 [N, K / 32], both dense (ld = K, K / 32). */
+typedef struct fk_mx_pair {
+  const void* q;
+  const void* s;
+} fk_mx_pair;
+typedef struct fk_double_block_weights_mx {
+  fk_mx_pair qkv_img, qkv_txt, out, add_out, ff1, ff1_ctx, ff2, ff2_ctx;
+} fk_double_block_weights_mx;
+typedef struct fk_single_block_weights_mx {
+  fk_mx_pair qkv, mlp, out;
+} fk_single_block_weights_mx;
+/* quantized activations of one launch: q >= B * S * 5D bytes (16-byte aligned), s >= B * S * 5D / 32 bytes (4-byte aligned) */
+typedef struct fk_mx_ws {
+  void* q;
+  void* s;
+  int64_t q_bytes, s_bytes;
+} fk_mx_ws;
+int fk_double_block_fwd_mx(const fk_block_ws* ws, const fk_mx_ws* mx, const fk_double_block_weights* w,
+                           const fk_double_block_weights_mx* wx, const void* mod, int64_t mod_batch_stride, fk_stream_t stream);
+int fk_single_block_fwd_mx(const fk_block_ws* ws, const fk_mx_ws* mx, const fk_single_block_weights* w,
+                           const fk_single_block_weights_mx* wx, const void* mod, int64_t mod_batch_stride, fk_stream_t stream);
+int fk_mmdit_blocks_fwd_mx(const fk_block_ws* ws, const fk_mx_ws* mx, const fk_double_block_weights* dbl,
+                           const fk_double_block_weights_mx* dblx, int32_t n_double, const fk_single_block_weights* sgl,
+                           const fk_single_block_weights_mx* sglx, int32_t n_single, const void* mod, int64_t mod_batch_stride,
+                           fk_stream_t stream);
 
 /* ---- backward pass of the MMDiT (train_denoiser.py:1172 `accelerator.backward(loss)` through diffusers' blocks) ---- */
 /* Forward attention that also saves lse[b, h, s] = log2(sum_j exp(q.k_j * scale)) (fp32) for the backward pass. */
