@@ -486,7 +486,7 @@ class FluxBackward:
             setattr(c, k, t.data_ptr())
         c.attn_ws_bytes, c.mod_batch_stride = bufs["attn_ws"].numel(), ws.mod.stride(0)
         L = ops.LAUNCH
-        c.gemm_variant, c.gemm_plan, c.gemm_group_m, c.gemm_mfma = L.gemm_variant, L.gemm_plan, L.gemm_group_m, L.gemm_mfma
+        c.gemm_variant, c.gemm_plan, c.gemm_group_m, c.gemm_mfma = L.gemm_variant, ops.launch_plan(), L.gemm_group_m, L.gemm_mfma
         c.attn_grid, c.attn_passes = L.attn_grid, L.attn_bwd_passes
         c.gemm_variant_used = ctypes.pointer(ops._variant_slot())
         return SimpleNamespace(c=c, st=st, bufs=bufs, lib=libfk.load(), stream=ctypes.c_void_p(torch.cuda.current_stream().cuda_stream),

@@ -88,9 +88,15 @@ FK_DEV void quad_set(f32x16_t& v, int q, const f32x4_t& c) {
 // chunk made the epilogue ~15 % of a K = 3072 tile).  All global reads are therefore issued unconditionally with
 // clamped indices, a batch of EPI_BATCH chunks at a time, ahead of the arithmetic of the batch; only the final
 // store is predicated.
-template <int EPI, int BN, class C>
+//
+// HALF = 0 / 1 (the split-K pairs' symmetric exchange): only rows [128 HALF, 128 HALF + 128) of the tile; needs a config whose
+// m-blocks [HALF MF / 2, + MF / 2) are exactly those rows (Cfg8).  -1: the whole tile.  The half-tile forms add the partner's
+// partial sums on the way: other[nf * 2 MF + (mf - first m-block) * 4 + q] = its quad q of block (nf, mf), own + other.
+template <int EPI, int BN, class C, int HALF = -1>
 FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& p, char* smem, int m0, int n0,
-                       int wm, int wn) {
+                       int wm, int wn, const u32x4_t* other = nullptr) {
+  constexpr int MF0 = HALF > 0 ? C::MF / 2 : 0, MF1 = HALF == 0 ? C::MF / 2 : C::MF;   // m-blocks stored
+  constexpr int row0 = HALF > 0 ? BM / 2 : 0;                                           // first tile row stored
   int tid = threadIdx.x;
   // gemm10 (the only 256-thread caller) may run this inside a per-CU tile loop around an asm statement that leaves 36 free
   // VGPRs: an opaque copy keeps hipcc from hoisting the 32 per-lane row indices below out of that loop and spilling them
@@ -123,12 +129,15 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
         const int n = n0 + C::tile_col(wn, nf) + FM::col(lane, q);
         const float b[4] = {bf_lo(bw[nf][q][0]), bf_hi(bw[nf][q][0]), bf_lo(bw[nf][q][1]), bf_hi(bw[nf][q][1])};
 #pragma unroll
-        for (int mf = 0; mf < C::MF; ++mf) {
+        for (int mf = MF0; mf < MF1; ++mf) {
           const int m = m0 + C::tile_row(wm, mf) + FM::row(lane, q);
+          f32x4_t x = quad_get(acc[nf][mf], q);
+          if constexpr (HALF >= 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[j] += __uint_as_float(other[nf * 2 * C::MF + (mf - MF0) * 4 + q][j]);
+          }
           if (m < p.M && n < p.N)
-            *(f32x4_t*)((float*)p.C + fk_row_offset(p.c, m) + n) =
-                f32x4_t{acc[nf][mf][4 * q + 0] + b[0], acc[nf][mf][4 * q + 1] + b[1], acc[nf][mf][4 * q + 2] + b[2],
-                        acc[nf][mf][4 * q + 3] + b[3]};
+            *(f32x4_t*)((float*)p.C + fk_row_offset(p.c, m) + n) = f32x4_t{x[0] + b[0], x[1] + b[1], x[2] + b[2], x[3] + b[3]};
         }
       }
     return;
@@ -142,11 +151,12 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
       const int nl = C::tile_col(wn, nf) + FM::col(lane, q);
       const float b[4] = {bf_lo(bw[nf][q][0]), bf_hi(bw[nf][q][0]), bf_lo(bw[nf][q][1]), bf_hi(bw[nf][q][1])};
 #pragma unroll
-      for (int mf = 0; mf < C::MF; ++mf) {
+      for (int mf = MF0; mf < MF1; ++mf) {
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float x = acc[nf][mf][q * 4 + j];
+          float x = acc[nf][mf][q * 4 + j];
+          if constexpr (HALF >= 0) x += __uint_as_float(other[nf * 2 * C::MF + (mf - MF0) * 4 + q][j]);
           if constexpr (EPI == FK_EPI_SCALE) v[j] = x * p.alpha;
           else v[j] = x + b[j];
         }
@@ -167,10 +177,11 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
   }
   __syncthreads();
   constexpr int CPR = BN / 8;  // 16-byte chunks per tile row
-  constexpr int ITERS = BM * CPR / C::NTHREADS;
+  constexpr int ITERS = (HALF >= 0 ? BM / 2 : BM) * CPR / C::NTHREADS;
   // chunks per batch; the fused QKV epilogue keeps 16 table registers per chunk, so the 4-wave kernel (32 chunks per
   // thread, VGPRs full) batches 4 and the 8-wave kernel takes all 8 of a thread's chunks at once
-  constexpr int U = (EPI == FK_EPI_QKV && ITERS > 8) ? 4 : 8;
+  // (and so do the half-tile forms, which stand twice in their kernel)
+  constexpr int U = (EPI == FK_EPI_QKV && (ITERS > 8 || HALF >= 0)) ? 4 : 8;
   static_assert(ITERS % U == 0 && C::NTHREADS % CPR == 0, "epilogue batching");
   // per-tile (scalar) row addressing of the output, the residual and the gate
   const TileRows crow(p.c, m0);
@@ -184,7 +195,7 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
   const int D = EPI == FK_EPI_QKV ? p.qkv_heads * 128 : 1;
   const int which = EPI == FK_EPI_QKV ? n0 / D : 0;   // 0 = q, 1 = k, 2 = v: a tile never straddles q | k | v
   // a thread keeps its chunk column over the iterations (NTHREADS % CPR == 0): only the row advances
-  const int cc = tid % CPR, ml0 = tid / CPR;
+  const int cc = tid % CPR, ml0 = row0 + tid / CPR;
   constexpr int ML_STEP = C::NTHREADS / CPR;
   const int n = n0 + cc * 8;
   const int nc = min(n, p.N - 8);          // clamped column for the unconditional loads

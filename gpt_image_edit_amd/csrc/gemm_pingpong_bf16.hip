@@ -46,6 +46,9 @@ constexpr int GROUP_M = FK_GROUP_M;
 #endif
 
 
+// GroupArgs.sk_mode: how the two workgroups of a split-K pair exchange their partial tiles (gemm8_body's rendezvous)
+enum { SK_WHOLE = 0, SK_SYM = 1, SK_SYM_UNANNOUNCED = 2 };
+
 struct GroupArgs {
   fk_gemm_args p[FK_MAX_GROUP];
   int tiles_before[FK_MAX_GROUP + 1];  // prefix sums of tile counts (mixed launch: of the 256 x 256 tiles)
@@ -59,6 +62,7 @@ struct GroupArgs {
   // tiles (256 KiB apiece) and one (ticket, flag) word pair per tile in a caller-owned workspace
   float* sk_partials;
   unsigned* sk_ctl;
+  int sk_mode;         // split-K pairs' exchange (SK_* below): whole tile one way, or each workgroup finishes a 128-row half
   int sk_min_part;     // stream-K launch (gemm8_streamk_kernel): the shortest part (in K-tiles) a cut may leave
   int group_m;         // depth (in row tiles) of the grouped tile order; >= the row-tile count: every XCD owns a column range
 };
@@ -185,8 +189,9 @@ struct Cfg8 {
 // block b ^ (r & 3)) and its MFMA fragments come through ds_read_b64_tr_b16 -- two reads of rows 8 hh + tj and + 4, which
 // deliver k = 8 hh + 0..7 in the slot order of the ds_read_b128 path, so a K-major operand multiplies a row-major one and
 // the sums are those of the LAY 0 kernel on transposed copies bit for bit (attention_fwd.hip's V^T operand is the recipe).
-template <int EPI, int BN, int LAY = 0, bool M16 = false>
-FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, int kt_first, int nk, int sk_slot) {
+// SYM (split-K pairs only): this workgroup is part sk_part (0 / 1) of its tile and may finish the 128-row half sk_part of it.
+template <int EPI, int BN, int LAY = 0, bool M16 = false, bool SYM = false>
+FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, int kt_first, int nk, int sk_slot, int sk_part = 0) {
   using C = Cfg8<BN, M16>;
   constexpr bool AT = LAY == 2, WT = LAY >= 1;
   const int tid = threadIdx.x;
@@ -342,6 +347,18 @@ FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, 
   dma_half(2, 1, 1);   // W0(1)   P4
   dma_half(0, 1, 1);   // A0(1)   P1 of tile 1
   dma_half(3, 1, 1);   // W1(1)   P2 of tile 1
+  // split-K pairs: "I am on the chip" (rendezvous below).  Behind the prologue's requests, so the round trip of the add hides
+  // behind theirs; only wave 0 waits for it (for all of its requests instead of the first four), and the value stays scalar.
+  unsigned sk_ann = 0;
+  if constexpr (SYM) {
+    if (ga.sk_mode != SK_WHOLE && wave == 0) {
+      unsigned r = 0;
+      if (lane == 0)
+        r = __hip_atomic_fetch_add((__attribute__((address_space(1))) unsigned*)(ga.sk_ctl + 2 * (size_t)sk_slot), 1u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+      sk_ann = __builtin_amdgcn_readfirstlane(r);
+    }
+  }
   wait_vmcnt<10>();    // W0(0), A0(0) (own pieces) landed
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -364,52 +381,123 @@ FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, 
   if (wm == 0) __builtin_amdgcn_s_barrier();   // balance the stagger
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // surplus (clamped) requests must not land in the C tile
 
-  if (sk_slot >= 0) {
+  if (SYM || sk_slot >= 0) {
     // ---- split-K rendezvous ---------------------------------------------------------------------------------------
-    // The two workgroups of a tile each hold the fp32 partial sums of half the K range.  Whoever finishes FIRST
-    // (ticket = an agent-scope fetch-add on the tile's counter word: even -> first) writes its accumulators to the
-    // tile's workspace slot with write-through stores, drains them, publishes flag = ticket + 1 and exits; the
-    // SECOND (odd ticket) waits for flag == its ticket, acquires, adds the stored partials to its own and runs the
-    // epilogue.  fp32 addition commutes, so own + other is the same bits whichever half arrives first: the result
-    // is deterministic.  The wait cannot deadlock under any dispatch order: it is only ever for a workgroup that has
-    // already drawn its ticket, i.e. is resident and a few microseconds from publishing.  Counter and flag are
-    // monotonic (every launch adds exactly two tickets per slot it uses), so nothing is reset between launches.
-    // Recipe: cdna_hip_programming.md Guideline 16 R1 (sc1 payload -> per-wave vmcnt(0) -> barrier -> one-lane
-    // relaxed agent flag store; consumer: one-lane relaxed poll -> ONE agent acquire -> barrier -> loads).
+    // The two workgroups of a tile each hold the fp32 partial sums of half the K range and meet through the tile's workspace
+    // slot: 256 KiB of payload and two control words, a COUNTER and a FLAG.  Every use of a slot moves each word forward by
+    // exactly 4, so both are multiples of 4 (and equal) whenever a launch starts, nothing is reset between launches, and
+    // 2^32 being a multiple of 4 a wrap changes nothing.  fp32 addition commutes, so own + other has the same bits whichever
+    // workgroup forms it: which of the forms below a tile takes does not show in the result.
+    //
+    // WHOLE (sk_mode = SK_WHOLE; stream-K ranges; the fallback of the symmetric form): a workgroup draws a ticket when it is
+    // done multiplying.  The FIRST writes its whole partial tile with write-through stores, drains them, moves the flag to
+    // counter base + 4 and exits; the SECOND waits for that flag value, acquires, adds the stored partials to its own and runs
+    // the whole epilogue.
+    //
+    // SYMMETRIC (split-K pairs): part p of the pair writes only rows [128 (1 - p), + 128) of its partial tile (half of every
+    // wave's accumulators: acc[.][mf] covers the 128-row half mf >> 1), moves the flag by 2, waits for the flag to reach
+    // base + 4 -- both halves published --, adds the partner's rows [128 p, + 128) to its own and runs the epilogue on that
+    // half: each workgroup moves half the bytes of the one-way form, at the same time.
+    //   A symmetric wait is only safe for a partner that is on the chip, so every workgroup ANNOUNCES itself on entry (+1 on
+    // the counter, behind the prologue's requests) and draws its ticket with another +1.  The counter's values base .. base + 3
+    // order the four events, and the two values a workgroup sees (announcement a, ticket t) tell it everything:
+    //     t = base + 1   first to finish, the partner has not announced itself   -> WHOLE, first
+    //     t = base + 2   first to finish, the partner is on the chip             -> SYMMETRIC
+    //     t = base + 3   second to finish; a = base + 2: the first saw t = base + 1 -> WHOLE, second; else SYMMETRIC
+    // so no workgroup ever waits for one that has not drawn a ticket or announced itself, i.e. that is not resident, under any
+    // dispatch order.  SK_SYM_UNANNOUNCED (tests) takes the decisions as if the partner's announcement had not been seen.
+    // Every wait is bounded (a corrupted workspace must end in a wrong tile, which the parity tests see, not in a hung device).
+    // Recipe: cdna_hip_programming.md Guideline 16 R1 (sc1 payload -> per-wave vmcnt(0) -> barrier -> one-lane relaxed agent
+    // flag update; consumer: one-lane relaxed poll -> ONE agent acquire -> barrier -> loads).
     typedef __attribute__((address_space(1))) unsigned gu32;
     gu32* const ctl = (gu32*)(ga.sk_ctl + 2 * (size_t)sk_slot);
     const __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(ga.sk_partials + (size_t)sk_slot * (BM * BN)), 0, BM * BN * 4, 0x00020000);
-    __syncthreads();   // every wave is done with the operand ring: its first word now carries the ticket
-    if (tid == 0) *(volatile unsigned*)smem = __hip_atomic_fetch_add(ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const unsigned ticket = __builtin_amdgcn_readfirstlane(*(volatile unsigned*)smem);
-    constexpr int NV = C::NF * C::MF * 4;   // 16-byte pieces of the accumulators per thread: piece r of thread t at (r * 512 + t) * 16
-    if ((ticket & 1u) == 0) {
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        const f32x16_t& a = acc[r / (C::MF * 4)][(r / 4) % C::MF];
-        const int q = r & 3;
-        const u32x4_t v = {__float_as_uint(a[4 * q]), __float_as_uint(a[4 * q + 1]), __float_as_uint(a[4 * q + 2]),
-                           __float_as_uint(a[4 * q + 3])};
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs_p, tid * 16, r * (C::NTHREADS * 16), /*sc1: write through*/ 16);
+    const bool announced = SYM && ga.sk_mode != SK_WHOLE;
+    __syncthreads();   // every wave is done with the operand ring: its first words now carry the ticket and the role
+    if (tid == 0) {
+      const unsigned t = __hip_atomic_fetch_add(ctl, announced ? 1u : 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      unsigned role;   // 0 = WHOLE first, 1 = WHOLE second, 2 = SYMMETRIC
+      if (!announced) role = (t & 2u) ? 1u : 0u;
+      else {
+        const bool blind = ga.sk_mode == SK_SYM_UNANNOUNCED;
+        if ((t & 3u) == 3u) role = (blind || (sk_ann & 3u) == 2u) ? 1u : 2u;
+        else role = ((t & 3u) == 2u && !blind) ? 2u : 0u;
       }
+      ((volatile unsigned*)smem)[0] = t;
+      ((volatile unsigned*)smem)[1] = role;
+    }
+    __syncthreads();
+    const unsigned ticket = __builtin_amdgcn_readfirstlane(((volatile unsigned*)smem)[0]);
+    const unsigned role = __builtin_amdgcn_readfirstlane(((volatile unsigned*)smem)[1]);
+    const unsigned target = (ticket & ~3u) + 4u;   // the flag once everything this rendezvous needs is published
+    auto wait_flag = [&]() {
+      if (tid == 0) {
+        // bounded (~seconds): the partner is resident and microseconds from publishing
+        int spins = 0;
+        while (__hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != target && spins < (1 << 22)) {
+          __builtin_amdgcn_s_sleep(8);
+          ++spins;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      }
+      __syncthreads();
+    };
+    auto publish = [&](unsigned step) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its own stores
       __syncthreads();
-      if (tid == 0) __hip_atomic_store(ctl + 1, ticket + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (tid == 0) __hip_atomic_fetch_add(ctl + 1, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    // 16-byte pieces of the accumulators per thread: piece r of thread t at (r * 512 + t) * 16, rows [0, 128) of the tile in
+    // pieces [0, NV / 2) -- piece = (row half, nf, mf & 1, quad)
+    constexpr int NV = C::NF * C::MF * 4, NH = NV / 2;
+    auto piece_acc = [&](int r) -> f32x16_t& { return acc[(r % NH) / 8][2 * (r / NH) + (r / 4) % 2]; };
+    auto store_piece = [&](int r, int at) {
+      const f32x16_t& a = piece_acc(r);
+      const int q = r & 3;
+      const u32x4_t v = {__float_as_uint(a[4 * q]), __float_as_uint(a[4 * q + 1]), __float_as_uint(a[4 * q + 2]),
+                         __float_as_uint(a[4 * q + 3])};
+      __builtin_amdgcn_raw_buffer_store_b128(v, rs_p, tid * 16, at * (C::NTHREADS * 16), /*sc1: write through*/ 16);
+    };
+    // rows [128 keep, + 128) of the tile: all 16 pieces of the partner's at once, own + other on the way into the epilogue (the
+    // accumulators stay where they are: no second copy of a 16-register block, nothing through scratch)
+    auto finish_half = [&](auto keep_c) {
+      constexpr int keep = decltype(keep_c)::value;
+      u32x4_t other[NH];
+#pragma unroll
+      for (int r = 0; r < NH; ++r)
+        other[r] = __builtin_amdgcn_raw_buffer_load_b128(rs_p, tid * 16, (keep * NH + r) * (C::NTHREADS * 16), /*sc1*/ 16);
+      store_tile<EPI, BN, C, keep>(acc, p, smem, m0, n0, wm, wn, other);
+    };
+    if constexpr (SYM) {
+      if (role == 2u) {
+        // part p hands over the pieces of row half 1 - p and finishes half p
+        if (sk_part == 0) {
+#pragma unroll
+          for (int r = 0; r < NH; ++r) store_piece(NH + r, NH + r);
+        } else {
+#pragma unroll
+          for (int r = 0; r < NH; ++r) store_piece(r, r);
+        }
+        publish(2u);
+        wait_flag();
+        if (sk_part == 0) finish_half(std::integral_constant<int, 0>{});
+        else finish_half(std::integral_constant<int, 1>{});
+        return;
+      }
+    }
+    if (role == 0u) {
+#pragma unroll
+      for (int r = 0; r < NV; ++r) store_piece(r, r);
+      publish(4u);
       return;
     }
-    if (tid == 0) {
-      // bounded (~seconds): the partner has drawn its ticket and is microseconds from publishing; a corrupted workspace must
-      // end in a wrong tile (the parity tests see it), not in a hung device
-      int spins = 0;
-      while (__hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ticket && spins < (1 << 22)) {
-        __builtin_amdgcn_s_sleep(8);
-        ++spins;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    wait_flag();
+    if constexpr (SYM) {   // the whole tile as its two halves, one after the other
+      finish_half(std::integral_constant<int, 0>{});
+      finish_half(std::integral_constant<int, 1>{});
+      return;
     }
-    __syncthreads();
 #pragma unroll
     for (int r0 = 0; r0 < NV; r0 += 4) {
       u32x4_t v[4];
@@ -418,9 +506,8 @@ FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, 
         v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_p, tid * 16, (r0 + u) * (C::NTHREADS * 16), /*sc1*/ 16);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const int r = r0 + u;
-        f32x16_t& a = acc[r / (C::MF * 4)][(r / 4) % C::MF];
-        const int q = r & 3;
+        f32x16_t& a = piece_acc(r0 + u);
+        const int q = u;
 #pragma unroll
         for (int j = 0; j < 4; ++j) a[4 * q + j] += __uint_as_float(v[u][j]);
       }
@@ -440,7 +527,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GroupArgs ga) {
   const int nk_all = ga.p[0].K / Cfg8<BN>::BK;
   if constexpr (SPLITK) {
     select_tile<BN>(ga, t >> 1, pi, m0, n0);
-    gemm8_body<EPI, BN, LAY, M16>(ga, smem, pi, m0, n0, (t & 1) * (nk_all >> 1), nk_all >> 1, t >> 1);
+    gemm8_body<EPI, BN, LAY, M16, true>(ga, smem, pi, m0, n0, (t & 1) * (nk_all >> 1), nk_all >> 1, t >> 1, t & 1);
   } else {
     select_tile<BN>(ga, t, pi, m0, n0);
     gemm8_body<EPI, BN, LAY, M16>(ga, smem, pi, m0, n0, 0, nk_all, -1);
@@ -1086,9 +1173,18 @@ double makespan(long nb, long ns, double cs, int G) {
 
 struct Plan { int variant, big_cols; };
 constexpr int SK_MIN_PART = 16;   // stream-K: the shortest part of a tile's K range a cut may leave, in K-tiles of 64
+// What the rendezvous of a cut tile adds to the launch, in seconds.  One way (256 KiB written through by one CU, read back
+// by the other, which then runs the whole epilogue alone; two barriers and a fence): priced at 17 us since round 3.
+// Symmetric (each workgroup 128 KiB out, 128 KiB in, half the epilogue): the K-long launches of the 512^2 edit went from
+// 179.5 to 171.6 us per launch (kernel trace, profiles/r07_splitk_symmetric_kernel_stats.md), so 17 - 7.9 ~ 9 us.
+constexpr double SK_TAIL_WHOLE = 17.0e-6, SK_TAIL_SYM = 9.0e-6;
+#ifndef FK_SPLITK_SYMMETRIC_DEFAULT
+#define FK_SPLITK_SYMMETRIC_DEFAULT 1
+#endif
+constexpr int SK_MODE_DEFAULT = FK_SPLITK_SYMMETRIC_DEFAULT ? SK_SYM : SK_WHOLE;
 
 // nbm: row tiles summed over the problems of the launch; N, K shared.  allow: bit 0 mixed, bit 1 split-K.
-Plan plan_launch(long nbm, int N, int K, int G, int allow, bool have_ws, int ws_slots) {
+Plan plan_launch(long nbm, int N, int K, int G, int allow, bool have_ws, int ws_slots, int sk_mode) {
   const double c128 = 0.5 * FK_RATE_256;   // a 256 x 128 tile in units of a 256 x 256 tile (measured rate ratio)
   const long t128 = nbm * ((N + 127) / 128), t256 = nbm * ((N + 255) / 256);
   Plan best = {128, 0};
@@ -1106,9 +1202,8 @@ Plan plan_launch(long nbm, int N, int K, int G, int allow, bool have_ws, int ws_
     }
   }
   if ((allow & 2) && have_ws && K >= 6144 && (K / 64) % 4 == 0 && 2 * t256 <= G && t256 <= ws_slots) {
-    // two half-K workgroups per tile in ONE round; the exchange costs ~17 us (256 KiB written through, read back, two
-    // barriers and a fence) against K x 25.8 ns for a whole tile
-    const double t = 0.5 + 17.0e-6 / (K * 25.8e-9);
+    // two half-K workgroups per tile in ONE round; the exchange (SK_TAIL_*) against K x 25.8 ns for a whole tile
+    const double t = 0.5 + (sk_mode == SK_WHOLE ? SK_TAIL_WHOLE : SK_TAIL_SYM) / (K * 25.8e-9);
     if (t < tbest * 0.97) { tbest = t; best = {512, 0}; }
   }
   // MEASURED AND OFF BY DEFAULT (allow bit 2, FK_GEMM_PLAN=7): inside the 1024^2 edit the stream-K form of the two long-K launch
@@ -1119,7 +1214,7 @@ Plan plan_launch(long nbm, int N, int K, int G, int allow, bool have_ws, int ws_
   if ((allow & 4) && have_ws && K >= 6144 && t256 > G && G <= ws_slots &&
       t256 * (K / 64) >= (long)G * (K / 64 + 2 * SK_MIN_PART) && t256 * (long)(K / 64) < (1l << 31)) {
     // stream-K ranges: every CU the same share of the K-tiles, one exchange per CU (a tile is cut at most once)
-    const double t = (double)t256 / G + 17.0e-6 / (K * 25.8e-9);
+    const double t = (double)t256 / G + SK_TAIL_WHOLE / (K * 25.8e-9);
     if (t < tbest * 0.97) { tbest = t; best = {640, G}; }
   }
   return best;
@@ -1159,8 +1254,12 @@ int fk_gemm2_launch(const fk_gemm_args* probs, int n, int variant_hint, hipStrea
                  "1024 (4-wave hand-placed 256 x 256 kernel)", variant_hint);
     return FK_EINVAL;
   }
-  if (ctl.plan != 0 && (ctl.plan & ~15) != 0 || (ctl.plan != 0 && !(ctl.plan & FK_GEMM_PLAN_EXPLICIT))) {
-    fk_set_error("fk_gemm_bf16: plan %d is not 0 (default) or FK_GEMM_PLAN_EXPLICIT | allow bits 0..2", ctl.plan);
+  constexpr int SK_BITS = FK_GEMM_PLAN_SPLITK_WHOLE | FK_GEMM_PLAN_SPLITK_SYMMETRIC | FK_GEMM_PLAN_SPLITK_UNANNOUNCED;
+  const int sk_bits = ctl.plan & SK_BITS;
+  if (ctl.plan != 0 && (ctl.plan & ~(15 | SK_BITS)) != 0 || (ctl.plan != 0 && !(ctl.plan & FK_GEMM_PLAN_EXPLICIT)) ||
+      (sk_bits & (sk_bits - 1)) != 0) {
+    fk_set_error("fk_gemm_bf16: plan %d is not 0 (default) or FK_GEMM_PLAN_EXPLICIT | allow bits 0..2 | at most one "
+                 "FK_GEMM_PLAN_SPLITK_* exchange", ctl.plan);
     return FK_EINVAL;
   }
   if (ctl.group_m < 0 || ctl.group_m > 4096 || !(ctl.mfma == 0 || ctl.mfma == 16 || ctl.mfma == 32)) {
@@ -1168,7 +1267,10 @@ int fk_gemm2_launch(const fk_gemm_args* probs, int n, int variant_hint, hipStrea
     return FK_EINVAL;
   }
   const int plan_allow = ctl.plan ? (ctl.plan & 7) : 3;
+  const int sk_mode = sk_bits == FK_GEMM_PLAN_SPLITK_WHOLE ? SK_WHOLE : sk_bits == FK_GEMM_PLAN_SPLITK_SYMMETRIC ? SK_SYM
+                      : sk_bits == FK_GEMM_PLAN_SPLITK_UNANNOUNCED ? SK_SYM_UNANNOUNCED : SK_MODE_DEFAULT;
   GroupArgs ga;
+  ga.sk_mode = sk_mode;
   ga.n = n;
   ga.group_m = ctl.group_m ? ctl.group_m : GROUP_M;
   ga.big_cols = 0;
@@ -1239,7 +1341,7 @@ int fk_gemm2_launch(const fk_gemm_args* probs, int n, int variant_hint, hipStrea
     case 128: plan = {128, 0}; break;
     case 256: plan = {ok256 ? 256 : 128, 0}; break;
     case 384: {
-      plan = plan_launch(nbm_total, N, K, G, 1, false, 0);
+      plan = plan_launch(nbm_total, N, K, G, 1, false, 0, sk_mode);
       if (plan.variant != 384) {   // forced: the best split of the columns even where it does not pay
         plan = {128, 0};
         if (ok256 && N >= 512) {
@@ -1261,7 +1363,7 @@ int fk_gemm2_launch(const fk_gemm_args* probs, int n, int variant_hint, hipStrea
       plan = ok ? Plan{640, Gs} : Plan{ok256 ? 256 : 128, 0};
       break;
     }
-    default: plan = plan_launch(nbm_total, N, K, G, plan_allow, ws_slots > 0 && ok256, ws_slots); break;
+    default: plan = plan_launch(nbm_total, N, K, G, plan_allow, ws_slots > 0 && ok256, ws_slots, sk_mode); break;
   }
   ga.sk_min_part = SK_MIN_PART;
   if (plan.variant == 512 || plan.variant == 640) {

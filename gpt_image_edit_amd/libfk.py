@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("FK_LIB_PATH") or os.path.join(_HERE, "libfk_gfx950.so
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
-FK_SPLITK_SLOT_BYTES = 256 * 256 * 4 + 8   # include/fk.h: one fp32 partial tile + its (ticket, flag) words
+FK_SPLITK_SLOT_BYTES = 256 * 256 * 4 + 8   # include/fk.h: one fp32 partial tile + its (counter, flag) words
 FK_EPI_NONE, FK_EPI_GELU_TANH, FK_EPI_SILU, FK_EPI_GATE_RES, FK_EPI_RES, FK_EPI_SCALE, FK_EPI_QKV = range(7)
 
 

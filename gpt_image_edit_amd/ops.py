@@ -193,6 +193,7 @@ def gemm(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=None, o
 # this process's Python callers see them); the environment variables FK_GEMM_PLAN, FK_GEMM_BN, FK_GEMM_GROUP_M, FK_GEMM_MFMA,
 # FK_ATTN_SPLIT, FK_ATTN_BWD of rounds 2-4 are read once, here.
 FK_GEMM_PLAN_EXPLICIT = 8
+FK_GEMM_PLAN_SPLITK = {"default": 0, "whole": 16, "symmetric": 32, "unannounced": 64}   # include/fk.h: FK_GEMM_PLAN_SPLITK_*
 
 
 def _env_int(name, default):
@@ -203,6 +204,7 @@ def _env_int(name, default):
 LAUNCH = SimpleNamespace(
     gemm_variant=_env_int("FK_GEMM_BN", 0),         # 0 = launch plan; 128 / 256 / 384 / 512 / 640 force a form where it applies
     gemm_plan=(FK_GEMM_PLAN_EXPLICIT | (_env_int("FK_GEMM_PLAN", 3) & 7)) if os.environ.get("FK_GEMM_PLAN") else 0,
+    gemm_splitk=0,                                  # exchange of the split-K pairs: 0 = built default, or a FK_GEMM_PLAN_SPLITK bit
     gemm_group_m=_env_int("FK_GEMM_GROUP_M", 0),
     gemm_mfma=_env_int("FK_GEMM_MFMA", 0),          # 0 = built default (16); 16 / 32
     attn_grid={0: -1, 1: 0}.get(_env_int("FK_ATTN_SPLIT", 1), _env_int("FK_ATTN_SPLIT", 1)),   # 0 default, -1 plain grid, >= 2 forced
@@ -240,6 +242,20 @@ def gemm_set_plan(allow):
     _set_launch(gemm_plan=FK_GEMM_PLAN_EXPLICIT | int(allow))
 
 
+def gemm_set_splitk_exchange(mode):
+    """How the two workgroups of a split-K pair exchange their partial tiles (fk_gemm_args.plan, FK_GEMM_PLAN_SPLITK_*):
+    "whole" = the first to finish hands its whole tile over, "symmetric" = each finishes 128 rows of it, "unannounced" = the
+    symmetric form's fallback taken always (tests), "default" = what the library was built with.  Same bits every way."""
+    _set_launch(gemm_splitk=FK_GEMM_PLAN_SPLITK[mode])
+
+
+def launch_plan():
+    """fk_gemm_args.plan / fk_block_ws.gemm_plan of this module's launch defaults."""
+    if not LAUNCH.gemm_splitk:
+        return LAUNCH.gemm_plan
+    return (LAUNCH.gemm_plan or (FK_GEMM_PLAN_EXPLICIT | 3)) | LAUNCH.gemm_splitk
+
+
 def gemm_set_group_m(depth):
     """Depth (in 256-row tiles) of the grouped tile order (fk_gemm_args.group_m; results do not depend on it); 0 = default."""
     if not 0 <= int(depth) <= 4096:
@@ -256,7 +272,7 @@ def gemm_set_mfma(shape):
 
 
 def _apply_gemm_launch(args):
-    args.variant, args.plan, args.group_m, args.mfma = LAUNCH.gemm_variant, LAUNCH.gemm_plan, LAUNCH.gemm_group_m, LAUNCH.gemm_mfma
+    args.variant, args.plan, args.group_m, args.mfma = LAUNCH.gemm_variant, launch_plan(), LAUNCH.gemm_group_m, LAUNCH.gemm_mfma
 
 
 def gemm_grouped(problems, epilogue=FK_EPI_NONE):

@@ -95,8 +95,8 @@ typedef struct fk_gemm_args {
                                   * value over the two columns of its pair, so the [S,128] cos / sin tables hold
                                   * every number twice; the epilogue reads 512 B per token row instead of 1 KiB) */
   /* Optional split-K workspace (caller-owned, one per stream that issues GEMMs): splitk_slots x 256 KiB of fp32 partial
-   * tiles followed by splitk_slots x 2 uint32 control words, the control words zeroed ONCE at allocation (they are
-   * monotonic tickets afterwards).  With it, a K >= 6144 GEMM whose 256 x 256 tiling fills at most half the CUs runs
+   * tiles followed by splitk_slots x 2 uint32 control words, the control words zeroed ONCE at allocation (a counter and a
+   * flag, each moved by exactly 4 per use of the slot afterwards: never reset, wrap-safe).  With it, a K >= 6144 GEMM whose 256 x 256 tiling fills at most half the CUs runs
    * as two half-K workgroups per tile (deterministic: the two fp32 partials are added once, and fp32 addition
    * commutes).  NULL: never split.  Launches that share a workspace must be ordered (same stream). */
   void* splitk_ws;
@@ -116,7 +116,8 @@ typedef struct fk_gemm_args {
    *   plan    : 0 = default (mixed grids and split-K pairs allowed); otherwise FK_GEMM_PLAN_EXPLICIT | allow-bits: bit 0 mixed
    *             grids (bit-identical results), bit 1 split-K pairs (results differ in the last bits from the unsplit sum: with
    *             bit 1 clear a sample's result does not depend on the grid it runs in -- "batch-invariant"), bit 2 stream-K
-   *             ranges for long-K launches with a poorly filled last round (measured slower inside the edits: off by default).
+   *             ranges for long-K launches with a poorly filled last round (measured slower inside the edits: off by default);
+   *             optionally one FK_GEMM_PLAN_SPLITK_* bit (below): the exchange of the split-K pairs.
    *   group_m : 0 = default (8): depth in row tiles of the grouped tile order; >= the row-tile count: every XCD owns a column
    *             range.  Results do not depend on it.
    *   mfma    : 0 = default (16); 16 = v_mfma_f32_16x16x32_bf16, 32 = v_mfma_f32_32x32x16_bf16 (the two differ in the last
@@ -130,6 +131,15 @@ typedef struct fk_gemm_args {
 } fk_gemm_args;
 #define FK_GEMM_PLAN_EXPLICIT 8
 #define FK_GEMM_PLAN_BATCH_INVARIANT (FK_GEMM_PLAN_EXPLICIT | 1)   /* mixed grids only: no K split of any kind */
+/* How the two workgroups of a split-K pair (variant 512) exchange their fp32 partial tiles; at most one bit, with
+ * FK_GEMM_PLAN_EXPLICIT; none = the built default.  Every form gives the same bits (fp32 own + other commutes).
+ *   WHOLE       : the first to finish writes its whole tile and exits, the second adds it and runs the whole epilogue.
+ *   SYMMETRIC   : each writes the 128 rows the other finishes and finishes its own 128 -- where both workgroups are known to be
+ *                 on the chip when the first is done; a pair of which one is not falls back to WHOLE by itself.
+ *   UNANNOUNCED : tests only -- SYMMETRIC taking its decisions as if the partner had never been seen on the chip: the fallback. */
+#define FK_GEMM_PLAN_SPLITK_WHOLE 16
+#define FK_GEMM_PLAN_SPLITK_SYMMETRIC 32
+#define FK_GEMM_PLAN_SPLITK_UNANNOUNCED 64
 #define FK_SPLITK_SLOT_BYTES (256 * 256 * 4 + 8)
 
 int fk_gemm_bf16(const fk_gemm_args* args, fk_stream_t stream);
