@@ -46,6 +46,14 @@ K_MAJOR = int(os.environ.get("FK_BWD_K_MAJOR", "2"))
 # per block instead of one per launch (~80 per double block), where the stage-2 shape allows -- stored activations, batch 1,
 # token counts that are multiples of 64, FK_BWD_K_MAJOR = 2; bit-identical to the per-launch route (0 selects it everywhere).
 BLOCK_API = int(os.environ.get("FK_BWD_BLOCK_API", "1"))
+# Largest batch each kind of block hands to its entry point.  The library takes any batch for a single block (whole-buffer
+# operands) and refuses a double block at B > 1 (include/fk.h); this adaptor keeps batch 1 for both, the configured step.
+BLOCK_API_MAX_BATCH = {"single": 1, "double": 1}
+
+
+def block_api_batch_ok(kind, B):
+    """Does a ``kind`` ("single" / "double") block of a batch-``B`` pass go through its block-level entry point?"""
+    return B <= BLOCK_API_MAX_BATCH[kind]
 
 
 def _pad64(n):
@@ -337,7 +345,7 @@ class FluxBackward:
                 s.copy_(sv.ckpt[nd + j])
                 self._single_forward(j, sv, s, save=True)
             bg = {}
-            if cb is not None:
+            if cb is not None and block_api_batch_ok("single", sv.B):
                 self._single_backward_c(j, sv, cb, bg)
             else:
                 self._single_backward(j, sv, g, bg)
@@ -347,7 +355,7 @@ class FluxBackward:
                 s.copy_(sv.ckpt[i])
                 self._double_forward(i, sv, s, save=True)
             bg = {}
-            if cb is not None:
+            if cb is not None and block_api_batch_ok("double", sv.B):
                 self._double_backward_c(i, sv, cb, bg)
             else:
                 self._double_backward(i, sv, g, bg)
@@ -465,7 +473,8 @@ class FluxBackward:
         """fk_bwd_ws of this pass, or None when the pass does not fit the entry points' scope (then: the per-launch route)."""
         m, ws, pk = self.m, sv.ws, sv.pk
         D, H, B, S = m.inner_dim, m.num_heads, sv.B, sv.S
-        if not (K_MAJOR >= 2 and sv.store and B == 1 and sv.S_txt % 64 == 0 and sv.S_img % 64 == 0 and D % 256 == 0):
+        in_batch_scope = block_api_batch_ok("single", B) or block_api_batch_ok("double", B)
+        if not (K_MAJOR >= 2 and sv.store and in_batch_scope and sv.S_txt % 64 == 0 and sv.S_img % 64 == 0 and D % 256 == 0):
             return None
         st = m._block_weight_structs(pk)
         for blk in list(pk.double) + list(pk.single):      # stored weights as the K-major GEMM forms take them: contiguous rows
@@ -535,27 +544,37 @@ class FluxBackward:
         if "dw_mod" in out:
             grads[p + "norm.linear.weight"], grads[p + "norm.linear.bias"] = out["dw_mod"], out["db_mod"][:, 0]
 
-    def _double_backward_c(self, i, sv, cb, grads):
-        from . import libfk
-        D, T, dev = self.m.inner_dim, self.trainable, cb.dev
+    # struct field stem of fk_double_block_grads -> (parameter stem, weight shape as a function of D)
+    _DOUBLE_PAIRS = {
+        "qkv_img": ("attn.to_q", (3, 1)), "qkv_txt": ("attn.add_q_proj", (3, 1)),
+        "_out": ("attn.to_out.0", (1, 1)), "_add_out": ("attn.to_add_out", (1, 1)),
+        "_ff1": ("ff.net.0.proj", (4, 1)), "_ff1_ctx": ("ff_context.net.0.proj", (4, 1)),
+        "_ff2": ("ff.net.2", (1, 4)), "_ff2_ctx": ("ff_context.net.2", (1, 4)),
+    }
+
+    def _double_grad_buffers(self, i, dev):
+        """Fresh gradient tensors of double block ``i`` by fk_double_block_grads field name (as the per-launch route hands out)."""
+        D, T = self.m.inner_dim, self.trainable
         p = f"transformer_blocks.{i}."
-        bb = self._block_bufs(sv, i, True)
         f32 = torch.float32
         e = lambda *shape, dtype=BF16: torch.empty(shape, device=dev, dtype=dtype)  # noqa: E731
         out = {"dnorm": e(2, 2, 128, dtype=f32)}
-        pairs = {   # struct field stem -> (parameter stem, weight shape)
-            "qkv_img": ("attn.to_q", (3 * D, D)), "qkv_txt": ("attn.add_q_proj", (3 * D, D)),
-            "_out": ("attn.to_out.0", (D, D)), "_add_out": ("attn.to_add_out", (D, D)),
-            "_ff1": ("ff.net.0.proj", (4 * D, D)), "_ff1_ctx": ("ff_context.net.0.proj", (4 * D, D)),
-            "_ff2": ("ff.net.2", (D, 4 * D)), "_ff2_ctx": ("ff_context.net.2", (D, 4 * D)),
-        }
-        for stem, (name, shape) in pairs.items():
+        for stem, (name, (r, c)) in self._DOUBLE_PAIRS.items():
             if p + name + ".weight" in T:
-                out["dw" + stem], out["db" + stem] = e(*shape), e(shape[0], dtype=f32)
+                out["dw" + stem], out["db" + stem] = e(r * D, c * D), e(r * D, dtype=f32)
         if p + "norm1.linear.weight" in T:
             out["dw_mod_img"], out["db_mod_img"] = e(6 * D, D), e(6 * D, 64)
         if p + "norm1_context.linear.weight" in T:
             out["dw_mod_txt"], out["db_mod_txt"] = e(6 * D, D), e(6 * D, 64)
+        return out
+
+    def _double_backward_c(self, i, sv, cb, grads):
+        from . import libfk
+        D = self.m.inner_dim
+        p = f"transformer_blocks.{i}."
+        bb = self._block_bufs(sv, i, True)
+        pairs = self._DOUBLE_PAIRS
+        out = self._double_grad_buffers(i, cb.dev)
         gs = libfk.DoubleBlockGrads()
         for k, t in out.items():
             setattr(gs, k, t.data_ptr())

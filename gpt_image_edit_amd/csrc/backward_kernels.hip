@@ -221,7 +221,9 @@ __global__ __launch_bounds__(256) void gate_res_bwd_kernel(const bf16_t* dout, f
 FK_DEV float gelu_tanh_grad(float x) {
   // y = x * sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3):  y' = sg + x sg (1 - sg) 2 u'
   const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-  const float x2 = x * x;
+  // x^2 capped: beyond |x| ~ 1.8e19 it overflows, du becomes inf and the saturated factor sg (1 - sg) = 0 turns the product
+  // into 0 * inf = NaN where the derivative is 1 (or 0); any |x| > 1e15 has sg = 0 or 1 exactly, so the cap changes nothing else
+  const float x2 = fminf(x * x, 1e30f);
   const float u = k0 * x * fmaf(k1, x2, 1.0f);
   const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.0f * 1.4426950408889634f * u));
   const float du = k0 * fmaf(3.0f * k1, x2, 1.0f);
@@ -430,6 +432,14 @@ __global__ __launch_bounds__(256) void f32_to_bf16_t_kernel(const float* src, in
   dst[i] = r < R ? f2bf(src[(int64_t)r * src_ld + c]) : (bf16_t)0;
 }
 
+// Grid of the grid-stride elementwise kernels (act_bwd, gate_res_fwd, gelu_fwd): one 256-thread block per 256 vectors of 8
+// elements up to this cap; beyond it (more than 2^27 elements) every thread takes further trips of its loop.
+constexpr int64_t EW_MAX_BLOCKS = 65536;
+int ew_blocks(int64_t nvec) {
+  const int64_t g = (nvec + 255) / 256;
+  return (int)(g > EW_MAX_BLOCKS ? EW_MAX_BLOCKS : g);
+}
+
 int pick_chunks(int64_t rows, int per_iter, int max_chunks = 64) {
   int64_t c = (rows + per_iter - 1) / per_iter;
   if (c > max_chunks) c = max_chunks;
@@ -442,6 +452,7 @@ int pick_chunks(int64_t rows, int per_iter, int max_chunks = 64) {
 #define FK_ALIGNED16(p) (((uintptr_t)(p) % 16) == 0)
 
 extern "C" int64_t fk_bwd_ws_floats(void) { return (int64_t)1 << 22; }   // 16 MiB of fp32 partials covers every kernel here
+extern "C" int64_t fk_bwd_ew_max_blocks(void) { return EW_MAX_BLOCKS; }
 
 extern "C" int fk_ln_modulate_bwd_bf16(const void* x, fk_rows xr, const void* dn, fk_rows dnr, const void* scale,
                                        int64_t mod_batch_stride, int64_t rows_per_batch, const void* dx_in, fk_rows dxi,
@@ -512,7 +523,7 @@ static int act_bwd(const char* name, const void* h, const void* df, void* out, i
   FK_CHECK_ARG(h && df && out && n > 0 && n % 8 == 0, "%s: bad arguments", name);
   FK_CHECK_ARG(FK_ALIGNED16(h) && FK_ALIGNED16(df) && FK_ALIGNED16(out), "%s: 16-byte alignment", name);
   const int64_t n8 = n / 8;
-  const int blocks = (int)((n8 + 255) / 256 > 65536 ? 65536 : (n8 + 255) / 256);
+  const int blocks = ew_blocks(n8);
   hipLaunchKernelGGL(act_bwd_kernel<SILU>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t*)h,
                      (const bf16_t*)df, (bf16_t*)out, n8);
   FK_CHECK_LAUNCH(name);
@@ -555,7 +566,7 @@ extern "C" int fk_gate_res_fwd_bf16(const void* res, fk_rows rr, const void* y, 
                    yr.ld % 8 == 0 && orr.ld % 8 == 0 && gate_batch_stride % 8 == 0,
                "fk_gate_res_fwd_bf16: 16-byte alignment");
   const int64_t n = M * (N / 8);
-  const int blocks = (int)((n + 255) / 256 > 65536 ? 65536 : (n + 255) / 256);
+  const int blocks = ew_blocks(n);
   hipLaunchKernelGGL(gate_res_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t*)res, rr,
                      (const bf16_t*)y, yr, (const bf16_t*)gate, gate_batch_stride, rows_per_batch, (bf16_t*)out, orr, M, N);
   FK_CHECK_LAUNCH("fk_gate_res_fwd_bf16");
@@ -566,7 +577,7 @@ extern "C" int fk_gelu_tanh_bf16(const void* x, fk_rows xr, void* y, fk_rows yr,
   FK_CHECK_ARG(x && y && M > 0 && N > 0 && N % 8 == 0, "fk_gelu_tanh_bf16: bad arguments");
   FK_CHECK_ARG(FK_ALIGNED16(x) && FK_ALIGNED16(y) && xr.ld % 8 == 0 && yr.ld % 8 == 0, "fk_gelu_tanh_bf16: 16-byte alignment");
   const int64_t n = M * (N / 8);
-  const int blocks = (int)((n + 255) / 256 > 65536 ? 65536 : (n + 255) / 256);
+  const int blocks = ew_blocks(n);
   hipLaunchKernelGGL(gelu_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t*)x, xr, (bf16_t*)y, yr, M, N);
   FK_CHECK_LAUNCH("fk_gelu_tanh_bf16");
   return FK_OK;

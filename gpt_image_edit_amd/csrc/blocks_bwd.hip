@@ -7,7 +7,8 @@
 // hand-off of a block's gradients stays in Python between two calls.
 //
 // Scope = the stage-2 step as configured: activations stored by the forward, weight gradients by the layout-2 GEMM (token counts
-// that are multiples of 64, uniformly strided views), data gradients on the stored weights (layout 1).  The Python adaptor keeps
+// that are multiples of 64, uniformly strided views: any B for a single block, B == 1 for a double block, which refuses a
+// larger batch with FK_EUNSUPPORTED before its first launch), data gradients on the stored weights (layout 1).  The Python adaptor keeps
 // the per-launch route for everything else (recomputation, padded token counts, FK_BWD_K_MAJOR < 2).
 #include "fk_common.h"
 
@@ -54,8 +55,14 @@ struct Ctx {
     ctl(g);
     return g;
   }
+  // the layout-2 GEMM addresses W by one row stride (ldw): a [B, R, *] operand must continue from batch to batch
+  bool uniform(const View& v) const { return d.B == 1 || v.r.batch_stride == (int64_t)v.R * v.r.ld; }
   // weight gradient dW [N, K] = dY^T X over the tokens of two [B, R, *] views: ops.gemm(dy, x, out=dw, layout=2)
   int wgrad(const View& dy, int n, const View& x, int k, void* dw) const {
+    if (!(uniform(x) && uniform(dy))) {   // unreachable from the entry points below (they refuse up front); kept for new callers
+      fk_set_error("block backward: weight gradient over views that are not uniformly strided (B = %d)", d.B);
+      return FK_EUNSUPPORTED;
+    }
     fk_gemm_args g = {};
     const bool one = d.B == 1;       // backward.wgrad: a one-batch view is passed as its [R, N] matrix (any batch stride)
     g.A = dy.p; g.a = one ? fk_rows{dy.r.ld, 0, 0} : dy.r;
@@ -182,6 +189,13 @@ extern "C" int fk_double_block_bwd(const fk_bwd_ws* wsp, const fk_block_saved* s
   FK_TRY(check(wsp, svp, d, "fk_double_block_bwd"));
   FK_CHECK_ARG(wp && gp && gp->dnorm && svp->x1 && svp->n2 && svp->y2 && d.S_txt > 0,
                "fk_double_block_bwd: null weights / gradient table / x1, n2, y2, or no text stream");
+  if (d.B != 1) {   // before the first launch: the caller's buffers are untouched
+    // every weight gradient here runs over the image or the text rows of a joint [B, S, *] buffer: batch stride S * ld, not
+    // R * ld, which the layout-2 GEMM cannot address for its second operand (Ctx::uniform)
+    fk_set_error("fk_double_block_bwd: B = %d unsupported, double blocks take B == 1 (the stream slices of a joint buffer are "
+                 "not uniformly strided)", d.B);
+    return FK_EUNSUPPORTED;
+  }
   const fk_bwd_ws& ws = *wsp;
   const fk_block_saved& sv = *svp;
   const fk_double_block_weights& w = *wp;

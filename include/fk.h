@@ -349,6 +349,9 @@ int fk_attention_bwd_ws_bf16(const fk_attn_view* q, const fk_attn_view* k, const
 
 /* fp32 elements of workspace `ws` the reductions below need (per-workgroup partial sums, fixed-order finalisation). */
 int64_t fk_bwd_ws_floats(void);
+/* Largest grid (256-thread blocks, 8 elements per thread and trip) of the grid-stride elementwise kernels fk_gelu_bwd_bf16,
+ * fk_silu_bwd_bf16, fk_gate_res_fwd_bf16, fk_gelu_tanh_bf16: above 2048 * this many elements their threads loop. */
+int64_t fk_bwd_ew_max_blocks(void);
 /* Adjoint of fk_ln_modulate_bf16 for one stream (rows [b*rows_per_batch, (b+1)*rows_per_batch) use scale row b):
  *   dx_out = (dx_in ? dx_in : 0) + dLN/dx,   dshift[b] = sum_s dn,   dscale[b] = sum_s dn * LN(x)     (fp32 outputs;
  * dscale must be dshift + D: the (shift, scale) chunk pair of the block's modulation vector, batch stride given). */
@@ -361,7 +364,13 @@ int fk_ln_modulate_bwd_bf16(const void* x, fk_rows xr, const void* dn, fk_rows d
 int fk_gate_res_bwd_bf16(const void* dout, fk_rows dor, const void* y, fk_rows yr, const void* gate,
                          int64_t gate_batch_stride, int64_t rows_per_batch, void* dy, fk_rows dyr, float* dgate,
                          int64_t dgate_batch_stride, float* ws, int32_t B, int32_t N, fk_stream_t stream);
-/* out = df * gelu_tanh'(h) over n elements (h = the Linear's bf16 output before the activation); out may alias df. */
+/* out = df * gelu_tanh'(h) over n elements (h = the Linear's bf16 output before the activation); out may alias df.
+ * Accuracy of the activation kernels (fk_gelu_bwd_bf16, fk_silu_bwd_bf16, fk_gelu_tanh_bf16, fk_silu_bf16 and the GEMM
+ * epilogues of the same functions), every finite bf16 input: within 1 bf16 ulp of the exact function rounded once, finite
+ * wherever it is (the derivative of GELU(tanh) is 1 / 0 at |h| > 1.8e19, where fp32 h^2 overflows).  They form
+ * sigmoid(.) in fp32 on the hardware exp2 / rcp, which flush subnormal results: where the exact sigmoid is below 2^-126
+ * (h < -87.3 for SiLU, h < -10.05 for GELU(tanh)) the output is +-0, although the exact value -- at most 2^-126 times the
+ * factor that multiplies the sigmoid (|h|; |df| (1 + |h| ...) for the derivatives) -- may still be a normal bf16 number. */
 int fk_gelu_bwd_bf16(const void* h, const void* df, void* out, int64_t n, fk_stream_t stream);
 /* The same for FK_EPI_SILU (the denoise_projector's activation, modeling_univa_denoise_tower.py:36-41; the projector is
  * among the parameters train_denoiser.py:71-119 trains). */
@@ -393,6 +402,9 @@ int fk_rowdot_bf16(const void* a, int64_t a_ld, int64_t a_batch_stride, const vo
  * Host code only: the same per-kernel calls with the same arguments, in the same order, as the Python adaptor
  * (gpt_image_edit_amd/backward.py) -- bit-identical results.  Data gradients read the stored weights (fk_gemm_args.layout 1),
  * weight gradients both operands token-major (layout 2): B * S_txt and B * S_img must be multiples of 64.
+ * Batch: fk_single_block_bwd takes any B (its operands are whole [B, S, *] buffers); double blocks: B == 1 (the stream
+ * slices of a joint buffer are not uniformly strided, and the layout-2 GEMM addresses its second operand by one row stride).
+ * fk_double_block_bwd with B > 1 returns FK_EUNSUPPORTED before its first launch: nothing has been written.
  * fk_bwd_ws = shapes, scratch shared by every block of a pass, launch controls; caller-owned, nothing is allocated. */
 typedef struct fk_bwd_ws {
   int32_t B, S_txt, S_img, H;

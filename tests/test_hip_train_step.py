@@ -259,6 +259,107 @@ def test_block_level_backward_entry_points_give_the_same_bits(monkeypatch, which
     assert calls == before
 
 
+def _count_block_calls(monkeypatch, backward, calls):
+    for kind in ("single", "double"):
+        orig = getattr(backward.FluxBackward, f"_{kind}_backward_c")
+
+        def counted(self, *a, _orig=orig, _kind=kind, **k):
+            calls[_kind] += 1
+            return _orig(self, *a, **k)
+        monkeypatch.setattr(backward.FluxBackward, f"_{kind}_backward_c", counted)
+
+
+def test_single_block_backward_entry_point_at_batch_2(monkeypatch):
+    """fk_single_block_bwd takes any batch (include/fk.h: its operands are whole [B, S, *] buffers, so the weight-gradient
+    GEMM sees uniformly strided rows): at B = 2, with every parameter trainable, loss, d(prompt_embeds) and every gradient bit
+    for bit against the per-launch route.  The adaptor's own scope stays batch 1 (backward.BLOCK_API_MAX_BATCH); the test
+    widens it for the single block only, the double block stays on the per-launch route in both runs."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from gpt_image_edit_amd import backward, training
+    from gpt_image_edit_amd.train_step import DenoiserTrainStep
+    from gpt_image_edit_amd.transformer import HipFluxTransformer2DModel
+    assert backward.BLOCK_API_MAX_BATCH == {"single": 1, "double": 1}
+    cfg, sd_bf, batch, _ = _setup(B=2, S_txt=64, h=16, w=16)
+    trainable = training.trainable_names(list(sd_bf.keys()), only_img_branch=False)
+    monkeypatch.setitem(backward.BLOCK_API_MAX_BATCH, "single", 2)
+    calls = {"single": 0, "double": 0}
+    res = {}
+    for api in (0, 1):
+        monkeypatch.setattr(backward, "BLOCK_API", api)
+        model = HipFluxTransformer2DModel(cfg, device="cuda")
+        model.load_state_dict(sd_bf)
+        ts = DenoiserTrainStep(model, lr=1e-3, trainable=trainable, store_activations=True)
+        if api:
+            _count_block_calls(monkeypatch, backward, calls)
+        loss, grads, d_enc = ts.forward_backward(**{k: v.cuda() for k, v in batch.items()})
+        torch.cuda.synchronize()
+        res[api] = (loss.clone(), {k: v.clone() for k, v in grads.items()}, d_enc.clone())
+    assert calls == {"single": 1, "double": 0}, calls
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][2], res[1][2])
+    assert set(res[0][1]) == set(res[1][1]) and set(trainable) <= set(res[1][1])
+    worst = 0.0
+    for k in sorted(res[0][1]):
+        a, b = res[0][1][k], res[1][1][k]
+        worst = max(worst, (a.float() - b.float()).abs().max().item())
+        assert a.shape == b.shape and a.dtype == b.dtype and torch.equal(a, b), f"B = 2 single block: {k}"
+    assert all(torch.isfinite(v.float()).all() and v.float().abs().max() > 0 for v in res[1][1].values())
+    print(f"[parity] fk_single_block_bwd at B = 2: loss, d(prompt_embeds) and {len(res[1][1])} gradients bit-identical to the "
+          f"per-launch route (max |d| {worst})", flush=True)
+
+
+def test_double_block_backward_entry_point_refuses_batch_2(monkeypatch):
+    """fk_double_block_bwd at B > 1: the image / text slices of a joint [B, S, *] buffer have batch stride S * ld, not R * ld,
+    and the layout-2 GEMM addresses its second operand by one row stride -- every dw_* would sum the wrong token rows.  The
+    library refuses (include/fk.h: double blocks B == 1): FK_EUNSUPPORTED with the reason in fk_last_error(), before its first
+    launch -- the gradient of the residual stream, every scratch buffer and every gradient buffer are untouched."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from gpt_image_edit_amd import backward, libfk, training
+    from gpt_image_edit_amd.train_step import DenoiserTrainStep
+    from gpt_image_edit_amd.transformer import HipFluxTransformer2DModel
+    cfg, sd_bf, batch, _ = _setup(B=2, S_txt=64, h=16, w=16)
+    trainable = training.trainable_names(list(sd_bf.keys()), only_img_branch=False)
+    monkeypatch.setattr(backward, "BLOCK_API", 1)
+    monkeypatch.setitem(backward.BLOCK_API_MAX_BATCH, "double", 2)       # single block: per-launch route
+    held = {}
+    orig_ctx, orig_bufs = backward.FluxBackward._c_backward_ctx, backward.FluxBackward._double_grad_buffers
+
+    def ctx(self, sv, g):
+        held["cb"] = orig_ctx(self, sv, g)
+        return held["cb"]
+
+    def filled(self, i, dev):
+        out = orig_bufs(self, i, dev)
+        for t in out.values():
+            t.fill_(-7.0)
+        scratch = {k: t for k, t in held["cb"].bufs.items() if k not in ("red_ws", "attn_ws")}
+        held.update(out=out, scratch=scratch, before={k: t.clone() for k, t in scratch.items()})
+        torch.cuda.synchronize()
+        return out
+    monkeypatch.setattr(backward.FluxBackward, "_c_backward_ctx", ctx)
+    monkeypatch.setattr(backward.FluxBackward, "_double_grad_buffers", filled)
+    model = HipFluxTransformer2DModel(cfg, device="cuda")
+    model.load_state_dict(sd_bf)
+    ts = DenoiserTrainStep(model, lr=1e-3, trainable=trainable, store_activations=True)
+    with pytest.raises(RuntimeError) as err:
+        ts.forward_backward(**{k: v.cuda() for k, v in batch.items()})
+    torch.cuda.synchronize()
+    msg = str(err.value)
+    print(f"[parity] fk_double_block_bwd at B = 2: {msg}", flush=True)
+    assert held.get("cb") is not None and "out" in held, "the entry point was not reached"
+    FK_EUNSUPPORTED = -2                                                  # include/fk.h
+    assert f"(code {FK_EUNSUPPORTED})" in msg and "fk_double_block_bwd" in msg
+    assert "B = 2 unsupported" in msg and "B == 1" in msg and "not uniformly strided" in msg
+    assert msg.endswith(libfk.load().fk_last_error().decode())
+    assert len(held["out"]) >= 1 + 2 * 8                                  # dnorm, (dw, db) of the eight Linears
+    for k, t in held["out"].items():
+        assert (t == -7.0).all(), f"gradient buffer {k} was written"
+    assert held["before"]["g"].float().abs().max().item() > 0
+    for k, t in held["scratch"].items():
+        assert torch.equal(t, held["before"][k]), f"{k} was written"
+
+
 def test_sharded_gradient_accumulation_and_modified_gradient_error():
     """with sharded=True a second forward_backward before optimizer_step is a further micro-batch
     (the reference's gradient_accumulation_steps) -- its gradients are ADDED to the optimiser's chunks and the step uses
