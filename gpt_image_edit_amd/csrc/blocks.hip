@@ -95,6 +95,7 @@ int block_gemm(fk_gemm_args* g, int n, const Mx* mx, fk_stream_t st) {
     void* q = (char*)mx->ws->q + qo;
     void* s = (char*)mx->ws->s + so;
     FK_TRY(fk_quantize_mxfp8(g[i].A, g[i].a, g[i].M, K, q, K, s, K / 32, st));
+    if (mx->ws->quantize_launches) ++*mx->ws->quantize_launches;
     a[i].g = g[i];
     a[i].g.A = nullptr; a[i].g.W = nullptr;
     a[i].g.splitk_ws = nullptr; a[i].g.splitk_slots = 0;
@@ -107,9 +108,157 @@ int block_gemm(fk_gemm_args* g, int n, const Mx* mx, fk_stream_t st) {
   return fk_gemm_mxfp8_grouped(a, n, st);
 }
 
+// ---- fused MXFP8 schedule (fk_mx_ws.fused): the producers emit the quantized operand themselves -------------------------------
+// a dense quantized operand in the workspace: rows of K bytes at q, of K / 32 scale bytes at s
+struct Q8 {
+  uint8_t *q, *s;
+  int64_t ld, lds;
+};
+Q8 q8_at(const fk_mx_ws& m, int64_t byte_off, int64_t ld) {
+  return Q8{(uint8_t*)m.q + byte_off, (uint8_t*)m.s + byte_off / 32, ld, ld / 32};
+}
+Q8 q8_rows(const Q8& a, int64_t row0) { return Q8{a.q + row0 * a.ld, a.s + row0 * a.lds, a.ld, a.lds}; }
+
+// the mxfp8 form of problem g (epilogue fields kept) on the pre-quantized operand a8 and weight pair w
+int mx_problem(fk_gemm_mxfp8_args& a, const fk_gemm_args& g, const Q8& a8, const fk_mx_pair& w) {
+  FK_CHECK_ARG(w.q && w.s, "fk_*_block_fwd_mx: null quantized weight");
+  a = fk_gemm_mxfp8_args{};
+  a.g = g;
+  a.g.A = nullptr; a.g.W = nullptr;
+  a.g.splitk_ws = nullptr; a.g.splitk_slots = 0;
+  a.g.variant = 0; a.g.plan = 0; a.g.group_m = 0; a.g.mfma = 0;
+  a.A8 = a8.q; a.lda8 = a8.ld; a.A_scale = a8.s; a.lda_scale = a8.lds;
+  a.W8 = w.q; a.ldw8 = g.K; a.W_scale = w.s; a.ldw_scale = g.K / 32;
+  return FK_OK;
+}
+// n problems (img first) on pre-quantized operands; out: their quantized outputs (nullptr: the bf16 epilogue of g)
+int mx_gemm(const fk_gemm_args* g, int n, const Q8* a8, const fk_mx_pair* w, const Q8* out, int64_t col_offset, fk_stream_t st) {
+  if (!out) {
+    fk_gemm_mxfp8_args a[2];
+    for (int i = 0; i < n; ++i) FK_TRY(mx_problem(a[i], g[i], a8[i], w[i]));
+    return fk_gemm_mxfp8_grouped(a, n, st);
+  }
+  fk_gemm_mxfp8_q_args a[2];
+  for (int i = 0; i < n; ++i) {
+    FK_TRY(mx_problem(a[i].a, g[i], a8[i], w[i]));
+    a[i].a.g.C = nullptr;
+    a[i].Q = out[i].q; a[i].ldq = out[i].ld; a[i].Q_scale = out[i].s; a[i].ldq_scale = out[i].lds;
+    a[i].col_offset = col_offset;
+  }
+  return fk_gemm_mxfp8_q_grouped(a, n, st);
+}
+// the standalone quantizer on a bf16 view (what is left of it in the fused schedule: the attention output)
+int quantize_view(const fk_mx_ws& m, const View& x, int64_t M, int K, const Q8& o, fk_stream_t st) {
+  FK_TRY(fk_quantize_mxfp8(x.p, x.r, M, K, o.q, o.ld, o.s, o.lds, st));
+  if (m.quantize_launches) ++*m.quantize_launches;
+  return FK_OK;
+}
+// the workspace holds n8 (D bytes per row) and the block's consumer operand (operand_cols bytes per row) at once
+int check_fused_ws(const fk_mx_ws& m, const Dims& d, int operand_cols, const char* who) {
+  const int64_t need = (int64_t)d.B * d.S * (d.D + (int64_t)operand_cols);
+  FK_CHECK_ARG(m.q_bytes >= need && m.s_bytes >= need / 32,
+               "%s: the fused schedule needs a quantized-activation workspace of %lld + %lld bytes (given %lld + %lld)", who,
+               (long long)need, (long long)(need / 32), (long long)m.q_bytes, (long long)m.s_bytes);
+  return FK_OK;
+}
+
+int double_block_fused(const fk_block_ws& ws, const Dims& d, const fk_double_block_weights& w, const void* mod, int64_t mod_bs,
+                       fk_stream_t st, const fk_mx_ws& mxws, const fk_double_block_weights_mx& wx) {
+  FK_CHECK_ARG(ws.o && d.S_txt > 0, "fk_double_block_fwd_mx: needs the o buffer and a text stream");
+  FK_TRY(check_fused_ws(mxws, d, 4 * d.D, "fk_double_block_fwd_mx"));
+  const int D = d.D, B = d.B, Mi = B * d.S_img, Mt = B * d.S_txt;
+  const char* mi = (const char*)mod + w.mod_off_img * 2;
+  const char* mt = (const char*)mod + w.mod_off_txt * 2;
+  auto chunk = [&](const char* m, int j) { return (const void*)(m + (int64_t)j * D * 2); };
+  const View s_all = view(ws.s, d, D, 0, d.S, 0);
+  const View h = view(ws.s, d, D, d.S_txt, d.S_img, 0), cx = view(ws.s, d, D, 0, d.S_txt, 0);
+  const View none = View{nullptr, fk_rows{0, 0, 0}};
+  const int64_t M = (int64_t)B * d.S;
+  // every operand: the img rows first, then the txt rows (each stream dense, batch-major)
+  const Q8 n8 = q8_at(mxws, 0, D), o8 = q8_at(mxws, M * D, D), ff8 = q8_at(mxws, M * D, 4 * D);
+  const Q8 n8s[2] = {n8, q8_rows(n8, Mi)}, o8s[2] = {o8, q8_rows(o8, Mi)}, ff8s[2] = {ff8, q8_rows(ff8, Mi)};
+  FK_TRY(fk_ln_modulate2_mxfp8(s_all.p, s_all.r, n8s[1].q, n8s[1].s, n8s[0].q, n8s[0].s, n8.ld, n8.lds, chunk(mt, 0), chunk(mt, 1),
+                               chunk(mi, 0), chunk(mi, 1), d.S_txt, mod_bs, d.S, M, D, ws.eps, st));
+  {
+    fk_gemm_args g[2];
+    g[0] = gemm(none, nullptr, w.bqkv_img, view(ws.qkv, d, 3 * D, d.S_txt, d.S_img, 0), Mi, 3 * D, D, FK_EPI_QKV);
+    qkv_epi(g[0], ws, d, w.norm_q, w.norm_k, d.S_txt);
+    g[1] = gemm(none, nullptr, w.bqkv_txt, view(ws.qkv, d, 3 * D, 0, d.S_txt, 0), Mt, 3 * D, D, FK_EPI_QKV);
+    qkv_epi(g[1], ws, d, w.norm_added_q, w.norm_added_k, 0);
+    ctl(g[0], ws); FK_TRY(mx_gemm(g, 2, n8s, &wx.qkv_img, nullptr, 0, st));
+  }
+  FK_TRY(fk_attention_fwd_ws_bf16(ws.q, ws.k, (const char*)ws.qkv + (int64_t)2 * D * 2, ws.o, nullptr, B, d.H, d.S, 3 * D,
+                                  (int64_t)d.S * 3 * D, D, (int64_t)d.S * D, 0.08838834764831845f, ws.attn_ws, ws.attn_ws_bytes, ws.attn_grid, st));
+  {
+    const View oi = view(ws.o, d, D, d.S_txt, d.S_img, 0), ot = view(ws.o, d, D, 0, d.S_txt, 0);
+    FK_TRY(quantize_view(mxws, oi, Mi, D, o8s[0], st));
+    FK_TRY(quantize_view(mxws, ot, Mt, D, o8s[1], st));
+    fk_gemm_args g[2];
+    g[0] = gemm(none, nullptr, w.b_out, h, Mi, D, D, FK_EPI_GATE_RES);
+    gate_res(g[0], h, chunk(mi, 2), mod_bs, d.S_img);
+    g[1] = gemm(none, nullptr, w.b_add_out, cx, Mt, D, D, FK_EPI_GATE_RES);
+    gate_res(g[1], cx, chunk(mt, 2), mod_bs, d.S_txt);
+    ctl(g[0], ws); FK_TRY(mx_gemm(g, 2, o8s, &wx.out, nullptr, 0, st));
+  }
+  FK_TRY(fk_ln_modulate2_mxfp8(s_all.p, s_all.r, n8s[1].q, n8s[1].s, n8s[0].q, n8s[0].s, n8.ld, n8.lds, chunk(mt, 3), chunk(mt, 4),
+                               chunk(mi, 3), chunk(mi, 4), d.S_txt, mod_bs, d.S, M, D, ws.eps, st));
+  {
+    fk_gemm_args g[2];
+    g[0] = gemm(none, nullptr, w.b_ff1, none, Mi, 4 * D, D, FK_EPI_GELU_TANH);
+    g[1] = gemm(none, nullptr, w.b_ff1_ctx, none, Mt, 4 * D, D, FK_EPI_GELU_TANH);
+    ctl(g[0], ws); FK_TRY(mx_gemm(g, 2, n8s, &wx.ff1, ff8s, 0, st));
+  }
+  {
+    fk_gemm_args g[2];
+    g[0] = gemm(none, nullptr, w.b_ff2, h, Mi, D, 4 * D, FK_EPI_GATE_RES);
+    gate_res(g[0], h, chunk(mi, 5), mod_bs, d.S_img);
+    g[1] = gemm(none, nullptr, w.b_ff2_ctx, cx, Mt, D, 4 * D, FK_EPI_GATE_RES);
+    gate_res(g[1], cx, chunk(mt, 5), mod_bs, d.S_txt);
+    ctl(g[0], ws); FK_TRY(mx_gemm(g, 2, ff8s, &wx.ff2, nullptr, 0, st));
+  }
+  return FK_OK;
+}
+
+int single_block_fused(const fk_block_ws& ws, const Dims& d, const fk_single_block_weights& w, const void* mod, int64_t mod_bs,
+                       fk_stream_t st, const fk_mx_ws& mxws, const fk_single_block_weights_mx& wx) {
+  FK_CHECK_ARG(ws.cat != nullptr, "fk_single_block_fwd_mx: needs the [attn | mlp] buffer");
+  FK_TRY(check_fused_ws(mxws, d, 5 * d.D, "fk_single_block_fwd_mx"));
+  const int D = d.D, B = d.B;
+  const int Ms = B * d.S;
+  const char* m0 = (const char*)mod + w.mod_off * 2;     // shift, scale, gate
+  auto chunk = [&](int j) { return (const void*)(m0 + (int64_t)j * D * 2); };
+  const View s_all = view(ws.s, d, D, 0, d.S, 0);
+  const View none = View{nullptr, fk_rows{0, 0, 0}};
+  const Q8 n8 = q8_at(mxws, 0, D), cat8 = q8_at(mxws, (int64_t)Ms * D, 5 * D);
+  // n8 once: the QKV and the MLP-up GEMM read the same quantized rows
+  FK_TRY(fk_ln_modulate_mxfp8(s_all.p, s_all.r, n8.q, n8.ld, n8.s, n8.lds, chunk(0), chunk(1), mod_bs, d.S, (int64_t)Ms, D, ws.eps, st));
+  {
+    fk_gemm_args g = gemm(none, nullptr, w.bqkv, view(ws.qkv, d, 3 * D, 0, d.S, 0), Ms, 3 * D, D, FK_EPI_QKV);
+    qkv_epi(g, ws, d, w.norm_q, w.norm_k, 0);
+    ctl(g, ws); FK_TRY(mx_gemm(&g, 1, &n8, &wx.qkv, nullptr, 0, st));
+  }
+  FK_TRY(fk_attention_fwd_ws_bf16(ws.q, ws.k, (const char*)ws.qkv + (int64_t)2 * D * 2, ws.cat, nullptr, B, d.H, d.S, 3 * D,
+                                  (int64_t)d.S * 3 * D, 5 * D, (int64_t)d.S * 5 * D, 0.08838834764831845f, ws.attn_ws,
+                                  ws.attn_ws_bytes, ws.attn_grid, st));
+  {
+    // columns [0, D) of cat8 from the attention output, columns [D, 5D) straight from the MLP-up GEMM's epilogue
+    const View att = view(ws.cat, d, 5 * D, 0, d.S, 0);
+    FK_TRY(quantize_view(mxws, att, Ms, D, cat8, st));
+    fk_gemm_args g = gemm(none, nullptr, w.b_mlp, none, Ms, 4 * D, D, FK_EPI_GELU_TANH);
+    ctl(g, ws); FK_TRY(mx_gemm(&g, 1, &n8, &wx.mlp, &cat8, D, st));
+  }
+  {
+    fk_gemm_args g = gemm(none, nullptr, w.b_out, s_all, Ms, D, 5 * D, FK_EPI_GATE_RES);
+    gate_res(g, s_all, chunk(2), mod_bs, d.S);
+    ctl(g, ws); FK_TRY(mx_gemm(&g, 1, &cat8, &wx.out, nullptr, 0, st));
+  }
+  return FK_OK;
+}
+
 int double_block(const fk_block_ws& ws, const Dims& d, const fk_double_block_weights& w, const void* mod, int64_t mod_bs,
                  fk_stream_t st, const fk_mx_ws* mxws = nullptr,
                  const fk_double_block_weights_mx* wx = nullptr) {
+  if (mxws && wx && mxws->fused) return double_block_fused(ws, d, w, mod, mod_bs, st, *mxws, *wx);
   FK_CHECK_ARG(ws.o && ws.ff && d.S_txt > 0, "fk_double_block_fwd: needs the o / ff buffers and a text stream");
   // the img / txt weight pairs of a launch are adjacent members of fk_double_block_weights_mx (qkv_img | qkv_txt, out | add_out, ...)
   Mx mxc;
@@ -166,6 +315,7 @@ int double_block(const fk_block_ws& ws, const Dims& d, const fk_double_block_wei
 
 int single_block(const fk_block_ws& ws, const Dims& d, const fk_single_block_weights& w, const void* mod, int64_t mod_bs,
                  fk_stream_t st, const fk_mx_ws* mxws = nullptr, const fk_single_block_weights_mx* wx = nullptr) {
+  if (mxws && wx && mxws->fused) return single_block_fused(ws, d, w, mod, mod_bs, st, *mxws, *wx);
   Mx mxc;
   auto mx = [&](const fk_mx_pair* pair) -> const Mx* { if (!pair) return nullptr; mxc = Mx{mxws, pair}; return &mxc; };
   FK_CHECK_ARG(ws.cat != nullptr, "fk_single_block_fwd: needs the [attn | mlp] buffer");
@@ -227,7 +377,7 @@ extern "C" int fk_mmdit_blocks_fwd(const fk_block_ws* ws, const fk_double_block_
   return FK_OK;
 }
 
-// ---- MXFP8 forms: the same launches with every block GEMM as quantize -> fk_gemm_mxfp8 ------------------------------------
+// ---- MXFP8 forms: the same launches with every block GEMM as quantize -> fk_gemm_mxfp8, or (fk_mx_ws.fused) the fused schedule
 namespace {
 int check_mx(const fk_mx_ws* mx, const char* who) {
   FK_CHECK_ARG(mx && mx->q && mx->s && (uintptr_t)mx->q % 16 == 0 && (uintptr_t)mx->s % 4 == 0,
@@ -265,6 +415,10 @@ extern "C" int fk_mmdit_blocks_fwd_mx(const fk_block_ws* ws, const fk_mx_ws* mx,
   FK_TRY(check_mx(mx, "fk_mmdit_blocks_fwd_mx"));
   FK_CHECK_ARG(mod && n_double >= 0 && n_single >= 0 && (n_double == 0 || (dbl && dblx)) && (n_single == 0 || (sgl && sglx)),
                "fk_mmdit_blocks_fwd_mx: null weights / modulation");
+  if (mx->fused) {   // before the first launch: nothing runs against a workspace that a later block would overrun
+    if (n_double > 0) FK_TRY(check_fused_ws(*mx, d, 4 * d.D, "fk_mmdit_blocks_fwd_mx"));
+    if (n_single > 0) FK_TRY(check_fused_ws(*mx, d, 5 * d.D, "fk_mmdit_blocks_fwd_mx"));
+  }
   for (int i = 0; i < n_double; ++i) FK_TRY(double_block(*ws, d, dbl[i], mod, mod_batch_stride, stream, mx, &dblx[i]));
   for (int i = 0; i < n_single; ++i) FK_TRY(single_block(*ws, d, sgl[i], mod, mod_batch_stride, stream, mx, &sglx[i]));
   return FK_OK;

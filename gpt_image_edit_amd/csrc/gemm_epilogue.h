@@ -4,6 +4,8 @@
 // through a config struct that provides NF, MF, M16, NTHREADS, CT_LD, tile_row and tile_col).
 #pragma once
 
+#include "mxfp8_quant.h"   // store_tile_mxq's quantizer arithmetic
+
 constexpr int BM = 256;
 
 // fk_rows addressing of the (at most BM) rows of one tile without per-row 64-bit divisions: one division per tile
@@ -294,6 +296,87 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
         }
       }
       if (ml <= mlast && n < p.N) *(u32x4_t*)(cbase + coff[u]) = o;
+    }
+  }
+}
+
+// Quantized-output epilogue (gemm_mxfp8.hip: gemm_mxq_kernel): the tile goes to
+// LDS as bf16 exactly as store_tile puts it there -- bias, bf16 rounding of the Linear's output in front of the activation, bf16
+// rounding of the result: the existing rounding points -- and every 32-column block of a row then leaves as 32 e4m3 bytes plus
+// one E8M0 byte, the bytes fk_quantize_mxfp8 gives for the bf16 tile store_tile would have written.  Nothing is stored as
+// bf16.  A thread owns one block per iteration: row m at q + m * ldq + n (q / s are already advanced to the caller's column
+// window; N % 256 == 0, so only rows are predicated); the BN / 32 threads of a tile row write BN consecutive bytes.
+template <int EPI, int BN, class C>
+FK_DEV void store_tile_mxq(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& p, uint8_t* __restrict__ q,
+                           uint8_t* __restrict__ s, int64_t ldq, int64_t ld_scale, char* smem, int m0, int n0, int wm, int wn) {
+  static_assert(EPI == FK_EPI_NONE || EPI == FK_EPI_GELU_TANH, "quantized output: plain and GELU epilogues");
+  const int tid = threadIdx.x, lane = tid & 63;
+  using FM = FragMap<C::M16>;
+  u32x2_t bw[C::NF][4];
+#pragma unroll
+  for (int nf = 0; nf < C::NF; ++nf)
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) bw[nf][qd] = u32x2_t{0u, 0u};
+  if (p.bias) {
+#pragma unroll
+    for (int nf = 0; nf < C::NF; ++nf)
+#pragma unroll
+      for (int qd = 0; qd < 4; ++qd) {
+        const int n = n0 + C::tile_col(wn, nf) + FM::col(lane, qd);
+        bw[nf][qd] = *(const u32x2_t*)((const bf16_t*)p.bias + min(n, p.N - 4));
+      }
+  }
+  __syncthreads();  // every wave is done reading the last stage before the C tile aliases it
+  bf16_t* ct = (bf16_t*)smem;
+#pragma unroll
+  for (int nf = 0; nf < C::NF; ++nf) {
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+      const int nl = C::tile_col(wn, nf) + FM::col(lane, qd);
+      const float b[4] = {bf_lo(bw[nf][qd][0]), bf_hi(bw[nf][qd][0]), bf_lo(bw[nf][qd][1]), bf_hi(bw[nf][qd][1])};
+#pragma unroll
+      for (int mf = 0; mf < C::MF; ++mf) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = acc[nf][mf][qd * 4 + j] + b[j];
+        if constexpr (EPI == FK_EPI_GELU_TANH) {
+          round_bf_pair(v[0], v[1]);
+          round_bf_pair(v[2], v[3]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = gelu_tanh_f(v[j]);
+        }
+        u32x2_t pk;
+        pk[0] = pack_bf2(v[0], v[1]);
+        pk[1] = pack_bf2(v[2], v[3]);
+        const int ml = C::tile_row(wm, mf) + FM::row(lane, qd);
+        *(u32x2_t*)(ct + ml * C::CT_LD + nl) = pk;
+      }
+    }
+  }
+  __syncthreads();
+  constexpr int BPR = BN / 32;                      // 32-column blocks per tile row
+  constexpr int ITERS = BM * BPR / C::NTHREADS;
+  constexpr int ML_STEP = C::NTHREADS / BPR;
+  static_assert(C::NTHREADS % BPR == 0 && (BM * BPR) % C::NTHREADS == 0, "quantized epilogue tiling");
+  const int bc = tid % BPR, ml0 = tid / BPR;
+  const int mlast = p.M - 1 - m0;                   // last valid tile row
+#pragma unroll
+  for (int j = 0; j < ITERS; ++j) {
+    const int ml = ml0 + ML_STEP * j;
+    const u32x4_t* src = (const u32x4_t*)(ct + ml * C::CT_LD + bc * 32);
+    uint32_t w[16], out[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const u32x4_t v = src[i];
+      w[4 * i] = v[0]; w[4 * i + 1] = v[1]; w[4 * i + 2] = v[2]; w[4 * i + 3] = v[3];
+    }
+    const uint32_t sbyte = mx_quant_block(w, out);
+    if (ml <= mlast) {
+      const int64_t m = (int64_t)m0 + ml;
+      u32x4_t* dst = (u32x4_t*)(q + m * ldq + n0 + bc * 32);
+      dst[0] = u32x4_t{out[0], out[1], out[2], out[3]};
+      dst[1] = u32x4_t{out[4], out[5], out[6], out[7]};
+      s[m * ld_scale + (n0 >> 5) + bc] = (uint8_t)sbyte;
     }
   }
 }

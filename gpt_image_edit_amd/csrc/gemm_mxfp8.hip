@@ -2,6 +2,8 @@
 //
 //   fk_quantize_mxfp8   bf16 rows (fk_rows addressing) -> e4m3 [M, K] + E8M0 [M, K / 32], one pass, one thread per block of 32
 //   gemm_mxfp8_kernel   C = epilogue(deq(A) . deq(W)^T + bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (both operands e4m3)
+//   gemm_mxq_kernel     the same tile, its bf16-rounded result stored as e4m3 + E8M0 (gemm_epilogue.h: store_tile_mxq): the
+//                       producer form for a GEMM whose only consumer is another MXFP8 GEMM (fk_gemm_mxfp8_q)
 //
 // The GEMM keeps the bf16 kernels' conventions so that their epilogue (gemm_epilogue.h: store_tile) takes its accumulators
 // unchanged: operands swapped (W rows -> MFMA src0, activation rows -> src1), 8 waves as 2 (M) x 4 (N), a wave's output the
@@ -24,20 +26,11 @@
 
 namespace {
 
-#include "gemm_epilogue.h"   // BM, TileRows, row16_sum, xcd_chunk_index, FragMap, store_tile
+#include "gemm_epilogue.h"   // BM, TileRows, row16_sum, xcd_chunk_index, FragMap, store_tile, store_tile_mxq; mxfp8_quant.h
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;   // 32 e4m3 bytes: the 16 x 16 x 128 operand of one lane
 
 // ---- quantizer ----------------------------------------------------------------------------------------------------------
-// |v| < 512 (v = x / 2^e with e >= floor(log2 amax) - 8) -> e4m3fn magnitude code, round-to-nearest-even, saturated to 448
-FK_DEV uint32_t e4m3_mag(float a) {
-  a = fminf(a, 448.0f);
-  if (a < 0.015625f) return (uint32_t)__builtin_rintf(a * 512.0f);   // subnormal: k * 2^-9, k = 0..8 (8 = the smallest normal)
-  uint32_t u = __float_as_uint(a);
-  u += 0x7ffffu + ((u >> 20) & 1u);      // round the fp32 mantissa to 3 bits (a carry moves into the exponent)
-  return (u >> 20) - (120u << 3);        // (biased exp - 127 + 7) << 3 | mantissa
-}
-
 __global__ __launch_bounds__(256) void quantize_mxfp8_kernel(const bf16_t* __restrict__ x, fk_rows xr, int64_t M, int K,
                                                              uint8_t* __restrict__ q, int64_t ldq, uint8_t* __restrict__ sc,
                                                              int64_t ld_scale) {
@@ -53,32 +46,8 @@ __global__ __launch_bounds__(256) void quantize_mxfp8_kernel(const bf16_t* __res
     const u32x4_t v = src[i];
     w[4 * i] = v[0]; w[4 * i + 1] = v[1]; w[4 * i + 2] = v[2]; w[4 * i + 3] = v[3];
   }
-  // amax as bf16 magnitude bits: they order like the values, Inf = 0x7f80, NaN above
-  uint32_t amax = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) amax = max(amax, max(w[i] & 0x7fffu, (w[i] >> 16) & 0x7fffu));
-  uint32_t sbyte, out[8];
-  if (amax >= 0x7f80u) {   // Inf / NaN: NaN scale and NaN elements
-    sbyte = 0xffu;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) out[i] = 0x7f7f7f7fu;
-  } else {
-    // e = max(floor(log2 amax) - 8, -127); byte = e + 127 (bf16 exponent field E: floor(log2) = E - 127; subnormal: clamped)
-    const int E = (int)(amax >> 7);
-    sbyte = amax == 0 ? 127u : (uint32_t)max(E - 8, 0);
-    const float inv = __uint_as_float((254u - sbyte) << 23);   // 2^-e, exact (254 - byte in [8, 254] for finite blocks)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      uint32_t o = 0;
-#pragma unroll
-      for (int h = 0; h < 4; ++h) {
-        const uint32_t b = (h & 1) ? (w[2 * i + (h >> 1)] >> 16) : (w[2 * i + (h >> 1)] & 0xffffu);
-        const float v = __uint_as_float((b & 0x7fffu) << 16) * inv;
-        o |= (e4m3_mag(v) | ((b >> 8) & 0x80u)) << (8 * h);
-      }
-      out[i] = o;
-    }
-  }
+  uint32_t out[8];
+  const uint32_t sbyte = mx_quant_block(w, out);
   u32x4_t* dst = (u32x4_t*)(q + m * ldq + j * 32);
   dst[0] = u32x4_t{out[0], out[1], out[2], out[3]};
   dst[1] = u32x4_t{out[4], out[5], out[6], out[7]};
@@ -120,8 +89,20 @@ FK_DEV void wait_vm() {
   else static_assert(N == 0, "add the vmcnt literal");
 }
 
-template <int EPI, int BN>
-__global__ __launch_bounds__(512, 2) void gemm_mxfp8_kernel(const MxGroup ga) {
+// quantized output of problem i of a launch (fk_gemm_mxfp8_q_args): bytes / scales already advanced to the column window
+struct MxQOut {
+  uint8_t* q;
+  uint8_t* s;
+  int64_t ldq, ld_scale;
+};
+struct MxGroupQ {
+  MxGroup g;
+  MxQOut o[FK_MAX_GROUP];
+};
+
+// one output tile; QOUT: the quantized-output epilogue into qo[problem] instead of store_tile
+template <int EPI, int BN, bool QOUT>
+FK_DEV void mx_tile(const MxGroup& ga, const MxQOut* qo) {
   using C = CfgMx<BN>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = xcd_chunk_index();
@@ -242,7 +223,18 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_kernel(const MxGroup ga) {
     }
     __syncthreads();
   }
-  store_tile<EPI, BN, C>(acc, p, smem, m0, n0, wm, wn);
+  if constexpr (QOUT) store_tile_mxq<EPI, BN, C>(acc, p, qo[pi].q, qo[pi].s, qo[pi].ldq, qo[pi].ld_scale, smem, m0, n0, wm, wn);
+  else store_tile<EPI, BN, C>(acc, p, smem, m0, n0, wm, wn);
+}
+
+template <int EPI, int BN>
+__global__ __launch_bounds__(512, 2) void gemm_mxfp8_kernel(const MxGroup ga) {
+  mx_tile<EPI, BN, false>(ga, nullptr);
+}
+
+template <int EPI, int BN>
+__global__ __launch_bounds__(512, 2) void gemm_mxq_kernel(const MxGroupQ gq) {
+  mx_tile<EPI, BN, true>(gq.g, gq.o);
 }
 
 int cu_count_mx() {
@@ -266,6 +258,16 @@ int launch_mx(MxGroup& ga, int tiles, hipStream_t stream) {
   return FK_OK;
 }
 
+template <int EPI, int BN>
+int launch_mxq(MxGroupQ& gq, int tiles, hipStream_t stream) {
+  using C = CfgMx<BN>;
+  auto kern = gemm_mxq_kernel<EPI, BN>;
+  FK_ENSURE_MAX_LDS(kern, C::SMEM_BYTES, "fk_gemm_mxfp8_q");
+  hipLaunchKernelGGL(kern, dim3(tiles), dim3(C::NTHREADS), C::SMEM_BYTES, stream, gq);
+  FK_CHECK_LAUNCH("fk_gemm_mxfp8_q");
+  return FK_OK;
+}
+
 template <int EPI>
 int launch_mx_bn(MxGroup& ga, int tiles, int bn, hipStream_t stream) {
   return bn == 256 ? launch_mx<EPI, 256>(ga, tiles, stream) : launch_mx<EPI, 128>(ga, tiles, stream);
@@ -278,9 +280,10 @@ bool rows32(const fk_rows& r, int elem) {
   return !(r.rows_per_batch > 0 && r.batch_stride < r.rows_per_batch * r.ld);
 }
 
-int validate_mx(const fk_gemm_mxfp8_args& a, const char* fn) {
+// qout: the quantized-output form (fk_gemm_mxfp8_q) -- g.C / g.c are unused, the epilogue is FK_EPI_NONE or GELU_TANH
+int validate_mx(const fk_gemm_mxfp8_args& a, const char* fn, bool qout = false) {
   const fk_gemm_args& p = a.g;
-  FK_CHECK_ARG(a.A8 && a.A_scale && a.W8 && a.W_scale && p.C, "%s: null operand, scale or output pointer", fn);
+  FK_CHECK_ARG(a.A8 && a.A_scale && a.W8 && a.W_scale && (qout || p.C), "%s: null operand, scale or output pointer", fn);
   FK_CHECK_ARG(p.M >= 0 && p.N > 0 && p.K > 0, "%s: M %d N %d K %d", fn, p.M, p.N, p.K);
   if (p.K % 128 != 0 || p.N % 256 != 0) {
     fk_set_error("%s: needs K %% 128 == 0 and N %% 256 == 0 (M %d N %d K %d)", fn, p.M, p.N, p.K);
@@ -293,9 +296,15 @@ int validate_mx(const fk_gemm_mxfp8_args& a, const char* fn) {
                  "and FK_EPI_NONE with out_fp32 = 2, layout 0", fn, p.epilogue, p.out_fp32, p.layout);
     return FK_EUNSUPPORTED;
   }
+  if (qout && (p.out_fp32 != 0 || !(p.epilogue == FK_EPI_NONE || p.epilogue == FK_EPI_GELU_TANH))) {
+    fk_set_error("%s: the quantized output takes FK_EPI_NONE or FK_EPI_GELU_TANH (epilogue %d, out_fp32 %d)", fn, p.epilogue, p.out_fp32);
+    return FK_EUNSUPPORTED;
+  }
   // the output / bias / residual / gate / QKV fields as fk_gemm_bf16 checks them (the epilogue is the same code)
-  FK_CHECK_ARG((uintptr_t)p.C % 16 == 0, "%s: C must be 16-byte aligned", fn);
-  if (p.out_fp32 == 2)
+  FK_CHECK_ARG(qout || (uintptr_t)p.C % 16 == 0, "%s: C must be 16-byte aligned", fn);
+  if (qout)
+    FK_CHECK_ARG(!p.bias || (uintptr_t)p.bias % 8 == 0, "%s: bias must be 8-byte aligned", fn);
+  else if (p.out_fp32 == 2)
     FK_CHECK_ARG(p.c.ld % 4 == 0 && (p.c.rows_per_batch <= 0 || p.c.batch_stride % 4 == 0) && (!p.bias || (uintptr_t)p.bias % 8 == 0),
                  "%s: out_fp32 = 2 needs ldc %% 4 == 0 and an 8-byte aligned bias", fn);
   else
@@ -329,7 +338,7 @@ int validate_mx(const fk_gemm_mxfp8_args& a, const char* fn) {
                "%s: operands must be 16-byte, scales 4-byte aligned", fn);
   const bool res = p.epilogue == FK_EPI_GATE_RES;
   if ((long long)BM * a.lda8 >= (1ll << 31) || (long long)BM * a.ldw8 >= (1ll << 31) || (long long)BM * a.lda_scale >= (1ll << 31) ||
-      (long long)BM * a.ldw_scale >= (1ll << 31) || !rows32(p.c, p.out_fp32 == 2 ? 4 : 2) || (res && !rows32(p.r, 2))) {
+      (long long)BM * a.ldw_scale >= (1ll << 31) || (!qout && !rows32(p.c, p.out_fp32 == 2 ? 4 : 2)) || (res && !rows32(p.r, 2))) {
     fk_set_error("%s: row strides must keep a 256-row tile within 2 GiB", fn);
     return FK_EUNSUPPORTED;
   }
@@ -403,4 +412,60 @@ extern "C" int fk_gemm_mxfp8_grouped(const fk_gemm_mxfp8_args* args, int32_t n, 
 extern "C" int fk_gemm_mxfp8(const fk_gemm_mxfp8_args* args, fk_stream_t stream) {
   FK_CHECK_ARG(args != nullptr, "fk_gemm_mxfp8: null args");
   return fk_gemm_mxfp8_grouped(args, 1, stream);
+}
+
+// The quantized-output form: the same launch plan and main loop; the tile leaves as e4m3 bytes + E8M0 scale bytes in a column
+// window [col_offset, col_offset + N) of a [M, ldq] byte buffer (scales: [col_offset / 32, ..) of [M, ldq_scale]).
+extern "C" int fk_gemm_mxfp8_q_grouped(const fk_gemm_mxfp8_q_args* args, int32_t n, fk_stream_t stream_) {
+  FK_CHECK_ARG(args != nullptr && n >= 1 && n <= FK_MAX_GROUP, "fk_gemm_mxfp8_q_grouped: 1 <= n <= %d", FK_MAX_GROUP);
+  const char* fn = n == 1 ? "fk_gemm_mxfp8_q" : "fk_gemm_mxfp8_q_grouped";
+  const fk_gemm_args& c0 = args[0].a.g;
+  for (int i = 0; i < n; ++i) {
+    const fk_gemm_mxfp8_q_args& a = args[i];
+    const int rc = validate_mx(a.a, fn, true);
+    if (rc != FK_OK) return rc;
+    const fk_gemm_args& g = a.a.g;
+    FK_CHECK_ARG(g.N == c0.N && g.K == c0.K && g.epilogue == c0.epilogue, "%s: all problems must share N, K and the epilogue", fn);
+    FK_CHECK_ARG(a.Q && a.Q_scale, "%s: null quantized output", fn);
+    FK_CHECK_ARG(a.col_offset >= 0 && a.col_offset % 32 == 0, "%s: column offset %lld must be a multiple of 32", fn,
+                 (long long)a.col_offset);
+    FK_CHECK_ARG(a.ldq >= a.col_offset + g.N && a.ldq_scale >= (a.col_offset + g.N) / 32,
+                 "%s: ldq %lld / ldq_scale %lld do not hold columns [%lld, %lld)", fn, (long long)a.ldq, (long long)a.ldq_scale,
+                 (long long)a.col_offset, (long long)(a.col_offset + g.N));
+    FK_CHECK_ARG((uintptr_t)a.Q % 16 == 0 && a.ldq % 16 == 0 && (uintptr_t)a.Q_scale % 4 == 0 && a.ldq_scale % 4 == 0,
+                 "%s: output byte rows must be 16-byte aligned (Q, ldq %lld), scale rows 4-byte aligned (Q_scale, ldq_scale %lld)", fn,
+                 (long long)a.ldq, (long long)a.ldq_scale);
+  }
+  FK_CHECK_ARG(c0.variant == 0 || c0.variant == 128 || c0.variant == 256, "%s: variant %d is not 0, 128 or 256", fn, c0.variant);
+  MxGroupQ gq;
+  MxGroup& ga = gq.g;
+  ga.n = n;
+  long nbm = 0;
+  ga.tiles_before[0] = 0;
+  for (int i = 0; i < FK_MAX_GROUP; ++i) {
+    const fk_gemm_mxfp8_q_args& a = args[i < n ? i : 0];
+    ga.p[i] = a.a;
+    gq.o[i] = MxQOut{(uint8_t*)a.Q + a.col_offset, (uint8_t*)a.Q_scale + a.col_offset / 32, a.ldq, a.ldq_scale};
+  }
+  for (int i = 0; i < n; ++i) nbm += (args[i].a.g.M + BM - 1) / BM;
+  const long t256 = nbm * (c0.N / 256);   // the launch plan of fk_gemm_mxfp8_grouped
+  const int bn = c0.variant ? c0.variant : (t256 < cu_count_mx() ? 128 : 256);
+  long tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    ga.tiles_before[i] = (int)tiles;
+    tiles += (long)((args[i].a.g.M + BM - 1) / BM) * (c0.N / bn);
+  }
+  for (int i = n; i <= FK_MAX_GROUP; ++i) ga.tiles_before[i] = (int)tiles;
+  if (c0.variant_used) *c0.variant_used = bn;
+  if (tiles == 0) return FK_OK;
+  FK_CHECK_ARG(tiles < (1l << 31), "%s: too many tiles", fn);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (c0.epilogue == FK_EPI_GELU_TANH)
+    return bn == 256 ? launch_mxq<FK_EPI_GELU_TANH, 256>(gq, (int)tiles, stream) : launch_mxq<FK_EPI_GELU_TANH, 128>(gq, (int)tiles, stream);
+  return bn == 256 ? launch_mxq<FK_EPI_NONE, 256>(gq, (int)tiles, stream) : launch_mxq<FK_EPI_NONE, 128>(gq, (int)tiles, stream);
+}
+
+extern "C" int fk_gemm_mxfp8_q(const fk_gemm_mxfp8_q_args* args, fk_stream_t stream) {
+  FK_CHECK_ARG(args != nullptr, "fk_gemm_mxfp8_q: null args");
+  return fk_gemm_mxfp8_q_grouped(args, 1, stream);
 }

@@ -46,6 +46,10 @@ class GemmMxfp8Args(ctypes.Structure):   # fk_gemm_mxfp8_args
     ]
 
 
+class GemmMxfp8QArgs(ctypes.Structure):   # fk_gemm_mxfp8_q_args: the GEMM with a quantized (MXFP8) output
+    _fields_ = [("a", GemmMxfp8Args), ("Q", c_vp), ("ldq", c_i64), ("Q_scale", c_vp), ("ldq_scale", c_i64), ("col_offset", c_i64)]
+
+
 class AttnView(ctypes.Structure):
     _fields_ = [("p", c_vp), ("ld", c_i64), ("head_stride", c_i64), ("batch_stride", c_i64)]
 
@@ -123,7 +127,8 @@ class SingleBlockWeightsMx(ctypes.Structure):   # fk_single_block_weights_mx
 
 
 class MxWs(ctypes.Structure):                 # fk_mx_ws
-    _fields_ = [("q", c_vp), ("s", c_vp), ("q_bytes", c_i64), ("s_bytes", c_i64)]
+    _fields_ = [("q", c_vp), ("s", c_vp), ("q_bytes", c_i64), ("s_bytes", c_i64), ("fused", c_i32),
+                ("quantize_launches", ctypes.POINTER(c_i32))]
 
 
 # symbol -> (restype, argtypes); must list every entry point of include/fk.h
@@ -133,6 +138,11 @@ SIGNATURES = {
     "fk_quantize_mxfp8": (c_i32, [c_vp, Rows, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "fk_gemm_mxfp8": (c_i32, [ctypes.POINTER(GemmMxfp8Args), c_vp]),
     "fk_gemm_mxfp8_grouped": (c_i32, [ctypes.POINTER(GemmMxfp8Args), c_i32, c_vp]),
+    "fk_gemm_mxfp8_q": (c_i32, [ctypes.POINTER(GemmMxfp8QArgs), c_vp]),
+    "fk_gemm_mxfp8_q_grouped": (c_i32, [ctypes.POINTER(GemmMxfp8QArgs), c_i32, c_vp]),
+    "fk_ln_modulate_mxfp8": (c_i32, [c_vp, Rows, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_f32, c_vp]),
+    "fk_ln_modulate2_mxfp8": (c_i32, [c_vp, Rows, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                      c_i64, c_i32, c_f32, c_vp]),
     "fk_ln_modulate_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_f32, c_vp]),
     "fk_ln_modulate2_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_f32, c_vp]),
     "fk_qkv_post_bf16": (c_i32, [c_vp] * 9 + [c_i32] * 4 + [c_f32, c_vp]),

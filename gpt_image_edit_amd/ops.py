@@ -12,7 +12,7 @@ import torch
 
 from . import libfk, param_tree
 from .libfk import (FK_EPI_GATE_RES, FK_EPI_GELU_TANH, FK_EPI_NONE, FK_EPI_QKV, FK_EPI_RES, FK_EPI_SCALE,  # noqa: F401
-                    FK_EPI_SILU, GemmArgs, GemmMxfp8Args, Rows)
+                    FK_EPI_SILU, GemmArgs, GemmMxfp8Args, GemmMxfp8QArgs, Rows)
 
 BF16 = torch.bfloat16
 
@@ -292,6 +292,15 @@ def gemm_grouped(problems, epilogue=FK_EPI_NONE):
 
 # ---- MXFP8 (opt-in inference format of the block GEMMs; include/fk.h) --------------------------------------------------------
 MXFP8_BLOCK = 32
+# launches of the standalone quantizer since import: those of quantize_mxfp8() below, and those the block-level C entry points
+# enqueue (they count into the int32 that fk_mx_ws.quantize_launches names).  Tests read the difference around a forward: the
+# fused schedule leaves 2 per double block and 1 per single block.
+QUANTIZE_LAUNCHES = [0]
+_QUANTIZE_SLOT = ctypes.c_int32(0)
+
+
+def quantize_launch_count():
+    return QUANTIZE_LAUNCHES[0] + int(_QUANTIZE_SLOT.value)
 
 
 def quantize_mxfp8(x, q=None, scales=None):
@@ -314,12 +323,70 @@ def quantize_mxfp8(x, q=None, scales=None):
         raise ValueError(f"quantize_mxfp8: q must be uint8 [{M}, {K}] and scales uint8 [{M}, {K // MXFP8_BLOCK}], rows contiguous")
     libfk.check(libfk.load().fk_quantize_mxfp8(x.data_ptr(), rx, M, K, q.data_ptr(), q.stride(0), scales.data_ptr(),
                                                 scales.stride(0), _stream()), "fk_quantize_mxfp8")
+    QUANTIZE_LAUNCHES[0] += 1
     return q, scales
 
 
+def _mx_pair_out(out, M, K, device, what):
+    """(q, scales) uint8 [M, >= K] / [M, >= K / 32] row-strided views for a producer's quantized output (allocated when None)."""
+    if out is None:
+        return (torch.empty((M, K), device=device, dtype=torch.uint8),
+                torch.empty((M, K // MXFP8_BLOCK), device=device, dtype=torch.uint8))
+    q, sc = out
+    _need_cuda(q, sc)
+    if (q.dtype != torch.uint8 or sc.dtype != torch.uint8 or q.dim() != 2 or sc.dim() != 2 or tuple(q.shape) != (M, K)
+            or tuple(sc.shape) != (M, K // MXFP8_BLOCK) or q.stride(1) != 1 or sc.stride(1) != 1):
+        raise ValueError(f"{what}: the output is a (uint8 [{M}, {K}], uint8 [{M}, {K // MXFP8_BLOCK}]) pair, rows contiguous")
+    return q, sc
+
+
+def ln_modulate_mxfp8(x, shift, scale, out=None, eps=1e-6):
+    """:func:`ln_modulate` with its result stored as MXFP8: returns the (q [B * R, D], scales [B * R, D / 32]) pair that
+    :func:`quantize_mxfp8` gives for ``ln_modulate(x, shift, scale)``, bit for bit; the bf16 rows are never written.  ``out``: such
+    a pair (row-strided views of wider buffers are fine)."""
+    _need_cuda(x, shift, scale)
+    if x.dim() != 3 or x.dtype != BF16:
+        raise ValueError("x must be bf16 [B, R, D]")
+    B, R, D = x.shape
+    M, rx = rows_of(x)
+    if shift.stride(0) != scale.stride(0) or shift.stride(1) != 1 or scale.stride(1) != 1:
+        raise ValueError("shift/scale must be [B, D] views with a common batch stride")
+    q, sc = _mx_pair_out(out, M, D, x.device, "ln_modulate_mxfp8")
+    libfk.check(libfk.load().fk_ln_modulate_mxfp8(_ptr(x), rx, _ptr(q), q.stride(0), _ptr(sc), sc.stride(0), _ptr(shift), _ptr(scale),
+                                                   shift.stride(0), R, M, D, eps, _stream()), "fk_ln_modulate_mxfp8")
+    return q, sc
+
+
+def ln_modulate2_mxfp8(x, shift, scale, shift_b, scale_b, split, out=None, out_b=None, eps=1e-6):
+    """:func:`ln_modulate2` with its result stored as MXFP8, each stream in its own dense pair: returns (first, second) where
+    ``first`` = quantize_mxfp8(n[:, :split]) ([B * split, D] rows, batch-major) and ``second`` = quantize_mxfp8(n[:, split:]) for
+    n = ln_modulate2(...), bit for bit.  ``out`` / ``out_b``: such pairs with a common row stride."""
+    _need_cuda(x, shift, scale, shift_b, scale_b)
+    if x.dim() != 3 or x.dtype != BF16:
+        raise ValueError("x must be bf16 [B, R, D]")
+    B, R, D = x.shape
+    M, rx = rows_of(x)
+    strides = {t.stride(0) for t in (shift, scale, shift_b, scale_b)}
+    if len(strides) != 1 or any(t.stride(1) != 1 for t in (shift, scale, shift_b, scale_b)):
+        raise ValueError("shift/scale vectors must be [B, D] views with a common batch stride")
+    if not 0 <= split <= R:
+        raise ValueError(f"split {split} outside [0, {R}]")
+    qa, sa = _mx_pair_out(out, B * split, D, x.device, "ln_modulate2_mxfp8")
+    qb, sb = _mx_pair_out(out_b, B * (R - split), D, x.device, "ln_modulate2_mxfp8")
+    ldq = {t.stride(0) for t in (qa, qb) if t.shape[0] > 1} or {D}
+    lds = {t.stride(0) for t in (sa, sb) if t.shape[0] > 1} or {D // MXFP8_BLOCK}
+    if len(ldq) != 1 or len(lds) != 1:
+        raise ValueError("ln_modulate2_mxfp8: both streams' outputs must share their row strides")
+    libfk.check(libfk.load().fk_ln_modulate2_mxfp8(_ptr(x), rx, _ptr(qa), _ptr(sa), _ptr(qb), _ptr(sb), ldq.pop(), lds.pop(),
+                                                    _ptr(shift), _ptr(scale), _ptr(shift_b), _ptr(scale_b), split, shift.stride(0), R,
+                                                    M, D, eps, _stream()), "fk_ln_modulate2_mxfp8")
+    return (qa, sa), (qb, sb)
+
+
 def _mx_args(a, w, bias, out, epilogue, res, gate, out_fp32, qkv, variant):
+    """fk_gemm_mxfp8_args of one problem; ``out`` False: no bf16 output (the quantized-output form fills its own fields)."""
     (aq, asc), (wq, wsc) = a, w
-    _need_cuda(aq, asc, wq, wsc, bias, out, res, gate)
+    _need_cuda(aq, asc, wq, wsc, bias, None if out is False else out, res, gate)
     for t in (aq, asc, wq, wsc):
         if t.dtype != torch.uint8 or t.dim() != 2 or t.stride(1) != 1:
             raise TypeError("gemm_mxfp8 operands are (uint8 e4m3 [rows, K], uint8 E8M0 [rows, K / 32]) pairs (quantize_mxfp8)")
@@ -327,15 +394,16 @@ def _mx_args(a, w, bias, out, epilogue, res, gate, out_fp32, qkv, variant):
     N = wq.shape[0]
     if wq.shape[1] != K or tuple(asc.shape) != (M, K // MXFP8_BLOCK) or tuple(wsc.shape) != (N, K // MXFP8_BLOCK):
         raise ValueError(f"gemm_mxfp8: a {tuple(aq.shape)} / {tuple(asc.shape)} vs w {tuple(wq.shape)} / {tuple(wsc.shape)}")
-    if out is None:
-        out = torch.empty((M, N), device=aq.device, dtype=torch.float32 if out_fp32 else BF16)
-    Mo, rc = rows_of(out)
-    if Mo != M or out.shape[-1] != N:
-        raise ValueError(f"output shape {tuple(out.shape)} does not match M={M}, N={N}")
     args = GemmMxfp8Args()
     g = args.g
+    if out is not False:
+        if out is None:
+            out = torch.empty((M, N), device=aq.device, dtype=torch.float32 if out_fp32 else BF16)
+        Mo, rc = rows_of(out)
+        if Mo != M or out.shape[-1] != N:
+            raise ValueError(f"output shape {tuple(out.shape)} does not match M={M}, N={N}")
+        g.C, g.c = out.data_ptr(), rc
     g.bias = bias.data_ptr() if bias is not None else None
-    g.C, g.c = out.data_ptr(), rc
     if res is not None:
         Mr, rr = rows_of(res)
         if Mr != M:
@@ -356,12 +424,44 @@ def _mx_args(a, w, bias, out, epilogue, res, gate, out_fp32, qkv, variant):
     return args, out
 
 
-def gemm_mxfp8(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=None, out_fp32=False, qkv=None, variant=0):
+def _mx_q_args(a, w, bias, epilogue, variant, out_mx):
+    """fk_gemm_mxfp8_q_args of one problem.  ``out_mx``: True = a fresh dense pair; (q, scales) = uint8 [M, N] / [M, N / 32]
+    views (row-strided is fine); (q, scales, col_offset) = WHOLE uint8 [M, ld] / [M, ld / 32] buffers of which columns
+    [col_offset, col_offset + N) (scales: / 32) are written.  Returns (args, (q, scales))."""
+    M, N = a[0].shape[0], w[0].shape[0]
+    col = 0
+    if out_mx is True or len(out_mx) == 2:
+        q, sc = _mx_pair_out(None if out_mx is True else out_mx, M, N, a[0].device, "gemm_mxfp8")
+    else:
+        q, sc, col = out_mx
+        _need_cuda(q, sc)
+        if (q.dtype != torch.uint8 or sc.dtype != torch.uint8 or q.dim() != 2 or sc.dim() != 2 or q.shape[0] != M
+                or sc.shape[0] != M or q.stride(1) != 1 or sc.stride(1) != 1):
+            raise ValueError(f"gemm_mxfp8: out_mx buffers must be uint8 [{M}, ld] / [{M}, ld / 32], rows contiguous")
+    qa = GemmMxfp8QArgs()
+    qa.a, _ = _mx_args(a, w, bias, False, epilogue, None, None, False, None, variant)
+    qa.Q, qa.ldq, qa.Q_scale, qa.ldq_scale, qa.col_offset = q.data_ptr(), q.stride(0), sc.data_ptr(), sc.stride(0), int(col)
+    return qa, (q, sc)
+
+
+def gemm_mxfp8(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=None, out_fp32=False, qkv=None, variant=0,
+               out_mx=None):
     """out = epilogue(deq(a) @ deq(w).T + bias) on the block-scaled MFMA, fp32 accumulation; the epilogues (FK_EPI_NONE,
     GELU_TANH, GATE_RES, QKV) round exactly like :func:`gemm`'s.  ``a`` / ``w``: the (q, scales) pairs of
     :func:`quantize_mxfp8` ([M, K] / [N, K]); out [M, N] or a [B, R, N] view (may alias res; with ``gate`` it must be 3-D).
     out_fp32: fp32(acc + bias) from the same main loop (parity build).  variant: 0 = launch plan, 128 / 256 = 256 x 128 /
-    256 x 256 tiles.  K % 128 == 0, N % 256 == 0."""
+    256 x 256 tiles.  K % 128 == 0, N % 256 == 0.
+
+    out_mx (FK_EPI_NONE / FK_EPI_GELU_TANH): the result leaves as MXFP8 instead of bf16 -- the (q, scales) pair that
+    ``quantize_mxfp8(gemm_mxfp8(...))`` gives, bit for bit, with no bf16 output stored.  True = a fresh pair, (q, scales) =
+    uint8 [M, N] / [M, N / 32] views, (q, scales, col_offset) = whole [M, ld] / [M, ld / 32] buffers and the first column of
+    the window to fill.  Returns the pair."""
+    if out_mx is not None:
+        if out is not None or res is not None or gate is not None or out_fp32 or qkv is not None:
+            raise ValueError("gemm_mxfp8: out_mx replaces out; it takes no res / gate / qkv / out_fp32")
+        qa, pair = _mx_q_args(a, w, bias, epilogue, variant, out_mx)
+        libfk.check(libfk.load().fk_gemm_mxfp8_q(ctypes.byref(qa), _stream()), "fk_gemm_mxfp8_q")
+        return pair
     args, out = _mx_args(a, w, bias, out, epilogue, res, gate, out_fp32, qkv, variant)
     libfk.check(libfk.load().fk_gemm_mxfp8(ctypes.byref(args), _stream()), "fk_gemm_mxfp8")
     return out
@@ -369,8 +469,19 @@ def gemm_mxfp8(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=N
 
 def gemm_mxfp8_grouped(problems, epilogue=FK_EPI_NONE, out_fp32=False, variant=0):
     """Up to 4 MXFP8 GEMMs sharing (N, K, epilogue) in ONE launch; ``problems``: dicts with the keyword arguments of
-    :func:`gemm_mxfp8` (a, w, bias, out, res, gate, qkv).  Returns the outputs."""
+    :func:`gemm_mxfp8` (a, w, bias, out, res, gate, qkv).  Returns the outputs.  With ``out_mx`` in every problem (see
+    :func:`gemm_mxfp8`) the launch is the quantized-output form and the (q, scales) pairs are returned."""
     n = len(problems)
+    if any(pr.get("out_mx") is not None for pr in problems):
+        if not all(pr.get("out_mx") is not None for pr in problems) or out_fp32:
+            raise ValueError("gemm_mxfp8_grouped: out_mx must be given for every problem of a launch (and no out_fp32)")
+        qarr = (GemmMxfp8QArgs * n)()
+        pairs = []
+        for i, pr in enumerate(problems):
+            qarr[i], pair = _mx_q_args(pr["a"], pr["w"], pr.get("bias"), epilogue, variant, pr["out_mx"])
+            pairs.append(pair)
+        libfk.check(libfk.load().fk_gemm_mxfp8_q_grouped(qarr, n, _stream()), "fk_gemm_mxfp8_q_grouped")
+        return pairs
     arr = (GemmMxfp8Args * n)()
     outs = []
     for i, pr in enumerate(problems):

@@ -43,6 +43,11 @@ MLP_FIRST = os.environ.get("FK_MLP_FIRST", "0") == "1"
 # 1 = one per block (fk_double_block_fwd / fk_single_block_fwd), 2 = ONE per forward (fk_mmdit_blocks_fwd; default).  The C
 # entry points issue the same launches with the same arguments: identical bits (tests/test_hip_mmdit.py).
 BLOCK_API = int(os.environ.get("FK_BLOCK_API", "2"))
+# MXFP8 weight format only: 1 = the fused schedule -- LN + modulate and the GELU GEMMs emit the quantized operand of their
+# consumer themselves, only the attention output goes through the standalone quantizer; 0 (default) = every block GEMM as
+# quantize -> gemm (the schedule MXFP8 shipped with).  Same bits either way (tests/test_hip_mxfp8_fused.py).  The default
+# moves to 1 once tools/mxfp8_fused_ab.py shows the fused arm's worst round ahead of the parent's best at cfg 2.
+MX_FUSED_QUANT = os.environ.get("FK_MX_FUSED_QUANT", "0") == "1"
 OVERLAP_MLP = {"0": False, "1": True, "auto": "auto"}.get(os.environ.get("FK_OVERLAP_MLP", "0"), False)
 
 
@@ -452,13 +457,18 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         block_api = BLOCK_API if (FUSE_QKV and not MLP_FIRST and not (OVERLAP_MLP and (OVERLAP_MLP != "auto" or self._overlap_pays(B, ws.S)))
                                   and S_txt > 0) else 0
         if pk.format == "mxfp8":
-            if ws.mxq is None:   # quantized activations of one launch: at most B * S rows of K = 5D
-                ws.mxq = torch.empty(B * ws.S * 5 * D, device=s.device, dtype=torch.uint8)
-                ws.mxs = torch.empty(B * ws.S * 5 * D // 32, device=s.device, dtype=torch.uint8)
+            if ws.mxq is None:
+                # quantized activations: one launch's operand, at most B * S rows of K = 5D -- and in front of it, in the fused
+                # schedule, the LN output n8 (D per row) that stays live while the block's consumer operand is filled
+                cols = 6 * D
+                ws.mxq = torch.empty(B * ws.S * cols, device=s.device, dtype=torch.uint8)
+                ws.mxs = torch.empty(B * ws.S * cols // 32, device=s.device, dtype=torch.uint8)
             if S_txt == 0:
                 raise ValueError("the mxfp8 weight format needs a text stream (S_txt > 0)")
             if BLOCK_API:
                 self._blocks_by_c_entry(ws, pk, mod, cs, B, S_txt, S_img, BLOCK_API)
+            elif MX_FUSED_QUANT:
+                self._blocks_by_kernel_calls_mx_fused(ws, pk, mod, cs, B, S_txt)
             else:
                 self._blocks_by_kernel_calls_mx(ws, pk, mod, cs, S_txt)
         elif block_api:
@@ -612,6 +622,70 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
             mm([dict(a=n, w=w.mlp, bias=P(p + "proj_mlp.bias"), out=ws.cat[:, :, D:])], ops.FK_EPI_GELU_TANH)
             mm([dict(a=ws.cat, w=w.out, bias=P(p + "proj_out.bias"), out=s, res=s, gate=chunk(m0, 2))], ops.FK_EPI_GATE_RES)
 
+    def _blocks_by_kernel_calls_mx_fused(self, ws, pk, mod, cs, B, S_txt):
+        """The fused MXFP8 schedule (FK_MX_FUSED_QUANT=1) as one ctypes call per launch: the launches of fk_double_block_fwd_mx /
+        fk_single_block_fwd_mx with fk_mx_ws.fused set, in their order and on the same workspace layout -- n8 (img rows, then txt
+        rows) in front, the block's consumer operand (o8 / ff8 / cat8) behind it.  The bf16 n, ff and cat[:, D:] are not written."""
+        P, D = self.p, self.inner_dim
+        s = ws.s
+        S = ws.S
+        h, cx = s[:, S_txt:], s[:, :S_txt]
+        M, Mi, Mt = B * S, B * (S - S_txt), B * S_txt
+
+        def chunk(off, j):
+            return mod[:, off + j * D: off + (j + 1) * D]
+
+        def region(byte_off, rows, ld):      # a dense (q [rows, ld], scales [rows, ld / 32]) pair of the workspace
+            return (ws.mxq[byte_off: byte_off + rows * ld].view(rows, ld),
+                    ws.mxs[byte_off // 32: (byte_off + rows * ld) // 32].view(rows, ld // 32))
+
+        def streams(byte_off, ld):           # img rows first, then txt rows
+            return region(byte_off, Mi, ld), region(byte_off + Mi * ld, Mt, ld)
+
+        n8_img, n8_txt = streams(0, D)
+        o8_img, o8_txt = streams(M * D, D)
+        ff8_img, ff8_txt = streams(M * D, 4 * D)
+        for i, (blk, w) in enumerate(zip(pk.double, pk.mx_double)):
+            p = f"transformer_blocks.{i}."
+            mi, mt = blk.mod_img, blk.mod_txt
+            ops.ln_modulate2_mxfp8(s, chunk(mt, 0), chunk(mt, 1), chunk(mi, 0), chunk(mi, 1), S_txt, out=n8_txt, out_b=n8_img)
+            ops.gemm_mxfp8_grouped(
+                [dict(a=n8_img, w=w.qkv_img, bias=blk.bqkv_img, out=ws.qkv[:, S_txt:],
+                      qkv=dict(q_out=ws.q, k_out=ws.k, wq=P(p + "attn.norm_q.weight"), wk=P(p + "attn.norm_k.weight"), cs=cs,
+                               s_offset=S_txt)),
+                 dict(a=n8_txt, w=w.qkv_txt, bias=blk.bqkv_txt, out=ws.qkv[:, :S_txt],
+                      qkv=dict(q_out=ws.q, k_out=ws.k, wq=P(p + "attn.norm_added_q.weight"), wk=P(p + "attn.norm_added_k.weight"),
+                               cs=cs, s_offset=0))], epilogue=ops.FK_EPI_QKV)
+            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.o)
+            ops.quantize_mxfp8(ws.o[:, S_txt:], *o8_img)
+            ops.quantize_mxfp8(ws.o[:, :S_txt], *o8_txt)
+            ops.gemm_mxfp8_grouped(
+                [dict(a=o8_img, w=w.out, bias=P(p + "attn.to_out.0.bias"), out=h, res=h, gate=chunk(mi, 2)),
+                 dict(a=o8_txt, w=w.add_out, bias=P(p + "attn.to_add_out.bias"), out=cx, res=cx, gate=chunk(mt, 2))],
+                epilogue=ops.FK_EPI_GATE_RES)
+            ops.ln_modulate2_mxfp8(s, chunk(mt, 3), chunk(mt, 4), chunk(mi, 3), chunk(mi, 4), S_txt, out=n8_txt, out_b=n8_img)
+            ops.gemm_mxfp8_grouped(
+                [dict(a=n8_img, w=w.ff1, bias=P(p + "ff.net.0.proj.bias"), out_mx=ff8_img),
+                 dict(a=n8_txt, w=w.ff1_ctx, bias=P(p + "ff_context.net.0.proj.bias"), out_mx=ff8_txt)], epilogue=ops.FK_EPI_GELU_TANH)
+            ops.gemm_mxfp8_grouped(
+                [dict(a=ff8_img, w=w.ff2, bias=P(p + "ff.net.2.bias"), out=h, res=h, gate=chunk(mi, 5)),
+                 dict(a=ff8_txt, w=w.ff2_ctx, bias=P(p + "ff_context.net.2.bias"), out=cx, res=cx, gate=chunk(mt, 5))],
+                epilogue=ops.FK_EPI_GATE_RES)
+        n8 = region(0, M, D)
+        cat8 = region(M * D, M, 5 * D)
+        cat8_attn = (cat8[0][:, :D], cat8[1][:, :D // 32])
+        for i, (blk, w) in enumerate(zip(pk.single, pk.mx_single)):
+            p = f"single_transformer_blocks.{i}."
+            m0 = blk.mod
+            ops.ln_modulate_mxfp8(s, chunk(m0, 0), chunk(m0, 1), out=n8)
+            ops.gemm_mxfp8(n8, w.qkv, bias=blk.bqkv, out=ws.qkv, epilogue=ops.FK_EPI_QKV,
+                           qkv=dict(q_out=ws.q, k_out=ws.k, wq=P(p + "attn.norm_q.weight"), wk=P(p + "attn.norm_k.weight"), cs=cs,
+                                    s_offset=0))
+            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.cat[:, :, :D])
+            ops.quantize_mxfp8(ws.cat[:, :, :D], *cat8_attn)
+            ops.gemm_mxfp8(n8, w.mlp, bias=P(p + "proj_mlp.bias"), epilogue=ops.FK_EPI_GELU_TANH, out_mx=(cat8[0], cat8[1], D))
+            ops.gemm_mxfp8(cat8, w.out, bias=P(p + "proj_out.bias"), out=s, res=s, gate=chunk(m0, 2), epilogue=ops.FK_EPI_GATE_RES)
+
     def _block_mx_structs(self, pk):
         """fk_double_block_weights_mx / fk_single_block_weights_mx of every block, built once per set of quantized weights."""
         from . import libfk
@@ -666,6 +740,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
     def _blocks_by_c_entry(self, ws, pk, mod, cs, B, S_txt, S_img, api):
         """The same launches through the block-level C entry points: argument structs built once per (weights, workspace)
         and re-used; per forward only the modulation pointer changes."""
+        import ctypes
         from . import libfk
         lib = libfk.load()
         st = self._block_weight_structs(pk)
@@ -673,7 +748,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         aw = ops.attention_workspace(ws.s.device)
         key = tuple(getattr(ws, f).data_ptr() for f in ("s", "n", "qkv", "q", "k", "o", "ff", "cat")) + (
             cs.data_ptr(), sk.data_ptr(), aw.data_ptr(), B, S_txt, S_img, pk.format,
-            ws.mxq.data_ptr() if pk.format == "mxfp8" else 0)
+            ws.mxq.data_ptr() if pk.format == "mxfp8" else 0, MX_FUSED_QUANT)
         bw = self.__dict__.get("_block_ws")
         if bw is None or bw[0] != key:
             c = libfk.BlockWs()
@@ -683,13 +758,13 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
             c.B, c.S_txt, c.S_img, c.H, c.eps = B, S_txt, S_img, self.num_heads, 1e-6
             mxw = None
             if pk.format == "mxfp8":
-                mxw = libfk.MxWs(ws.mxq.data_ptr(), ws.mxs.data_ptr(), ws.mxq.numel(), ws.mxs.numel())
+                mxw = libfk.MxWs(ws.mxq.data_ptr(), ws.mxs.data_ptr(), ws.mxq.numel(), ws.mxs.numel(), int(MX_FUSED_QUANT),
+                                 ctypes.pointer(ops._QUANTIZE_SLOT))   # OUT: ops.quantize_launch_count() reads it
             bw = (key, c, (cs, sk, aw, ws.mxq, ws.mxs), mxw)   # strong references keep the buffers the structs point into alive
             self.__dict__["_block_ws"] = bw
         c = bw[1]
         L = ops.LAUNCH       # the host's launch defaults travel with the call (the library keeps no launch state)
         c.gemm_variant, c.gemm_plan, c.gemm_group_m, c.gemm_mfma, c.attn_grid = L.gemm_variant, ops.launch_plan(), L.gemm_group_m, L.gemm_mfma, L.attn_grid
-        import ctypes
         c.gemm_variant_used = ctypes.pointer(ops._variant_slot())
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         mp, mbs = ctypes.c_void_p(mod.data_ptr()), mod.stride(0)

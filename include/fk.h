@@ -180,6 +180,22 @@ int fk_gemm_mxfp8(const fk_gemm_mxfp8_args* args, fk_stream_t stream);
 /* n (<= FK_MAX_GROUP) problems with identical N, K and epilogue in one launch (the img + txt pairs of a double block). */
 int fk_gemm_mxfp8_grouped(const fk_gemm_mxfp8_args* args, int32_t n, fk_stream_t stream);
 
+/* The same GEMM as a PRODUCER of quantized activations: the result, rounded to bf16 where fk_gemm_mxfp8 rounds it, leaves as
+ * MXFP8 -- exactly the bytes fk_quantize_mxfp8 gives for fk_gemm_mxfp8's bf16 output, without that output ever being stored
+ * (a.g.C / a.g.c are unused).  Epilogues FK_EPI_NONE and FK_EPI_GELU_TANH.  Row m, column n goes to byte
+ * Q + m * ldq + col_offset + n and its block's scale to Q_scale + m * ldq_scale + (col_offset + n) / 32: a GEMM can fill a column
+ * window of a wider operand (the single block's MLP-up writes columns [D, 5D) of the [M, 5D] operand of proj_out).
+ * Q 16-byte aligned, ldq % 16 == 0; Q_scale 4-byte aligned, ldq_scale % 4 == 0; col_offset % 32 == 0; ldq >= col_offset + N,
+ * ldq_scale >= (col_offset + N) / 32.  Launch plan, tile widths (a.g.variant / variant_used) and grouping as fk_gemm_mxfp8. */
+typedef struct fk_gemm_mxfp8_q_args {
+  fk_gemm_mxfp8_args a;
+  void* Q; int64_t ldq;                    /* e4m3 [M, ldq] */
+  void* Q_scale; int64_t ldq_scale;        /* E8M0 [M, ldq_scale] */
+  int64_t col_offset;
+} fk_gemm_mxfp8_q_args;
+int fk_gemm_mxfp8_q(const fk_gemm_mxfp8_q_args* args, fk_stream_t stream);
+int fk_gemm_mxfp8_q_grouped(const fk_gemm_mxfp8_q_args* args, int32_t n, fk_stream_t stream);
+
 /* out = LN(x; eps, no affine) * (1 + scale[b]) + shift[b], rows of width D (=3072), bf16 in/out.
  * Rounds like the reference graph: LN -> bf16, (1+scale) -> bf16, product -> bf16, sum -> bf16.
  * Replaces AdaLayerNormZero / AdaLayerNormZeroSingle / AdaLayerNormContinuous / norm2 (+modulate)
@@ -196,6 +212,21 @@ int fk_ln_modulate2_bf16(const void* x, fk_rows xr, void* out, fk_rows outr, con
                          const void* scale, const void* shift_b, const void* scale_b, int64_t split,
                          int64_t mod_batch_stride, int64_t mod_rows_per_batch, int64_t M, int32_t D, float eps,
                          fk_stream_t stream);
+
+/* fk_ln_modulate_bf16 / fk_ln_modulate2_bf16 as PRODUCERS of quantized activations: the same statistics, modulation and bf16
+ * rounding points, and the bf16 values then stored as MXFP8 -- exactly the bytes fk_quantize_mxfp8 gives for the bf16 output,
+ * which is not written.  Outputs are dense, as fk_gemm_mxfp8 addresses an operand: row m of x at q + m * ldq and
+ * scales + m * ld_scale.  The joint form gives each stream its own buffers, batch-major: row r < split of batch b at row
+ * b * split + r of (q, scales), row r >= split at row b * (mod_rows_per_batch - split) + r - split of (q_b, scales_b).
+ * D % 32 == 0 (512, 1024, 3072); q / q_b 16-byte aligned, ldq >= D, ldq % 16 == 0; scales 4-byte aligned, ld_scale >= D / 32,
+ * ld_scale % 4 == 0. */
+int fk_ln_modulate_mxfp8(const void* x, fk_rows xr, void* q, int64_t ldq, void* scales, int64_t ld_scale, const void* shift,
+                         const void* scale, int64_t mod_batch_stride, int64_t mod_rows_per_batch, int64_t M, int32_t D,
+                         float eps, fk_stream_t stream);
+int fk_ln_modulate2_mxfp8(const void* x, fk_rows xr, void* q, void* scales, void* q_b, void* scales_b, int64_t ldq,
+                          int64_t ld_scale, const void* shift, const void* scale, const void* shift_b, const void* scale_b,
+                          int64_t split, int64_t mod_batch_stride, int64_t mod_rows_per_batch, int64_t M, int32_t D, float eps,
+                          fk_stream_t stream);
 
 /* QKV post-processing of FluxAttnProcessor2_0: per-head RMSNorm(eps, weight) on q and k
  * (text rows s < s_txt use the *_added weights), interleaved-pair RoPE in fp32, and re-layout:
@@ -303,11 +334,22 @@ typedef struct fk_double_block_weights_mx {
 typedef struct fk_single_block_weights_mx {
   fk_mx_pair qkv, mlp, out;
 } fk_single_block_weights_mx;
-/* quantized activations of one launch: q >= B * S * 5D bytes (16-byte aligned), s >= B * S * 5D / 32 bytes (4-byte aligned) */
+/* quantized activations of one launch: q >= B * S * 5D bytes (16-byte aligned), s >= B * S * 5D / 32 bytes (4-byte aligned).
+ * fused != 0 selects the fused schedule: the producers emit MXFP8 themselves (fk_ln_modulate(2)_mxfp8, fk_gemm_mxfp8_q) and
+ * only the attention output goes through fk_quantize_mxfp8 --
+ *   double block: LN -> n8, QKV GEMM, attention, quantize o -> o8, out GEMMs, LN -> n8, ff1 GEMMs (GELU) -> ff8, ff2 GEMMs;
+ *   single block: LN -> n8 (once), QKV GEMM, attention -> cat[:, :D], quantize -> cat8[:, :D], MLP GEMM (GELU) -> cat8[:, D:],
+ *                 out GEMM on cat8;
+ * the bf16 n, ff and cat[:, D:] are not written.  Same bits as the unfused schedule (blocks of 32 never straddle a producer).
+ * The workspace then holds n8 (D bytes per row) AND the block's consumer operand at once: q >= B * S * 5D bytes for a double
+ * block (n8 | o8 or ff8), B * S * 6D for a single block (n8 | cat8), s 1/32 of that; too small: FK_EINVAL, nothing launched. */
 typedef struct fk_mx_ws {
   void* q;
   void* s;
   int64_t q_bytes, s_bytes;
+  int32_t fused;
+  int32_t* quantize_launches;   /* OUT, optional (NULL: not wanted): incremented by the host code of the call once per
+                                 * fk_quantize_mxfp8 launch it enqueues (tests: 2 per double, 1 per single block when fused) */
 } fk_mx_ws;
 int fk_double_block_fwd_mx(const fk_block_ws* ws, const fk_mx_ws* mx, const fk_double_block_weights* w,
                            const fk_double_block_weights_mx* wx, const void* mod, int64_t mod_batch_stride, fk_stream_t stream);
