@@ -29,6 +29,15 @@ struct AttnParams {
   unsigned* sk_ctl;    // ... and its (ticket, flag) word pair
 };
 
+// Quantized (MXFP8) destination of attention_fwd4.hip's mx kernels, row-split like fk_ln_modulate2_mxfp8's: rows [0, split) of
+// every batch are the dense rows b * split + s of stream A, rows [split, S) the dense rows b * (S - split) + s - split of
+// stream B; head h fills bytes [128 h, 128 h + 128) of its row and scale bytes [4 h, 4 h + 4).  split = S: stream A alone.
+struct AttnMxOut {
+  uint8_t *qa, *sa, *qb, *sb;
+  int64_t ldq, lds;    // bytes per row of e4m3 codes / of E8M0 scales, both streams
+  int split;
+};
+
 namespace {
 
 constexpr int HD = 128;
@@ -86,3 +95,4 @@ FK_DEV float merge2(float a, float wa, float b, float wb) {
 
 // attention_fwd4.hip: the 4-wave kernel's launcher (grid = work items or, stream-K, one workgroup per CU)
 int fk_attention_fwd4_launch(const AttnParams& p, int grid, bool streamk, hipStream_t stream);
+int fk_attention_fwd4_mx_launch(const AttnParams& p, const AttnMxOut& mx, int grid, bool streamk, hipStream_t stream);

@@ -665,12 +665,13 @@ static bool use_interleaved(const AttnParams& p) {
 
 int attention_entry(const void* q, const void* k, const void* v, void* o, int32_t B, int32_t H, int32_t S, int64_t v_ld,
                     int64_t v_batch_stride, int64_t o_ld, int64_t o_batch_stride, float scale, bool f32out,
-                    hipStream_t stream, float* lse = nullptr, void* ws = nullptr, int64_t ws_bytes = 0, int grid = 0) {
+                    hipStream_t stream, float* lse = nullptr, void* ws = nullptr, int64_t ws_bytes = 0, int grid = 0,
+                    const AttnMxOut* mx = nullptr) {   // mx: the MXFP8-output form (4-wave kernel only); o / o_ld / o_batch_stride unused
   FK_CHECK_ARG(grid >= -1 && grid != 1, "fk_attention_fwd_ws_bf16: grid %d is not 0 (stream-K grid where the plain one wastes a round), "
                "-1 (always one workgroup per 256-row block) or a workgroup count >= 2 (test hook)", grid);
-  FK_CHECK_ARG(q && k && v && o, "fk_attention_fwd_bf16: null pointer");
+  FK_CHECK_ARG(q && k && v && (o || mx), "fk_attention_fwd_bf16: null pointer");
   FK_CHECK_ARG(B > 0 && H > 0 && S > 0, "fk_attention_fwd_bf16: bad B/H/S %d %d %d", B, H, S);
-  FK_CHECK_ARG(o_ld % 4 == 0 && o_batch_stride % 4 == 0 && ((uintptr_t)o % (f32out ? 16 : 8) == 0),
+  FK_CHECK_ARG(mx || (o_ld % 4 == 0 && o_batch_stride % 4 == 0 && ((uintptr_t)o % (f32out ? 16 : 8) == 0)),
                "fk_attention_fwd_bf16: output must be 8-byte aligned (o_ld %% 4 == 0)");
   FK_CHECK_ARG(v_ld % 8 == 0 && v_batch_stride % 8 == 0, "fk_attention_fwd_bf16: V strides must be multiples of 8");
   FK_CHECK_ARG(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0),
@@ -710,9 +711,11 @@ int attention_entry(const void* q, const void* k, const void* v, void* o, int32_
     // read its tickets from what a 256-workgroup launch used as partial storage), partials behind them
     p.sk_ctl = (unsigned*)ws;
     p.sk_partials = (float*)((char*)ws + ATTN_CTL_BYTES);
+    if (mx) return fk_attention_fwd4_mx_launch(p, *mx, G, true, stream);
     if (attn_kernel_choice() == 4) return fk_attention_fwd4_launch(p, G, true, stream);
     return use_interleaved(p) ? launch<8, false, true, true>(p, G, stream) : launch<8, false, false, true>(p, G, stream);
   }
+  if (mx) return fk_attention_fwd4_mx_launch(p, *mx, (int)n_items, false, stream);
   if (attn_kernel_choice() == 4) return fk_attention_fwd4_launch(p, (int)n_items, false, stream);
   return use_interleaved(p) ? launch<8, false, true, false>(p, (int)n_items, stream)
                             : launch<8, false, false, false>(p, (int)n_items, stream);
@@ -743,6 +746,33 @@ extern "C" int fk_attention_fwd_ws_bf16(const void* q, const void* k, const void
                                         float scale, void* ws, int64_t ws_bytes, int32_t grid, fk_stream_t stream_) {
   return attention_entry(q, k, v, o, B, H, S, v_ld, v_batch_stride, o_ld, o_batch_stride, scale, false,
                          (hipStream_t)stream_, lse, ws, ws_bytes, grid);
+}
+
+extern "C" int fk_attention_fwd_ws_mxfp8(const void* q, const void* k, const void* v, float* lse, int32_t B, int32_t H, int32_t S,
+                                         int64_t v_ld, int64_t v_batch_stride, float scale, const fk_attn_mx_out* out, void* ws,
+                                         int64_t ws_bytes, int32_t grid, fk_stream_t stream_) {
+  // everything about the destination is settled here, before attention_entry (which validates the rest) can launch
+  FK_CHECK_ARG(out != nullptr, "fk_attention_fwd_ws_mxfp8: null destination");
+  FK_CHECK_ARG(H > 0 && S > 0 && out->split >= 0 && out->split <= S, "fk_attention_fwd_ws_mxfp8: bad H / S / split %d %d %lld", H, S,
+               (long long)out->split);
+  const int split = out->split == 0 ? S : (int)out->split;      // 0: one stream, like split = S
+  FK_CHECK_ARG(out->q && out->scales && (split == S || (out->q_b && out->scales_b)),
+               "fk_attention_fwd_ws_mxfp8: null output pointer (rows [%d, %d) need the second stream)", split, S);
+  const uintptr_t qbits = (uintptr_t)out->q | (split < S ? (uintptr_t)out->q_b : 0);
+  const uintptr_t sbits = (uintptr_t)out->scales | (split < S ? (uintptr_t)out->scales_b : 0);
+  FK_CHECK_ARG(out->ldq >= (int64_t)H * 128 && out->ldq % 16 == 0 && qbits % 16 == 0,
+               "fk_attention_fwd_ws_mxfp8: output byte rows must be 16-byte aligned with ldq >= H * 128 (ldq %lld)", (long long)out->ldq);
+  FK_CHECK_ARG(out->ldq_scale >= (int64_t)H * 4 && out->ldq_scale % 4 == 0 && sbits % 4 == 0,
+               "fk_attention_fwd_ws_mxfp8: scale rows must be 4-byte aligned with ldq_scale >= H * 4 (ldq_scale %lld)",
+               (long long)out->ldq_scale);
+  if (attn_kernel_choice() != 4) {
+    fk_set_error("fk_attention_fwd_ws_mxfp8: only the 4-wave kernel has the MXFP8-output form (FK_ATTN_KERNEL=8 is set)");
+    return FK_EUNSUPPORTED;
+  }
+  const AttnMxOut mx = {(uint8_t*)out->q, (uint8_t*)out->scales, (uint8_t*)out->q_b, (uint8_t*)out->scales_b, out->ldq, out->ldq_scale,
+                        split};
+  return attention_entry(q, k, v, nullptr, B, H, S, v_ld, v_batch_stride, 0, 0, scale, false, (hipStream_t)stream_, lse, ws, ws_bytes,
+                         grid, &mx);
 }
 
 extern "C" int fk_attention_fwd_f32_debug(const void* q, const void* k, const void* v, float* o, int32_t B,

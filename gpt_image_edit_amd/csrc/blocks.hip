@@ -163,6 +163,15 @@ int quantize_view(const fk_mx_ws& m, const View& x, int64_t M, int K, const Q8& 
   if (m.quantize_launches) ++*m.quantize_launches;
   return FK_OK;
 }
+// fk_mx_ws.fused bit 1: the attention writes the quantized rows itself (stream A = rows [0, split) -> a, stream B = the rest -> b;
+// split = 0: everything to a).  FK_EUNSUPPORTED (no MXFP8 form of the selected attention kernel) comes back to the caller, which
+// then takes the bf16 attention + quantizer route; nothing has been launched at that point.
+int attention_mx(const fk_block_ws& ws, const Dims& d, const Q8& a, const Q8* b, int split, fk_stream_t st) {
+  const int D = d.D;
+  const fk_attn_mx_out out = {a.q, a.s, b ? b->q : nullptr, b ? b->s : nullptr, split, a.ld, a.lds};
+  return fk_attention_fwd_ws_mxfp8(ws.q, ws.k, (const char*)ws.qkv + (int64_t)2 * D * 2, nullptr, d.B, d.H, d.S, 3 * D,
+                                   (int64_t)d.S * 3 * D, 0.08838834764831845f, &out, ws.attn_ws, ws.attn_ws_bytes, ws.attn_grid, st);
+}
 // the workspace holds n8 (D bytes per row) and the block's consumer operand (operand_cols bytes per row) at once
 int check_fused_ws(const fk_mx_ws& m, const Dims& d, int operand_cols, const char* who) {
   const int64_t need = (int64_t)d.B * d.S * (d.D + (int64_t)operand_cols);
@@ -197,12 +206,17 @@ int double_block_fused(const fk_block_ws& ws, const Dims& d, const fk_double_blo
     qkv_epi(g[1], ws, d, w.norm_added_q, w.norm_added_k, 0);
     ctl(g[0], ws); FK_TRY(mx_gemm(mxws, g, 2, n8s, &wx.qkv_img, nullptr, 0, st));
   }
-  FK_TRY(fk_attention_fwd_ws_bf16(ws.q, ws.k, (const char*)ws.qkv + (int64_t)2 * D * 2, ws.o, nullptr, B, d.H, d.S, 3 * D,
-                                  (int64_t)d.S * 3 * D, D, (int64_t)d.S * D, 0.08838834764831845f, ws.attn_ws, ws.attn_ws_bytes, ws.attn_grid, st));
-  {
+  // o8: txt rows (stream A, split = S_txt) behind the img rows (stream B), from the attention itself or through the quantizer
+  const int rc_mx = (mxws.fused & 2) ? attention_mx(ws, d, o8s[1], &o8s[0], d.S_txt, st) : FK_EUNSUPPORTED;
+  if (rc_mx != FK_EUNSUPPORTED) FK_TRY(rc_mx);
+  else {
+    FK_TRY(fk_attention_fwd_ws_bf16(ws.q, ws.k, (const char*)ws.qkv + (int64_t)2 * D * 2, ws.o, nullptr, B, d.H, d.S, 3 * D,
+                                    (int64_t)d.S * 3 * D, D, (int64_t)d.S * D, 0.08838834764831845f, ws.attn_ws, ws.attn_ws_bytes, ws.attn_grid, st));
     const View oi = view(ws.o, d, D, d.S_txt, d.S_img, 0), ot = view(ws.o, d, D, 0, d.S_txt, 0);
     FK_TRY(quantize_view(mxws, oi, Mi, D, o8s[0], st));
     FK_TRY(quantize_view(mxws, ot, Mt, D, o8s[1], st));
+  }
+  {
     fk_gemm_args g[2];
     g[0] = gemm(none, nullptr, w.b_out, h, Mi, D, D, FK_EPI_GATE_RES);
     gate_res(g[0], h, chunk(mi, 2), mod_bs, d.S_img);
@@ -248,13 +262,18 @@ int single_block_fused(const fk_block_ws& ws, const Dims& d, const fk_single_blo
     qkv_epi(g, ws, d, w.norm_q, w.norm_k, 0);
     ctl(g, ws); FK_TRY(mx_gemm(mxws, &g, 1, &n8, &wx.qkv, nullptr, 0, st));
   }
-  FK_TRY(fk_attention_fwd_ws_bf16(ws.q, ws.k, (const char*)ws.qkv + (int64_t)2 * D * 2, ws.cat, nullptr, B, d.H, d.S, 3 * D,
-                                  (int64_t)d.S * 3 * D, 5 * D, (int64_t)d.S * 5 * D, 0.08838834764831845f, ws.attn_ws,
-                                  ws.attn_ws_bytes, ws.attn_grid, st));
-  {
-    // columns [0, D) of cat8 from the attention output, columns [D, 5D) straight from the MLP-up GEMM's epilogue
+  // columns [0, D) of cat8 from the attention output (directly, or bf16 cat[:, :D] through the quantizer), columns [D, 5D)
+  // straight from the MLP-up GEMM's epilogue
+  const int rc_mx = (mxws.fused & 2) ? attention_mx(ws, d, cat8, nullptr, 0, st) : FK_EUNSUPPORTED;
+  if (rc_mx != FK_EUNSUPPORTED) FK_TRY(rc_mx);
+  else {
+    FK_TRY(fk_attention_fwd_ws_bf16(ws.q, ws.k, (const char*)ws.qkv + (int64_t)2 * D * 2, ws.cat, nullptr, B, d.H, d.S, 3 * D,
+                                    (int64_t)d.S * 3 * D, 5 * D, (int64_t)d.S * 5 * D, 0.08838834764831845f, ws.attn_ws,
+                                    ws.attn_ws_bytes, ws.attn_grid, st));
     const View att = view(ws.cat, d, 5 * D, 0, d.S, 0);
     FK_TRY(quantize_view(mxws, att, Ms, D, cat8, st));
+  }
+  {
     fk_gemm_args g = gemm(none, nullptr, w.b_mlp, none, Ms, 4 * D, D, FK_EPI_GELU_TANH);
     ctl(g, ws); FK_TRY(mx_gemm(mxws, &g, 1, &n8, &wx.mlp, &cat8, D, st));
   }
@@ -394,6 +413,9 @@ namespace {
 int check_mx(const fk_mx_ws* mx, const char* who) {
   FK_CHECK_ARG(mx && mx->q && mx->s && (uintptr_t)mx->q % 16 == 0 && (uintptr_t)mx->s % 4 == 0,
                "%s: null or misaligned quantized-activation workspace", who);
+  FK_CHECK_ARG((mx->fused & 3) != 2,
+               "%s: fk_mx_ws.fused = %d: bit 1 (the attention emits MXFP8) is valid only together with bit 0 (the fused schedule)", who,
+               (int)mx->fused);
   return FK_OK;
 }
 }  // namespace

@@ -122,6 +122,8 @@ def build_parser():
                    help="block GEMM weights: bf16, or opt-in OCP MXFP8 (inference only)")
     p.add_argument("--mx_splitk", action="store_true",
                    help="mxfp8 only: let the long-K block GEMMs run as split-K pairs (FK_MX_SPLITK=1; default off)")
+    p.add_argument("--mx_fused_attn", action="store_true",
+                   help="mxfp8 with FK_MX_FUSED_QUANT=1 only: the attention emits MXFP8 itself (FK_MX_FUSED_ATTN=1; default off)")
     return p
 
 
@@ -162,6 +164,8 @@ def main(args):
     from ..serve import cli
     if getattr(args, "mx_splitk", False):
         cli.transformer.set_mx_splitk(True)
+    if getattr(args, "mx_fused_attn", False):
+        cli.transformer.set_mx_fused_attn(True)
     pipe, tokenizers, text_encoders = cli.load_pipe(args.model_path, args.flux_path, device,
                                                     weight_format=getattr(args, "weight_format", "bf16"))
     if args.t5_only:

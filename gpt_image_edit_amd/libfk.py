@@ -126,6 +126,10 @@ class SingleBlockWeightsMx(ctypes.Structure):   # fk_single_block_weights_mx
     _fields_ = [(n, MxPair) for n in SINGLE_BLOCK_MX_FIELDS]
 
 
+class AttnMxOut(ctypes.Structure):            # fk_attn_mx_out
+    _fields_ = [("q", c_vp), ("scales", c_vp), ("q_b", c_vp), ("scales_b", c_vp), ("split", c_i64), ("ldq", c_i64), ("ldq_scale", c_i64)]
+
+
 class MxWs(ctypes.Structure):                 # fk_mx_ws
     _fields_ = [("q", c_vp), ("s", c_vp), ("q_bytes", c_i64), ("s_bytes", c_i64), ("fused", c_i32),
                 ("quantize_launches", ctypes.POINTER(c_i32)), ("splitk", c_i32)]
@@ -148,6 +152,7 @@ SIGNATURES = {
     "fk_qkv_post_bf16": (c_i32, [c_vp] * 9 + [c_i32] * 4 + [c_f32, c_vp]),
     "fk_attention_fwd_bf16": (c_i32, [c_vp] * 4 + [c_i32] * 3 + [c_i64] * 4 + [c_f32, c_vp]),
     "fk_attention_fwd_ws_bf16": (c_i32, [c_vp] * 5 + [c_i32] * 3 + [c_i64] * 4 + [c_f32, c_vp, c_i64, c_i32, c_vp]),
+    "fk_attention_fwd_ws_mxfp8": (c_i32, [c_vp] * 4 + [c_i32] * 3 + [c_i64] * 2 + [c_f32, ctypes.POINTER(AttnMxOut), c_vp, c_i64, c_i32, c_vp]),
     "fk_attention_ws_bytes": (c_i64, []),
     "fk_attention_fwd_f32_debug": (c_i32, [c_vp] * 4 + [c_i32] * 3 + [c_i64] * 4 + [c_f32, c_vp]),
     "fk_attention_fwd_lse_bf16": (c_i32, [c_vp] * 5 + [c_i32] * 3 + [c_i64] * 4 + [c_f32, c_vp]),

@@ -597,6 +597,35 @@ def attention(q, k, v, out, scale=None, lse=None):
     return out
 
 
+def attention_mxfp8(q, k, v, out, out_b=None, split=0, scale=None, lse=None):
+    """:func:`attention` with its result stored as MXFP8 (fk_attention_fwd_ws_mxfp8): the bytes :func:`quantize_mxfp8` gives for
+    the bf16 output, which is never written.  ``out`` = (codes uint8 [rows, >= H*128], scales uint8 [rows, >= H*4]) row-strided
+    views; head h fills columns [128 h, 128 h + 128) / [4 h, 4 h + 4) of a row.  Tokens [0, split) of batch b are the rows
+    b * split + s of ``out``, tokens [split, S) the rows b * (S - split) + s - split of ``out_b`` (same row strides);
+    ``split`` 0 or S: everything goes to ``out``.  Same grid choice (``LAUNCH.attn_grid``) and workspace as :func:`attention`."""
+    _need_cuda(q, k, v, lse, *out, *(out_b or ()))
+    B, H, S, hd = q.shape
+    if hd != 128:
+        raise ValueError("head_dim must be 128")
+    if v.dim() != 3 or v.shape[-1] != H * 128 or v.stride(2) != 1:
+        raise ValueError("v must be a [B, S, H*128] view with a contiguous last dimension")
+    if lse is not None and (lse.dtype != torch.float32 or lse.shape != (B, H, S) or not lse.is_contiguous()):
+        raise ValueError("lse must be a contiguous fp32 [B,H,S] tensor")
+    pairs = [out] + ([out_b] if out_b is not None else [])
+    for qt, st in pairs:
+        if qt.dtype != torch.uint8 or st.dtype != torch.uint8 or qt.dim() != 2 or st.dim() != 2 or qt.stride(1) != 1 or st.stride(1) != 1:
+            raise ValueError("attention_mxfp8: an output is a (uint8 [rows, cols], uint8 [rows, cols / 32]) pair, rows contiguous")
+    if len({pr[0].stride(0) for pr in pairs}) != 1 or len({pr[1].stride(0) for pr in pairs}) != 1:
+        raise ValueError("attention_mxfp8: both streams' outputs must share their row strides")
+    dst = libfk.AttnMxOut(_ptr(out[0]), _ptr(out[1]), _ptr(out_b[0]) if out_b is not None else None,
+                          _ptr(out_b[1]) if out_b is not None else None, int(split), out[0].stride(0), out[1].stride(0))
+    ws = attention_workspace(q.device)
+    libfk.check(libfk.load().fk_attention_fwd_ws_mxfp8(_ptr(q), _ptr(k), _ptr(v), _ptr(lse), B, H, S, v.stride(1), v.stride(0),
+                                                      hd ** -0.5 if scale is None else scale, ctypes.byref(dst), _ptr(ws),
+                                                      ws.numel(), LAUNCH.attn_grid, _stream()), "fk_attention_fwd_ws_mxfp8")
+    return out if out_b is None else (out, out_b)
+
+
 def attention_f32_debug(q, k, v, scale=None):
     """Parity build of :func:`attention` (fk_attention_fwd_f32_debug): fp32 [B, S, H*128] output, P as hi + lo bf16."""
     _need_cuda(q, k, v)

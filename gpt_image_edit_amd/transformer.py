@@ -62,6 +62,28 @@ def set_mx_splitk(on):
     global MX_SPLITK
     MX_SPLITK = bool(on)
     ops._set_launch()
+
+
+# MXFP8 weight format with MX_FUSED_QUANT only (no effect without it): 1 = the attention forward emits the quantized operand of its
+# consumer as well (fk_attention_fwd_ws_mxfp8 -> o8 / cat8[:, :D]), so a forward launches the standalone quantizer not at all and the
+# bf16 o / cat[:, :D] are not written; 0 (default) = attention to bf16, then the quantizer (2 launches per double block, 1 per
+# single block).  Same bits either way, on all three FK_BLOCK_API routes (tests/test_hip_mxfp8_attention.py).  What it buys is
+# not measured yet: the default moves on the evidence of the third arm of tools/mxfp8_fused_ab.py.
+MX_FUSED_ATTN = os.environ.get("FK_MX_FUSED_ATTN", "0") == "1"
+
+
+def set_mx_fused_attn(on):
+    """Switch MX_FUSED_ATTN at run time; a launch-control change like :func:`set_mx_splitk` (``ops.launch_config_epoch``)."""
+    global MX_FUSED_ATTN
+    MX_FUSED_ATTN = bool(on)
+    ops._set_launch()
+
+
+def _mx_fused_bits():
+    """fk_mx_ws.fused: bit 0 = the fused schedule, bit 1 (only with bit 0) = the attention emits MXFP8 too."""
+    return (1 | (2 if MX_FUSED_ATTN else 0)) if MX_FUSED_QUANT else 0
+
+
 OVERLAP_MLP = {"0": False, "1": True, "auto": "auto"}.get(os.environ.get("FK_OVERLAP_MLP", "0"), False)
 
 
@@ -640,7 +662,8 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
     def _blocks_by_kernel_calls_mx_fused(self, ws, pk, mod, cs, B, S_txt):
         """The fused MXFP8 schedule (FK_MX_FUSED_QUANT=1) as one ctypes call per launch: the launches of fk_double_block_fwd_mx /
         fk_single_block_fwd_mx with fk_mx_ws.fused set, in their order and on the same workspace layout -- n8 (img rows, then txt
-        rows) in front, the block's consumer operand (o8 / ff8 / cat8) behind it.  The bf16 n, ff and cat[:, D:] are not written."""
+        rows) in front, the block's consumer operand (o8 / ff8 / cat8) behind it.  The bf16 n, ff and cat[:, D:] are not written;
+        with MX_FUSED_ATTN the attention fills o8 / cat8[:, :D] itself (fk_mx_ws.fused bit 1) and o / cat[:, :D] are not written either."""
         P, D = self.p, self.inner_dim
         s = ws.s
         S = ws.S
@@ -671,9 +694,12 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
                  dict(a=n8_txt, w=w.qkv_txt, bias=blk.bqkv_txt, out=ws.qkv[:, :S_txt],
                       qkv=dict(q_out=ws.q, k_out=ws.k, wq=P(p + "attn.norm_added_q.weight"), wk=P(p + "attn.norm_added_k.weight"),
                                cs=cs, s_offset=0))], epilogue=ops.FK_EPI_QKV)
-            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.o)
-            ops.quantize_mxfp8(ws.o[:, S_txt:], *o8_img)
-            ops.quantize_mxfp8(ws.o[:, :S_txt], *o8_txt)
+            if MX_FUSED_ATTN:
+                ops.attention_mxfp8(ws.q, ws.k, ws.qkv[:, :, 2 * D:], o8_txt, out_b=o8_img, split=S_txt)
+            else:
+                ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.o)
+                ops.quantize_mxfp8(ws.o[:, S_txt:], *o8_img)
+                ops.quantize_mxfp8(ws.o[:, :S_txt], *o8_txt)
             ops.gemm_mxfp8_grouped(
                 [dict(a=o8_img, w=w.out, bias=P(p + "attn.to_out.0.bias"), out=h, res=h, gate=chunk(mi, 2)),
                  dict(a=o8_txt, w=w.add_out, bias=P(p + "attn.to_add_out.bias"), out=cx, res=cx, gate=chunk(mt, 2))],
@@ -696,8 +722,11 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
             ops.gemm_mxfp8(n8, w.qkv, bias=blk.bqkv, out=ws.qkv, epilogue=ops.FK_EPI_QKV,
                            qkv=dict(q_out=ws.q, k_out=ws.k, wq=P(p + "attn.norm_q.weight"), wk=P(p + "attn.norm_k.weight"), cs=cs,
                                     s_offset=0))
-            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.cat[:, :, :D])
-            ops.quantize_mxfp8(ws.cat[:, :, :D], *cat8_attn)
+            if MX_FUSED_ATTN:
+                ops.attention_mxfp8(ws.q, ws.k, ws.qkv[:, :, 2 * D:], cat8_attn)
+            else:
+                ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.cat[:, :, :D])
+                ops.quantize_mxfp8(ws.cat[:, :, :D], *cat8_attn)
             ops.gemm_mxfp8(n8, w.mlp, bias=P(p + "proj_mlp.bias"), epilogue=ops.FK_EPI_GELU_TANH, out_mx=(cat8[0], cat8[1], D))
             ops.gemm_mxfp8(cat8, w.out, bias=P(p + "proj_out.bias"), out=s, res=s, gate=chunk(m0, 2), epilogue=ops.FK_EPI_GATE_RES,
                            splitk=MX_SPLITK)
@@ -764,7 +793,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         aw = ops.attention_workspace(ws.s.device)
         key = tuple(getattr(ws, f).data_ptr() for f in ("s", "n", "qkv", "q", "k", "o", "ff", "cat")) + (
             cs.data_ptr(), sk.data_ptr(), aw.data_ptr(), B, S_txt, S_img, pk.format,
-            ws.mxq.data_ptr() if pk.format == "mxfp8" else 0, MX_FUSED_QUANT, MX_SPLITK)
+            ws.mxq.data_ptr() if pk.format == "mxfp8" else 0, _mx_fused_bits(), MX_SPLITK)
         bw = self.__dict__.get("_block_ws")
         if bw is None or bw[0] != key:
             c = libfk.BlockWs()
@@ -774,7 +803,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
             c.B, c.S_txt, c.S_img, c.H, c.eps = B, S_txt, S_img, self.num_heads, 1e-6
             mxw = None
             if pk.format == "mxfp8":
-                mxw = libfk.MxWs(ws.mxq.data_ptr(), ws.mxs.data_ptr(), ws.mxq.numel(), ws.mxs.numel(), int(MX_FUSED_QUANT),
+                mxw = libfk.MxWs(ws.mxq.data_ptr(), ws.mxs.data_ptr(), ws.mxq.numel(), ws.mxs.numel(), _mx_fused_bits(),
                                  ctypes.pointer(ops._QUANTIZE_SLOT),   # OUT: ops.quantize_launch_count() reads it
                                  int(MX_SPLITK))
             bw = (key, c, (cs, sk, aw, ws.mxq, ws.mxs), mxw)   # strong references keep the buffers the structs point into alive

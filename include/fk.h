@@ -273,6 +273,25 @@ int fk_attention_fwd_ws_bf16(const void* q, const void* k, const void* v, void* 
                              float scale, void* ws, int64_t ws_bytes, int32_t grid, fk_stream_t stream);
 int64_t fk_attention_ws_bytes(void);
 
+/* fk_attention_fwd_ws_bf16 as a PRODUCER of quantized activations: the same kernel, grid choice (`grid`, ws, ws_bytes: exactly as
+ * above) and lse, the output rounded to bf16 as above and then stored as MXFP8 -- exactly the bytes fk_quantize_mxfp8 gives for
+ * the bf16 output, which is not written.  The destination is row-split like fk_ln_modulate2_mxfp8's: token s < split of batch b is
+ * the dense row b * split + s of (q, scales), token s >= split the dense row b * (S - split) + s - split of (q_b, scales_b); head h
+ * fills bytes [128 h, 128 h + 128) of its row (row stride ldq) and scale bytes [4 h, 4 h + 4) (row stride ldq_scale), so a
+ * row may be a window of a wider operand (the single block's [M, 5D] operand of proj_out: ldq = 5D).  split = 0 or S: one stream,
+ * (q, scales) alone -- q_b / scales_b may be NULL.  0 <= split <= S; q / q_b 16-byte aligned, ldq % 16 == 0, ldq >= H * 128;
+ * scales / scales_b 4-byte aligned, ldq_scale % 4 == 0, ldq_scale >= H * 4: a violation is FK_EINVAL before anything is launched.
+ * Only the 4-wave kernel has this form: with FK_ATTN_KERNEL=8 in the environment the call returns FK_EUNSUPPORTED. */
+typedef struct fk_attn_mx_out {
+  void* q; void* scales;           /* stream A: tokens [0, split) */
+  void* q_b; void* scales_b;       /* stream B: tokens [split, S) */
+  int64_t split;
+  int64_t ldq, ldq_scale;          /* bytes per row, both streams */
+} fk_attn_mx_out;
+int fk_attention_fwd_ws_mxfp8(const void* q, const void* k, const void* v, float* lse, int32_t B, int32_t H, int32_t S,
+                              int64_t v_ld, int64_t v_batch_stride, float scale, const fk_attn_mx_out* out, void* ws,
+                              int64_t ws_bytes, int32_t grid, fk_stream_t stream);
+
 /* Parity / debug build of the SAME kernel (same tiling, LDS layouts, softmax, key <-> MFMA k-slot binding): the output
  * is fp32 (o_ld / o_batch_stride in fp32 elements, 16-byte aligned) and every probability enters the PV product as
  * two bf16 terms (hi + lo), so the result can be compared with an fp32 reference at the tolerance BASELINE.json
@@ -354,6 +373,11 @@ typedef struct fk_single_block_weights_mx {
  *   single block: LN -> n8 (once), QKV GEMM, attention -> cat[:, :D], quantize -> cat8[:, :D], MLP GEMM (GELU) -> cat8[:, D:],
  *                 out GEMM on cat8;
  * the bf16 n, ff and cat[:, D:] are not written.  Same bits as the unfused schedule (blocks of 32 never straddle a producer).
+ * fused is a bit set: bit 0 (1) = the schedule above; bit 1 (2), valid only together with bit 0 (fused = 3; fused = 2 alone is
+ * FK_EINVAL) = the attention emits MXFP8 as well (fk_attention_fwd_ws_mxfp8: o8 img rows as stream B and txt rows as stream A with
+ * split = S_txt; cat8 columns [0, D) with ldq = 5D) and no fk_quantize_mxfp8 launch is left -- the bf16 o and cat[:, :D] are then
+ * not written either.  Same bits again.  Where that entry answers FK_EUNSUPPORTED (FK_ATTN_KERNEL=8), and only then, the block runs
+ * the bf16 attention and the quantizer as with fused = 1.
  * The workspace then holds n8 (D bytes per row) AND the block's consumer operand at once: q >= B * S * 5D bytes for a double
  * block (n8 | o8 or ff8), B * S * 6D for a single block (n8 | cat8), s 1/32 of that; too small: FK_EINVAL, nothing launched.
  * splitk != 0 (either schedule): the long-K GEMMs of a block -- ff.net.2 / ff_context.net.2 (K = 4D) and the single block's

@@ -1,4 +1,4 @@
-"""Census of attention_fwd4_kernel's tile bodies from hipcc -S output (no GPU): per MFMA-carrying block the instruction count,
+"""Census of the tile bodies of attention_fwd4_kernel and attention_fwd4_mx_kernel (its MXFP8-output form) from hipcc -S output (no GPU): per MFMA-carrying block the instruction count,
 AGPR copies, scratch traffic, and the distance (in instructions + s_nop states) from the last MFMA of every inline-asm S^T
 chain to the first vector instruction that reads its result -- the hazard hipcc cannot see (12 wait states needed).
   python tools/a4_census.py /tmp/af.s
@@ -47,27 +47,42 @@ def hazard_distances(ins):
     return res
 
 
+# every kernel that carries the hand-placed S^T chains: (tag, symbol), plain and stream-K grid of each output form
+KERNELS = [(form + tag, '_ZN12_GLOBAL__N_1%s%sEEv10AttnParams%s' % (stem, tag, extra))
+           for form, stem, extra in (('', '21attention_fwd4_kernel', ''), ('mx ', '24attention_fwd4_mx_kernel', '9AttnMxOut'))
+           for tag in ('ILb0E', 'ILb1E')]
+
+def kernel_body(s, name):
+    """The assembly of kernel `name`, or None when the file does not define it."""
+    i = s.find(name + ':')
+    return None if i < 0 else s[i:s.index('.Lfunc_end', i)]
+
 def check(path):
     s = open(path).read()
-    bad, chains = [], 0
-    for tag in ('ILb0E', 'ILb1E'):
-        name = '_ZN12_GLOBAL__N_121attention_fwd4_kernel%sEEv10AttnParams' % tag
-        i = s.index(name + ':')
-        body = s[i:s.index('.Lfunc_end', i)]
+    bad, short, missing = [], [], []
+    for tag, name in KERNELS:
+        body = kernel_body(s, name)
+        if body is None:
+            missing.append(name)
+            continue
+        chains = 0
         for lab, ins in blocks_of(body):
             for at, states, reader in hazard_distances(ins):
                 chains += 1
                 if states < 12: bad.append((tag, lab, at, states, reader))
+        if chains < 8: short.append((tag, chains))
+    for n in missing: print('attention_fwd4: kernel %s is not in %s: the hazard check cannot cover it' % (n, path), file=sys.stderr)
     for b in bad: print('attention_fwd4: XDL-write -> VALU-read hazard: %s %s MFMA #%d: %d states before `%s`' % b, file=sys.stderr)
-    if chains < 16: print('attention_fwd4: only %d inline-asm MFMA chains found (expected >= 16)' % chains, file=sys.stderr)
-    return 1 if bad or chains < 16 else 0
+    for t in short: print('attention_fwd4: %s: only %d inline-asm MFMA chains found (expected >= 8)' % t, file=sys.stderr)
+    return 1 if bad or short or missing else 0
 
 def main(path):
     s = open(path).read()
-    for tag in ('ILb0E', 'ILb1E'):
-        name = '_ZN12_GLOBAL__N_121attention_fwd4_kernel%sEEv10AttnParams' % tag
-        i = s.index(name + ':')
-        body = s[i:s.index('.Lfunc_end', i)]
+    for tag, name in KERNELS:
+        body = kernel_body(s, name)
+        if body is None:
+            print(tag, 'not found:', name)
+            continue
         for lab, ins in blocks_of(body):
             n = sum(x.startswith('v_mfma') for x in ins)
             if n < 32: continue

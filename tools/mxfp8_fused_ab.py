@@ -1,7 +1,11 @@
 """Fused vs unfused MXFP8 activation quantization, and both against the bf16 edit -- and, with --parent-tree, against another
 checkout's MXFP8 edit (the commit this schedule is judged against).
 
-FK_MX_FUSED_QUANT is read at import and a parent tree is other code, so every arm of every round is a FRESH child process;
+A third MXFP8 arm, "mxfp8 fused+attn" (FK_MX_FUSED_QUANT=1 FK_MX_FUSED_ATTN=1), adds the attention forward that emits its consumer's
+quantized operand itself: no standalone quantizer launch is left in a forward.  Its record belongs in profiles/ beside the fused
+A/B's; until one exists the switch's gain is unmeasured and its default stays 0.
+
+FK_MX_FUSED_QUANT / FK_MX_FUSED_ATTN are read at import and a parent tree is other code, so every arm of every round is a FRESH child process;
 the arms alternate round by round on one GPU (interleaved: box drift hits all arms alike).  A child builds bench.py's synthetic
 full-depth pipeline, then per workload runs warm-up edits and times each following edit with HIP events; it prints the median.
 
@@ -9,7 +13,8 @@ full-depth pipeline, then per workload runs warm-up edits and times each followi
     rocprofv3 --kernel-trace --stats -d DIR -o fused -- python tools/mxfp8_fused_ab.py --child mxfp8 --one-edit   (FK_MX_FUSED_QUANT=1)
 
 The verdict line applies the repository's bar for keeping a default: the fused arm's WORST round must beat the reference arm's
-BEST round (the parent tree's when given, else this tree's unfused switch) at cfg 2."""
+BEST round (the parent tree's when given, else this tree's unfused switch) at cfg 2; for the fused+attn arm the reference is the
+fused arm (what the switch is added to)."""
 import argparse
 import json
 import os
@@ -63,16 +68,18 @@ def main():
     args = ap.parse_args()
     if args.child:
         return child(args)
-    arms = [("mxfp8 unfused", ROOT, "mxfp8", "0"), ("mxfp8 fused", ROOT, "mxfp8", "1"), ("bf16", ROOT, "bf16", "1")]
+    # (name, tree, weight format, FK_MX_FUSED_QUANT, FK_MX_FUSED_ATTN)
+    arms = [("mxfp8 unfused", ROOT, "mxfp8", "0", "0"), ("mxfp8 fused", ROOT, "mxfp8", "1", "0"),
+            ("mxfp8 fused+attn", ROOT, "mxfp8", "1", "1"), ("bf16", ROOT, "bf16", "1", "0")]
     if args.parent_tree:
-        arms.insert(0, ("mxfp8 parent", os.path.abspath(args.parent_tree), "mxfp8", "1"))
+        arms.insert(0, ("mxfp8 parent", os.path.abspath(args.parent_tree), "mxfp8", "1", "0"))
     sizes = args.sizes.split(",")
     res = {a[0]: {s: [] for s in sizes} for a in arms}
     print(f"# mxfp8_fused_ab: {args.rounds} interleaved rounds, a fresh process per arm and round, per workload {args.warmup} warm-up + "
           f"{args.steps} timed edits (HIP events, median); images/s", flush=True)
     for r in range(args.rounds):
-        for name, tree, fmt, fused in arms:
-            env = dict(os.environ, FK_MX_FUSED_QUANT=fused)
+        for name, tree, fmt, fused, fused_attn in arms:
+            env = dict(os.environ, FK_MX_FUSED_QUANT=fused, FK_MX_FUSED_ATTN=fused_attn)
             env.pop("FK_LIB_PATH", None)
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", fmt, "--tree", tree, "--steps", str(args.steps),
                                 "--warmup", str(args.warmup), "--sizes", args.sizes], env=env, capture_output=True, text=True, timeout=900)
@@ -83,18 +90,21 @@ def main():
             got = json.loads(line[-1][7:])
             for s in sizes:
                 res[name][s].append(got[s])
-            print(f"round {r} {name:14s} " + "  ".join(f"{s} {got[s]:.4f}" for s in sizes), flush=True)
+            print(f"round {r} {name:16s} " + "  ".join(f"{s} {got[s]:.4f}" for s in sizes), flush=True)
     for s in sizes:
         print(f"## {WORKLOADS[s]}")
         for name, *_ in arms:
             v = res[name][s]
-            print(f"{name:14s} median {statistics.median(v):.4f}  best {max(v):.4f}  worst {min(v):.4f}   ({' '.join(f'{x:.4f}' for x in v)})")
+            print(f"{name:16s} median {statistics.median(v):.4f}  best {max(v):.4f}  worst {min(v):.4f}   ({' '.join(f'{x:.4f}' for x in v)})")
         bf = statistics.median(res["bf16"][s])
         print("ratios to bf16: " + "  ".join(f"{name} {statistics.median(res[name][s]) / bf:.3f}" for name, *_ in arms if name != "bf16"))
     ref = "mxfp8 parent" if args.parent_tree else "mxfp8 unfused"
     if "cfg2" in sizes:
         worst, best = min(res["mxfp8 fused"]["cfg2"]), max(res[ref]["cfg2"])
         print(f"verdict (cfg 2): fused worst {worst:.4f} vs {ref} best {best:.4f}: the fused default "
+              f"{'meets' if worst > best else 'does NOT meet'} the bar")
+        worst, best = min(res["mxfp8 fused+attn"]["cfg2"]), max(res["mxfp8 fused"]["cfg2"])
+        print(f"verdict (cfg 2): fused+attn worst {worst:.4f} vs mxfp8 fused best {best:.4f}: the FK_MX_FUSED_ATTN default "
               f"{'meets' if worst > best else 'does NOT meet'} the bar")
     return 0
 
