@@ -204,7 +204,11 @@ class FluxBackward:
 
     # ---- forward (training): the inference kernels, one checkpoint per block -------------------------------------------
     @torch.no_grad()
-    def forward(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance):
+    def forward(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
+                key_mask=None):
+        """``key_mask``: the packed key-padding mask of the joint sequence (``ops.pack_key_mask``; the model's
+        ``_joint_key_mask`` builds it) -- every attention of this forward, of the recomputation and of the backward then runs
+        masked, in the recompute policy and the stored-activation policy alike."""
         m, P = self.m, self.m.p
         pk = m.packed()
         D = m.inner_dim
@@ -227,7 +231,7 @@ class FluxBackward:
         o_ckpt = self._b("o_ckpt", (nblk, B, S, D))
         lse_ckpt = self._b("lse_ckpt", (nblk, B, m.num_heads, S), torch.float32)
         sv = SimpleNamespace(B=B, S=S, S_txt=S_txt, S_img=S_img, cos=cos, sin=sin, ckpt=ckpt, o_ckpt=o_ckpt, lse_ckpt=lse_ckpt,
-                             enc=enc, hs=hs, ws=ws, pk=pk, nd=len(pk.double),
+                             enc=enc, hs=hs, ws=ws, pk=pk, nd=len(pk.double), key_mask=key_mask,
                              store=self._should_store(B, S, len(pk.double), len(pk.single)))
         for i in range(len(pk.double)):
             ckpt[i].copy_(s)
@@ -265,7 +269,7 @@ class FluxBackward:
                      P(p + "attn.norm_added_q.weight"), P(p + "attn.norm_added_k.weight"), sv.cos, sv.sin, S_txt)
         o = sv.o_ckpt[i]
         if first:
-            ops.attention_lse(bb.q, bb.k, qkv[:, :, 2 * D:], o, sv.lse_ckpt[i])
+            ops.attention_lse(bb.q, bb.k, qkv[:, :, 2 * D:], o, sv.lse_ckpt[i], key_mask=sv.key_mask)
         y1 = bb.y1
         ops.gemm_grouped([dict(a=o[:, img], w=P(p + "attn.to_out.0.weight"), bias=P(p + "attn.to_out.0.bias"), out=y1[:, img]),
                           dict(a=o[:, txt], w=P(p + "attn.to_add_out.weight"), bias=P(p + "attn.to_add_out.bias"), out=y1[:, txt])])
@@ -301,7 +305,7 @@ class FluxBackward:
         ops.gelu_tanh(h1, ws.cat[:, :, D:])
         o = sv.o_ckpt[sv.nd + j]
         if first:
-            ops.attention_lse(bb.q, bb.k, qkv[:, :, 2 * D:], o, sv.lse_ckpt[sv.nd + j])
+            ops.attention_lse(bb.q, bb.k, qkv[:, :, 2 * D:], o, sv.lse_ckpt[sv.nd + j], key_mask=sv.key_mask)
         ws.cat[:, :, :D].copy_(o)          # proj_out reads [attn | mlp] as one K = 5D operand
         y1 = bb.y1
         ops.gemm(ws.cat, P(p + "proj_out.weight"), P(p + "proj_out.bias"), out=y1)
@@ -417,7 +421,7 @@ class FluxBackward:
         dqkv = self._b("dqkv", (B, S, 3 * D))
         dq, dk = self._b("dq", (B, H, S, 128)), self._b("dk", (B, H, S, 128))
         dsum = ops.rowdot(do, o, H, out=self._b("dsum", (B, H, S), torch.float32))
-        ops.attention_bwd(bb.q, bb.k, bb.qkv[:, :, 2 * D:], do, lse, dsum, dq, dk, dqkv[:, :, 2 * D:])
+        ops.attention_bwd(bb.q, bb.k, bb.qkv[:, :, 2 * D:], do, lse, dsum, dq, dk, dqkv[:, :, 2 * D:], key_mask=sv.key_mask)
         dw = ops.qkv_post_bwd(dq, dk, bb.qkv, dqkv, P(p + "attn.norm_q.weight"), P(p + "attn.norm_k.weight"),
                               P(p + "attn.norm_added_q.weight"), P(p + "attn.norm_added_k.weight"), sv.cos, sv.sin, S_txt)
         # views of this call's own fresh [2, 2, 128] result: nothing to clone
@@ -473,6 +477,8 @@ class FluxBackward:
         """fk_bwd_ws of this pass, or None when the pass does not fit the entry points' scope (then: the per-launch route)."""
         m, ws, pk = self.m, sv.ws, sv.pk
         D, H, B, S = m.inner_dim, m.num_heads, sv.B, sv.S
+        if sv.key_mask is not None:          # the block-level entry points take no mask
+            return None
         in_batch_scope = block_api_batch_ok("single", B) or block_api_batch_ok("double", B)
         if not (K_MAJOR >= 2 and sv.store and in_batch_scope and sv.S_txt % 64 == 0 and sv.S_img % 64 == 0 and D % 256 == 0):
             return None
@@ -619,7 +625,7 @@ class FluxBackward:
         dq, dk = self._b("dq", (B, H, S, 128)), self._b("dk", (B, H, S, 128))
         o, lse = sv.o_ckpt[len(pk.double) + j], sv.lse_ckpt[len(pk.double) + j]
         dsum = ops.rowdot(do, o, H, out=self._b("dsum", (B, H, S), torch.float32))
-        ops.attention_bwd(bb.q, bb.k, bb.qkv[:, :, 2 * D:], do, lse, dsum, dq, dk, dqkv[:, :, 2 * D:])
+        ops.attention_bwd(bb.q, bb.k, bb.qkv[:, :, 2 * D:], do, lse, dsum, dq, dk, dqkv[:, :, 2 * D:], key_mask=sv.key_mask)
         dw = ops.qkv_post_bwd(dq, dk, bb.qkv, dqkv, P(p + "attn.norm_q.weight"), P(p + "attn.norm_k.weight"), None, None,
                               sv.cos, sv.sin, 0)
         grads[p + "attn.norm_q.weight"], grads[p + "attn.norm_k.weight"] = dw[0, 0], dw[1, 0]
@@ -657,11 +663,12 @@ class FluxTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, bw, names, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids,
-                guidance, *params):
+                guidance, key_mask, *params):
         ctx.bw, ctx.names = bw, names
         ctx.enc_dtype = encoder_hidden_states.dtype
         ctx.need_enc = encoder_hidden_states.requires_grad
-        return bw.forward(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance)
+        return bw.forward(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids, guidance,
+                          key_mask=key_mask)          # key_mask: packed int64, not differentiable
 
     @staticmethod
     def backward(ctx, dsample):
@@ -673,4 +680,4 @@ class FluxTrainFunction(torch.autograd.Function):
                 raise RuntimeError(f"FluxBackward produced no gradient for {n}")
             out.append(g if g.dtype == BF16 else g.to(BF16))
         d_enc = d_enc.to(ctx.enc_dtype) if ctx.need_enc else None
-        return (None, None, None, d_enc, None, None, None, None, None, *out)
+        return (None, None, None, d_enc, None, None, None, None, None, None, *out)

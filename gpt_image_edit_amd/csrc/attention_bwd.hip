@@ -74,6 +74,16 @@ struct BwdParams {
   unsigned* sk_ctl;
 };
 constexpr int PART_FLOATS = 256 * 128 + 2 * 512;   // the attention forward's slot layout (the (l, m) pairs are unused here)
+// KMASK (fk_attention_bwd_masked_bf16): the forward's key-padding mask, one 64-bit word per (batch, 64-key tile) -- CBLK is the
+// forward's KVBLK, so the words serve every pass as they are.  Where keys are the streamed columns (dQ pass) the word picks the
+// tile: all zeros -> taken from the ring and not computed, otherwise the masked body with w = 0 at the masked keys (one copy,
+// its selects are no-ops in a full tile).  Where keys are the stationary rows (dV, dK, the paired pass) a masked key's row
+// is STORED as zeros, and an item without a valid key streams nothing.  Queries are never masked.  Plain grids only.
+struct BwdParamsMasked : BwdParams {
+  const uint64_t* kmask;   // [B, ceil(S / 64)]
+};
+template <bool KMASK>
+using BwdParamsOf = std::conditional_t<KMASK, BwdParamsMasked, BwdParams>;
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
@@ -101,8 +111,9 @@ FK_DEV void wait_vmcnt() {
 }
 FK_DEV int swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }   // slot XOR of LDS row r (header)
 
-template <int MODE, bool STREAMK = false>
-__global__ __launch_bounds__(512, 2) void attention_bwd_kernel(const BwdParams p) {
+template <int MODE, bool STREAMK = false, bool KMASK = false>
+__global__ __launch_bounds__(512, 2) void attention_bwd_kernel(const BwdParamsOf<KMASK> p) {
+  static_assert(!(KMASK && STREAMK), "masked launches take the plain grid");
   constexpr bool HAS_C = MODE != MODE_DV;          // second product (dp) and its streamed image
   constexpr bool COL_STATS = MODE != MODE_DQ;      // lse / D vary along the streamed dimension
   constexpr int LOADS = 4 + (COL_STATS ? (MODE == MODE_DK ? 2 : 1) : 0);
@@ -168,6 +179,25 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_kernel(const BwdParams p
   const int rb = item % nrb;
   const int bh = item / nrb;
   const int b = bh / p.H, h = bh - b * p.H;
+  // KMASK: the valid-key word of 64-key tile t (wave-uniform; bits >= S cleared)
+  [[maybe_unused]] uint64_t kw = 0;
+  [[maybe_unused]] auto key_word = [&](int t) __attribute__((always_inline)) {
+    if constexpr (KMASK) {
+      uint64_t w = p.kmask[(int64_t)b * nt + t];
+      const int left = p.S - t * CBLK;
+      if (left < CBLK) w &= (1ull << left) - 1;
+      return w;
+    } else {
+      return ~0ull;
+    }
+  };
+  if constexpr (KMASK && MODE != MODE_DQ) {   // rows are keys: an item (4 words) without a valid key streams nothing
+    uint64_t any = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (rb * 4 + i < nt) any |= key_word(rb * 4 + i);
+    if (any == 0) te = tb;
+  }
 
   // which tensors play which role: image 0 feeds the s product (row fragments), image 1 the dp product (row fragments) or,
   // in the dV pass, the accumulating product (transpose reads); the dQ / dK passes transpose-read image 0
@@ -180,6 +210,8 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_kernel(const BwdParams p
   // ---- stationary row operands (B operand of the swapped products): lane holds X[row][16 kk + 8 hh .. +8] ----------
   const int row = rb * 256 + wave * 32 + ql;
   const int rowc = min(row, p.S - 1);
+  [[maybe_unused]] bool row_valid = true;   // KMASK, rows are keys: this lane's key is valid
+  if constexpr (KMASK && MODE != MODE_DQ) row_valid = (p.kmask[(int64_t)b * nt + (rowc >> 6)] >> (rowc & 63)) & 1;
   bf16x8_t x1f[8], x2f[8];
   {
     const bf16_t* xp = X1.p + (int64_t)b * X1.bs + (int64_t)h * X1.hs + (int64_t)rowc * X1.ld + 8 * hh;
@@ -316,8 +348,11 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_kernel(const BwdParams p
           const float pr = __builtin_amdgcn_exp2f(fmaf(s[r], p.scale_log2, -lv[j]));
           float wv = pr;
           if constexpr (HAS_C) wv = pr * dp[r];   // = -p (dP - D); sign and softmax scale multiply the accumulator at the store
-          if constexpr (MASK)
+          if constexpr (MASK && KMASK && MODE == MODE_DQ) {
+            if (!(((uint32_t)(kw >> (32 * kb)) >> (8 * g + 4 * hh + j)) & 1u)) wv = 0.f;
+          } else if constexpr (MASK) {
             if (t * CBLK + 32 * kb + 8 * g + 4 * hh + j >= p.S) wv = 0.f;
+          }
           w[r] = wv;
         }
       }
@@ -357,10 +392,20 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_kernel(const BwdParams p
     st_pf = (st_pf == STAGES - 1) ? 0 : st_pf + 1;
     return sb;
   };
+  if constexpr (KMASK && MODE == MODE_DQ) {
+    for (int t = tb; t < te; ++t) {
+      kw = key_word(t);
+      const char* sb = acquire(t);        // an empty tile still goes through the ring
+      // ONE copy of the body, its selects driven by the word (no-ops in a full tile): a second copy inside this loop costs
+      // the accumulators their registers (80 spilled VGPRs)
+      if (kw != 0) tile_body(sb, t, std::true_type{});
+    }
+  } else {
   const bool masked = ragged && te == nt;               // the pass ends with the item's ragged tile
   const int n_plain = masked ? te - 1 : te;
   for (int t = tb; t < n_plain; ++t) tile_body(acquire(t), t, std::false_type{});
   if (masked) tile_body(acquire(nt - 1), nt - 1, std::true_type{});   // after the loop: one accumulator live range each
+  }
 
   // ---- stream-K seam (attention_fwd.hip): the two parts of a cut item ADD their accumulators; whoever arrives second does it
   if constexpr (STREAMK) {
@@ -430,6 +475,8 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_kernel(const BwdParams p
         u32x2_t pk;
         pk[0] = pack_bf2(acc[df][4 * g + 0] * osc, acc[df][4 * g + 1] * osc);
         pk[1] = pack_bf2(acc[df][4 * g + 2] * osc, acc[df][4 * g + 3] * osc);
+        if constexpr (KMASK)
+          if (!row_valid) pk = u32x2_t{0u, 0u};   // a masked key's gradient row: exact zeros
         *(u32x2_t*)(op + 32 * df + 8 * g) = pk;
       }
   }
@@ -448,8 +495,9 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_kernel(const BwdParams p
 // two parts of a cut item ADD their fp32 accumulators (the producers' dV^T, the consumers' dK^T) through the cut's workspace
 // slot: commutative, so still deterministic.  Built, parity-green, and no faster than the plain grid (the launcher has the
 // numbers): not the default.
-template <bool STREAMK>
-__global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdParams p) {
+template <bool STREAMK, bool KMASK = false>
+__global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdParamsOf<KMASK> p) {
+  static_assert(!(KMASK && STREAMK), "masked launches take the plain grid");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -511,6 +559,22 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdPara
   // ---- stationary row operand: K rows for the producer, V rows for the consumer ----------------------------------------
   const int row = rb * 128 + pair * 32 + ql;
   const int rowc = min(row, p.S - 1);
+  [[maybe_unused]] bool row_valid = true;   // KMASK: this lane's key is valid
+  if constexpr (KMASK) {
+    row_valid = (p.kmask[(int64_t)b * nt + (rowc >> 6)] >> (rowc & 63)) & 1;
+    uint64_t any = 0;                        // the item's 128 keys = 2 words; none valid (within S): stream nothing
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int t = rb * 2 + i;
+      if (t < nt) {
+        uint64_t w = p.kmask[(int64_t)b * nt + t];
+        const int left = p.S - t * CBLK;
+        if (left < CBLK) w &= (1ull << left) - 1;
+        any |= w;
+      }
+    }
+    if (any == 0) te = tb;
+  }
   bf16x8_t xf[8];
   {
     const bf16_t* xb = producer ? p.k.p + (int64_t)b * p.k.bs + (int64_t)h * p.k.hs + (int64_t)rowc * p.k.ld
@@ -678,7 +742,7 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdPara
   };
 
   char* const pbuf = smem + STAGES * STAGE_BYTES + pair * 8192 + lane * 16;
-  issue_tile(tb, 0);
+  if (!KMASK || tb < te) issue_tile(tb, 0);
 
   // Iteration i = tb .. te of BOTH roles: wait for the own DMA pieces of tile i and the own p stores of tile i - 1, meet,
   // start the DMA of tile i + 1 into the stage the consumers left in iteration i - 1.  The roles run separate loops (one
@@ -790,6 +854,8 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdPara
         u32x2_t pk;
         pk[0] = pack_bf2(acc[df][4 * g + 0] * osc, acc[df][4 * g + 1] * osc);
         pk[1] = pack_bf2(acc[df][4 * g + 2] * osc, acc[df][4 * g + 3] * osc);
+        if constexpr (KMASK)
+          if (!row_valid) pk = u32x2_t{0u, 0u};   // a masked key's gradient row: exact zeros
         *(u32x2_t*)(op + 32 * df + 8 * g) = pk;
       }
   }
@@ -798,10 +864,10 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdPara
   }   // passes
 }
 
-template <int MODE, bool STREAMK = false>
-int launch_bwd(const BwdParams& p, hipStream_t stream, int grid = 0) {
+template <int MODE, bool STREAMK = false, bool KMASK = false>
+int launch_bwd(const BwdParamsOf<KMASK>& p, hipStream_t stream, int grid = 0) {
   constexpr int SMEM = STAGES * STAGE_BYTES;
-  auto kern = attention_bwd_kernel<MODE, STREAMK>;
+  auto kern = attention_bwd_kernel<MODE, STREAMK, KMASK>;
   FK_ENSURE_MAX_LDS(kern, SMEM, "fk_attention_bwd_bf16");
   const int nrb = (p.S + 255) / 256;
   hipLaunchKernelGGL(kern, dim3(STREAMK ? grid : nrb * p.H * p.B), dim3(512), SMEM, stream, p);
@@ -822,10 +888,10 @@ int bwd_cu_count() {
 constexpr int BWD_MIN_PART = 8;
 constexpr int BWD_CTL_BYTES = 16384;   // = ATTN_CTL_BYTES of attention_fwd.hip
 
-template <bool STREAMK>
-int launch_dkv(const BwdParams& p, hipStream_t stream, int grid = 0) {
+template <bool STREAMK, bool KMASK = false>
+int launch_dkv(const BwdParamsOf<KMASK>& p, hipStream_t stream, int grid = 0) {
   constexpr int SMEM = STAGES * STAGE_BYTES + PBUF_BYTES;
-  auto kern = attention_bwd_dkv_kernel<STREAMK>;
+  auto kern = attention_bwd_dkv_kernel<STREAMK, KMASK>;
   FK_ENSURE_MAX_LDS(kern, SMEM, "fk_attention_bwd_bf16");
   const int nrb = (p.S + 127) / 128;
   hipLaunchKernelGGL(kern, dim3(STREAMK ? grid : nrb * p.H * p.B), dim3(512), SMEM, stream, p);
@@ -844,7 +910,8 @@ TView tv(const fk_attn_view& v) { return TView{(const bf16_t*)v.p, v.ld, v.head_
 static int attention_bwd_entry(const fk_attn_view* q, const fk_attn_view* k, const fk_attn_view* v,
                                const fk_attn_view* dout, const float* lse, const float* dsum, const fk_attn_view* dq,
                                const fk_attn_view* dk, const fk_attn_view* dv, int32_t B, int32_t H, int32_t S,
-                               float scale, void* ws, int64_t ws_bytes, int grid, int passes, fk_stream_t stream_) {
+                               float scale, void* ws, int64_t ws_bytes, int grid, int passes, fk_stream_t stream_,
+                               const uint64_t* kmask = nullptr) {
   FK_CHECK_ARG(q && k && v && dout && lse && dsum && dq && dk && dv, "fk_attention_bwd_bf16: null pointer");
   FK_CHECK_ARG(grid >= -1 && grid != 1, "fk_attention_bwd_ws_bf16: grid %d is not 0 (default), -1 (plain grid) or a workgroup count >= 2", grid);
   FK_CHECK_ARG(passes == 0 || passes == 2 || passes == 3, "fk_attention_bwd_ws_bf16: passes %d is not 0 / 2 (dQ pass + paired dK / dV "
@@ -864,6 +931,26 @@ static int attention_bwd_entry(const fk_attn_view* q, const fk_attn_view* k, con
     p.out = (bf16_t*)o.p; p.o_ld = o.ld; p.o_hs = o.head_stride; p.o_bs = o.batch_stride;
   };
   set_out(*dq);
+  if (kmask) {   // the key-masked form: the same passes on plain grids
+    BwdParamsMasked pm;
+    auto masked = [&]() -> const BwdParamsMasked& {
+      static_cast<BwdParams&>(pm) = p;
+      pm.kmask = kmask;
+      return pm;
+    };
+    int rc = launch_bwd<MODE_DQ, false, true>(masked(), stream);
+    if (rc != FK_OK) return rc;
+    if (passes != 3) {
+      set_out(*dk);
+      p.out2 = (bf16_t*)dv->p; p.o2_ld = dv->ld; p.o2_hs = dv->head_stride; p.o2_bs = dv->batch_stride;
+      return launch_dkv<false, true>(masked(), stream);
+    }
+    set_out(*dv);
+    rc = launch_bwd<MODE_DV, false, true>(masked(), stream);
+    if (rc != FK_OK) return rc;
+    set_out(*dk);
+    return launch_bwd<MODE_DK, false, true>(masked(), stream);
+  }
   // Stream-K grid where one workgroup per item would waste >= 4 % of its rounds of CUs (attention_fwd.hip); items of `rows` rows
   const int mode = grid == 0 ? 1 : (grid < 0 ? 0 : grid);
   const int G = mode >= 2 ? (mode < bwd_cu_count() ? mode : bwd_cu_count()) : bwd_cu_count();
@@ -913,4 +1000,12 @@ extern "C" int fk_attention_bwd_ws_bf16(const fk_attn_view* q, const fk_attn_vie
                                         const fk_attn_view* dk, const fk_attn_view* dv, int32_t B, int32_t H, int32_t S,
                                         float scale, void* ws, int64_t ws_bytes, int32_t grid, int32_t passes, fk_stream_t stream_) {
   return attention_bwd_entry(q, k, v, dout, lse, dsum, dq, dk, dv, B, H, S, scale, ws, ws_bytes, grid, passes, stream_);
+}
+
+extern "C" int fk_attention_bwd_masked_bf16(const fk_attn_view* q, const fk_attn_view* k, const fk_attn_view* v,
+                                            const fk_attn_view* dout, const float* lse, const float* dsum, const fk_attn_view* dq,
+                                            const fk_attn_view* dk, const fk_attn_view* dv, const uint64_t* kmask, int32_t B,
+                                            int32_t H, int32_t S, float scale, int32_t passes, fk_stream_t stream_) {
+  FK_CHECK_ARG(kmask != nullptr && (uintptr_t)kmask % 8 == 0, "fk_attention_bwd_masked_bf16: the key mask must be an 8-byte aligned pointer");
+  return attention_bwd_entry(q, k, v, dout, lse, dsum, dq, dk, dv, B, H, S, scale, nullptr, 0, -1, passes, stream_, kmask);
 }

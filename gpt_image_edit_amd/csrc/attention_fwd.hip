@@ -27,8 +27,20 @@ namespace {
 // the probabilities enter the PV product as TWO bf16 terms (p = hi + lo, 16 mantissa bits instead of 8), so that
 // the result can be held against an fp32 reference at rtol 1e-3 / atol 1e-4 -- with one bf16 term the rounding of
 // P alone (2^-9 per term) sits above that tolerance whatever the kernel does.
-template <int NW, bool F32OUT, bool ILV, bool STREAMK>
-__global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel(const AttnParams p) {
+//
+// KMASK (fk_attention_fwd_masked_bf16): a key-padding mask, one 64-bit word per (batch, KV tile), bit j = key 64 t + j is
+// valid.  It generalises the ragged last tile: bits at positions >= S are cleared in the word, and the word picks the tile's
+// copy -- all ones: the unmasked body; all zeros: the tile is taken from the ring (wait, barrier, prefetch: the ring protocol
+// is untouched) and nothing is computed; otherwise the MASK body, whose select is driven by the bit.  A masked key's score is
+// -1e30, its numerator exp2(-1e30 c - m_ref) = 0 exactly, as beyond S.  Plain grid only (the launcher).
+struct AttnParamsMasked : AttnParams {
+  const uint64_t* kmask;   // [B, ceil(S / 64)]
+};
+
+template <int NW, bool F32OUT, bool ILV, bool STREAMK, bool KMASK = false>
+__global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel(
+    const std::conditional_t<KMASK, AttnParamsMasked, AttnParams> p) {
+  static_assert(!(KMASK && STREAMK), "masked launches take the plain grid");
   constexpr int STAGES = 3;           // K / V ring: one barrier per tile, tile kt + 2 requested when tile kt is published
   constexpr int QBLK = NW * 32;
   static_assert(QBLK == 256, "the item list and the stream-K partial layout assume 256 query rows per workgroup");
@@ -114,6 +126,19 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel
   const int bh = item / nqb;
   const int b = bh / p.H, h = bh - b * p.H;
   const int q_row0 = qb * QBLK;
+
+  // KMASK: the valid-key word of the tile being worked on (wave-uniform; bits >= S cleared)
+  [[maybe_unused]] uint64_t kw = 0;
+  [[maybe_unused]] auto tile_word = [&](int kt) __attribute__((always_inline)) {
+    if constexpr (KMASK) {
+      uint64_t w = p.kmask[(int64_t)b * nkt + kt];
+      const int left = p.S - kt * KVBLK;                 // >= 1
+      if (left < KVBLK) w &= (1ull << left) - 1;
+      return w;
+    } else {
+      return ~0ull;
+    }
+  };
 
   const bf16_t* Kg = p.k + (int64_t)bh * p.S * HD;
   const bf16_t* Vg = p.v + (int64_t)b * p.v_bs + h * HD;
@@ -220,7 +245,12 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // the DS read of this slot first ...
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // ... then its MFMA
     }
-    if constexpr (MASK) {
+    if constexpr (MASK && KMASK) {
+      const uint32_t bits = (uint32_t)(kw >> (32 * kb)) >> (4 * hh);   // bit (r & 3) + 8 (r >> 2): this lane's key r
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (!((bits >> ((r & 3) + 8 * (r >> 2))) & 1u)) s[r] = -1.0e30f;
+    } else if constexpr (MASK) {
       const int kbase = kt * KVBLK + 32 * kb + 4 * hh;
 #pragma unroll
       for (int r = 0; r < 16; ++r)
@@ -254,7 +284,11 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel
   #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         f32x16_t s = scores(sb, kb, kt, mask_tag);
-        if constexpr (FIRST) {
+        if constexpr (FIRST && KMASK) {
+          // the reference comes from the first 32-key block that HAS a valid key; an all-masked block 0 runs against the
+          // initial m_ref = 0, where its numerators exp2(-1e30 c) are exactly 0
+          if (kb == 0 ? (uint32_t)kw != 0 : (uint32_t)kw == 0) m_ref = block_max(s) + REF_BIAS;
+        } else if constexpr (FIRST) {
           if (kb == 0) m_ref = block_max(s) + REF_BIAS;   // reference = row maximum over the first 32 keys + bias
         }
         const float nm = -m_ref;
@@ -307,8 +341,10 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel
       const char* sb = acquire_tile(kt);
       float psum = 0.f;
       f32x16_t s0 = scores(sb, 0, kt, mask_tag);
-      if constexpr (FIRST) m_ref = block_max(s0) + REF_BIAS;   // reference = row maximum over the first 32 keys + bias
-      const float nm = -m_ref;
+      if constexpr (FIRST && KMASK) {
+        if ((uint32_t)kw != 0) m_ref = block_max(s0) + REF_BIAS;   // else: from block 1, below (block 0's numerators are 0)
+      } else if constexpr (FIRST) m_ref = block_max(s0) + REF_BIAS;   // reference = row maximum over the first 32 keys + bias
+      float nm = -m_ref;   // (KMASK: moved to block 1 when block 0 of the first tile is all masked)
       // softmax numerators of two scores (log2 domain; raw v_exp_f32, denormal results may flush)
       auto expo2 = [&](f32x16_t& s, int r) __attribute__((always_inline)) {
   #pragma unroll
@@ -353,11 +389,22 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel
             __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // two row-sum adds
           }
         }
-        if constexpr (MASK) {
+        if constexpr (MASK && KMASK) {
+          const uint32_t bits = (uint32_t)(kw >> 32) >> (4 * hh);
+  #pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (!((bits >> ((r & 3) + 8 * (r >> 2))) & 1u)) s1[r] = -1.0e30f;
+        } else if constexpr (MASK) {
           const int kbase = kt * KVBLK + 32 + 4 * hh;
   #pragma unroll
           for (int r = 0; r < 16; ++r)
             if (kbase + (r & 3) + 8 * (r >> 2) >= p.S) s1[r] = -1.0e30f;
+        }
+        if constexpr (FIRST && KMASK) {
+          if ((uint32_t)kw == 0) {
+            m_ref = block_max(s1) + REF_BIAS;
+            nm = -m_ref;
+          }
         }
       }
       // ---- O^T += V^T P^T: block 0 (block 1's exponentials in the shadow), then block 1 ------------------------------
@@ -401,6 +448,30 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel
   int* const wg_flag = (int*)(smem + STAGES * STAGE_BYTES);   // one word past the ring (allocated by the launcher)
   // tiles [kt0, kt1): the first one sets the exponent reference (attempt 0), only the item's last one can need the mask
   auto run_tiles = [&](auto first_tag) __attribute__((always_inline)) {
+    if constexpr (KMASK) {
+      // empty tiles go through the ring only; the first tile WITH a valid key sets the exponent reference (attempt 0)
+      int kt = kt0;
+      for (; kt < kt1; ++kt) {
+        kw = tile_word(kt);
+        if (kw != 0) break;
+        acquire_tile(kt);
+        release_tile();
+      }
+      if (kt < kt1) {   // (no valid key at all breaks the precondition: l = 0, the rows come out NaN)
+        if (kw == ~0ull) do_tile(kt, FF{}, first_tag);
+        else do_tile(kt, TT{}, first_tag);
+        ++kt;
+      }
+      for (; kt < kt1; ++kt) {
+        kw = tile_word(kt);
+        if (kw == 0) {
+          acquire_tile(kt);
+          release_tile();
+        } else if (kw == ~0ull) do_tile(kt, FF{}, FF{});
+        else do_tile(kt, TT{}, FF{});
+      }
+      return;
+    }
     const int last = kt1 - 1;
     if (kt0 == last) {
       if (last_masked) do_tile(kt0, TT{}, first_tag);
@@ -419,10 +490,21 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel
       m_ref = -3.0e38f;
       for (int kt = kt0; kt < kt1; ++kt) {
         const char* sb = acquire_tile(kt);
+        if constexpr (KMASK) {
+          kw = tile_word(kt);
+          if (kw == ~0ull) {
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          if (last_masked && kt == kt1 - 1) m_ref = fmaxf(m_ref, block_max(scores(sb, kb, kt, TT{})));
-          else m_ref = fmaxf(m_ref, block_max(scores(sb, kb, kt, FF{})));
+            for (int kb = 0; kb < 2; ++kb) m_ref = fmaxf(m_ref, block_max(scores(sb, kb, kt, FF{})));
+          } else if (kw != 0) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) m_ref = fmaxf(m_ref, block_max(scores(sb, kb, kt, TT{})));
+          }
+        } else {
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb) {
+            if (last_masked && kt == kt1 - 1) m_ref = fmaxf(m_ref, block_max(scores(sb, kb, kt, TT{})));
+            else m_ref = fmaxf(m_ref, block_max(scores(sb, kb, kt, FF{})));
+          }
         }
         release_tile();
       }
@@ -602,10 +684,19 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 2 : 1) void attention_fwd_kernel
 // barrier (timing probe): +1..6 %.  Counters at B = 4, S = 8704: matrix pipe 52 % busy at 1.86 GHz, waves 37 % parked,
 // 32 % issue-stalled, LDS array ~26 % busy, no bank conflicts.
 
-template <int NW, bool F32OUT, bool ILV, bool STREAMK>
-int launch(const AttnParams& p, int grid, hipStream_t stream) {
+// [B, S] bytes -> [B, ceil(S / 64)] words: one wave per word, lane j votes for key 64 t + j (keys >= S vote 0)
+__global__ __launch_bounds__(64) void pack_key_mask_kernel(const uint8_t* mask, int64_t batch_stride, int S, uint64_t* out) {
+  const int t = blockIdx.x, b = blockIdx.y;
+  const int key = t * KVBLK + (int)threadIdx.x;
+  const bool valid = key < S && mask[(int64_t)b * batch_stride + key] != 0;
+  const uint64_t w = __builtin_amdgcn_ballot_w64(valid);
+  if (threadIdx.x == 0) out[(int64_t)b * gridDim.x + t] = w;
+}
+
+template <int NW, bool F32OUT, bool ILV, bool STREAMK, bool KMASK = false>
+int launch(const std::conditional_t<KMASK, AttnParamsMasked, AttnParams>& p, int grid, hipStream_t stream) {
   constexpr int SMEM = 3 * STAGE_BYTES + 16;   // ring + the restart flag word
-  auto kern = attention_fwd_kernel<NW, F32OUT, ILV, STREAMK>;
+  auto kern = attention_fwd_kernel<NW, F32OUT, ILV, STREAMK, KMASK>;
   FK_ENSURE_MAX_LDS(kern, SMEM, "fk_attention_fwd_bf16");
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), SMEM, stream, p);
   FK_CHECK_LAUNCH("fk_attention_fwd_bf16");
@@ -666,7 +757,8 @@ static bool use_interleaved(const AttnParams& p) {
 int attention_entry(const void* q, const void* k, const void* v, void* o, int32_t B, int32_t H, int32_t S, int64_t v_ld,
                     int64_t v_batch_stride, int64_t o_ld, int64_t o_batch_stride, float scale, bool f32out,
                     hipStream_t stream, float* lse = nullptr, void* ws = nullptr, int64_t ws_bytes = 0, int grid = 0,
-                    const AttnMxOut* mx = nullptr) {   // mx: the MXFP8-output form (4-wave kernel only); o / o_ld / o_batch_stride unused
+                    const AttnMxOut* mx = nullptr,     // mx: the MXFP8-output form (4-wave kernel only); o / o_ld / o_batch_stride unused
+                    const uint64_t* kmask = nullptr) { // kmask: the key-masked form (8-wave kernel, plain grid)
   FK_CHECK_ARG(grid >= -1 && grid != 1, "fk_attention_fwd_ws_bf16: grid %d is not 0 (stream-K grid where the plain one wastes a round), "
                "-1 (always one workgroup per 256-row block) or a workgroup count >= 2 (test hook)", grid);
   FK_CHECK_ARG(q && k && v && (o || mx), "fk_attention_fwd_bf16: null pointer");
@@ -693,6 +785,14 @@ int attention_entry(const void* q, const void* k, const void* v, void* o, int32_
   p.sk_rounds = 0;
   p.sk_partials = nullptr;
   p.sk_ctl = nullptr;
+  if (kmask) {
+    AttnParamsMasked pm;
+    static_cast<AttnParams&>(pm) = p;
+    pm.kmask = kmask;
+    if (f32out) return launch<8, true, false, false, true>(pm, (int)n_items, stream);
+    return use_interleaved(p) ? launch<8, false, true, false, true>(pm, (int)n_items, stream)
+                              : launch<8, false, false, false, true>(pm, (int)n_items, stream);
+  }
   if (f32out) return launch<8, true, false, false>(p, (int)n_items, stream);
   const int mode = grid == 0 ? 1 : (grid < 0 ? 0 : grid);   // 0: never; 1: where it pays; >= 2 (test hook): a persistent grid of `mode` workgroups
   const int G = mode >= 2 ? (mode < attn_cu_count() ? mode : attn_cu_count()) : attn_cu_count();
@@ -780,4 +880,29 @@ extern "C" int fk_attention_fwd_f32_debug(const void* q, const void* k, const vo
                                           int64_t o_batch_stride, float scale, fk_stream_t stream_) {
   return attention_entry(q, k, v, o, B, H, S, v_ld, v_batch_stride, o_ld, o_batch_stride, scale, true,
                          (hipStream_t)stream_);
+}
+
+extern "C" int fk_pack_key_mask(const uint8_t* mask, int64_t batch_stride, int32_t B, int32_t S, uint64_t* out, fk_stream_t stream_) {
+  FK_CHECK_ARG(mask && out && (uintptr_t)out % 8 == 0, "fk_pack_key_mask: null pointer or an output that is not 8-byte aligned");
+  FK_CHECK_ARG(B > 0 && B <= 65535 && S > 0 && batch_stride >= 0, "fk_pack_key_mask: bad B / S / batch_stride %d %d %lld", B, S,
+               (long long)batch_stride);
+  hipLaunchKernelGGL(pack_key_mask_kernel, dim3((S + KVBLK - 1) / KVBLK, B), dim3(64), 0, (hipStream_t)stream_, mask, batch_stride, (int)S, out);
+  FK_CHECK_LAUNCH("fk_pack_key_mask");
+  return FK_OK;
+}
+
+extern "C" int fk_attention_fwd_masked_bf16(const void* q, const void* k, const void* v, void* o, float* lse, const uint64_t* kmask,
+                                            int32_t B, int32_t H, int32_t S, int64_t v_ld, int64_t v_batch_stride, int64_t o_ld,
+                                            int64_t o_batch_stride, float scale, fk_stream_t stream_) {
+  FK_CHECK_ARG(kmask != nullptr && (uintptr_t)kmask % 8 == 0, "fk_attention_fwd_masked_bf16: the key mask must be an 8-byte aligned pointer");
+  return attention_entry(q, k, v, o, B, H, S, v_ld, v_batch_stride, o_ld, o_batch_stride, scale, false, (hipStream_t)stream_, lse,
+                         nullptr, 0, -1, nullptr, kmask);
+}
+
+extern "C" int fk_attention_fwd_masked_f32_debug(const void* q, const void* k, const void* v, float* o, const uint64_t* kmask, int32_t B,
+                                                 int32_t H, int32_t S, int64_t v_ld, int64_t v_batch_stride, int64_t o_ld,
+                                                 int64_t o_batch_stride, float scale, fk_stream_t stream_) {
+  FK_CHECK_ARG(kmask != nullptr && (uintptr_t)kmask % 8 == 0, "fk_attention_fwd_masked_f32_debug: the key mask must be an 8-byte aligned pointer");
+  return attention_entry(q, k, v, o, B, H, S, v_ld, v_batch_stride, o_ld, o_batch_stride, scale, true, (hipStream_t)stream_, nullptr,
+                         nullptr, 0, -1, nullptr, kmask);
 }

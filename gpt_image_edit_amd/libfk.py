@@ -155,6 +155,10 @@ SIGNATURES = {
     "fk_attention_fwd_ws_mxfp8": (c_i32, [c_vp] * 4 + [c_i32] * 3 + [c_i64] * 2 + [c_f32, ctypes.POINTER(AttnMxOut), c_vp, c_i64, c_i32, c_vp]),
     "fk_attention_ws_bytes": (c_i64, []),
     "fk_attention_fwd_f32_debug": (c_i32, [c_vp] * 4 + [c_i32] * 3 + [c_i64] * 4 + [c_f32, c_vp]),
+    "fk_pack_key_mask": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "fk_attention_fwd_masked_bf16": (c_i32, [c_vp] * 6 + [c_i32] * 3 + [c_i64] * 4 + [c_f32, c_vp]),
+    "fk_attention_fwd_masked_f32_debug": (c_i32, [c_vp] * 5 + [c_i32] * 3 + [c_i64] * 4 + [c_f32, c_vp]),
+    "fk_attention_bwd_masked_bf16": (c_i32, [ctypes.POINTER(AttnView)] * 4 + [c_vp, c_vp] + [ctypes.POINTER(AttnView)] * 3 + [c_vp] + [c_i32] * 3 + [c_f32, c_i32, c_vp]),
     "fk_attention_fwd_lse_bf16": (c_i32, [c_vp] * 5 + [c_i32] * 3 + [c_i64] * 4 + [c_f32, c_vp]),
     "fk_attention_bwd_bf16": (c_i32, [ctypes.POINTER(AttnView)] * 4 + [c_vp, c_vp] + [ctypes.POINTER(AttnView)] * 3 + [c_i32] * 3 + [c_f32, c_vp]),
     "fk_attention_bwd_ws_bf16": (c_i32, [ctypes.POINTER(AttnView)] * 4 + [c_vp, c_vp] + [ctypes.POINTER(AttnView)] * 3 + [c_i32] * 3 + [c_f32, c_vp, c_i64, c_i32, c_i32, c_vp]),

@@ -575,12 +575,33 @@ def attention_set_split(mode):
     _set_launch(attn_grid={0: -1, 1: 0}.get(mode, mode))
 
 
-def attention(q, k, v, out, scale=None, lse=None):
+def pack_key_mask(mask):
+    """Key-padding mask of the attention kernels (fk_pack_key_mask): bool / 0-1 ``mask`` [B, S], True = valid key, ->
+    int64 [B, ceil(S / 64)]; bit j of word (b, t) is key 64 t + j of sample b (bits at positions >= S are 0).  Every sample
+    needs at least one valid key, and the K / V rows of masked keys must be finite (fk.h has the precondition)."""
+    _need_cuda(mask)
+    if mask.dim() != 2:
+        raise ValueError("pack_key_mask takes a [B, S] mask")
+    m = (mask != 0).to(torch.uint8).contiguous()
+    B, S = m.shape
+    out = torch.empty((B, (S + 63) // 64), device=m.device, dtype=torch.int64)
+    libfk.check(libfk.load().fk_pack_key_mask(_ptr(m), m.stride(0), B, S, _ptr(out), _stream()), "fk_pack_key_mask")
+    return out
+
+
+def _check_key_mask(key_mask, B, S):
+    if key_mask.dtype != torch.int64 or key_mask.shape != (B, (S + 63) // 64) or not key_mask.is_contiguous():
+        raise ValueError(f"key_mask must be the contiguous int64 [{B}, {(S + 63) // 64}] tensor pack_key_mask gives")
+
+
+def attention(q, k, v, out, scale=None, lse=None, key_mask=None):
     """out[b, s, h*128:(h+1)*128] = softmax(q k^T * scale) v.
 
     q, k: [B,H,S,128] contiguous; v: [B,S,H*128] view with contiguous last dim (e.g. qkv[:, :, 2D:]);
-    out: [B,S,>=H*128] view; lse: optional fp32 [B,H,S] (log2 domain, for :func:`attention_bwd`)."""
-    _need_cuda(q, k, v, out, lse)
+    out: [B,S,>=H*128] view; lse: optional fp32 [B,H,S] (log2 domain, for :func:`attention_bwd`);
+    key_mask: optional :func:`pack_key_mask` tensor -- only valid keys take part (fk_attention_fwd_masked_bf16: the 8-wave
+    kernel on the plain grid)."""
+    _need_cuda(q, k, v, out, lse, key_mask)
     B, H, S, hd = q.shape
     if hd != 128:
         raise ValueError("head_dim must be 128")
@@ -590,6 +611,12 @@ def attention(q, k, v, out, scale=None, lse=None):
         raise ValueError("lse must be a contiguous fp32 [B,H,S] tensor")
     if scale is None:
         scale = hd ** -0.5
+    if key_mask is not None:
+        _check_key_mask(key_mask, B, S)
+        libfk.check(libfk.load().fk_attention_fwd_masked_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(key_mask), B, H, S,
+                                                             v.stride(1), v.stride(0), out.stride(1), out.stride(0), scale,
+                                                             _stream()), "fk_attention_fwd_masked_bf16")
+        return out
     ws = attention_workspace(q.device)
     libfk.check(libfk.load().fk_attention_fwd_ws_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, H, S, v.stride(1),
                                                      v.stride(0), out.stride(1), out.stride(0), scale, _ptr(ws), ws.numel(),
@@ -626,13 +653,21 @@ def attention_mxfp8(q, k, v, out, out_b=None, split=0, scale=None, lse=None):
     return out if out_b is None else (out, out_b)
 
 
-def attention_f32_debug(q, k, v, scale=None):
-    """Parity build of :func:`attention` (fk_attention_fwd_f32_debug): fp32 [B, S, H*128] output, P as hi + lo bf16."""
-    _need_cuda(q, k, v)
+def attention_f32_debug(q, k, v, scale=None, key_mask=None):
+    """Parity build of :func:`attention` (fk_attention_fwd_f32_debug): fp32 [B, S, H*128] output, P as hi + lo bf16;
+    with ``key_mask`` (:func:`pack_key_mask`) fk_attention_fwd_masked_f32_debug."""
+    _need_cuda(q, k, v, key_mask)
     B, H, S, hd = q.shape
     if hd != 128 or v.dim() != 3 or v.shape[-1] != H * 128 or v.stride(2) != 1:
         raise ValueError("q, k: [B,H,S,128]; v: [B,S,H*128] view with a contiguous last dimension")
     out = torch.empty((B, S, H * 128), device=q.device, dtype=torch.float32)
+    if key_mask is not None:
+        _check_key_mask(key_mask, B, S)
+        libfk.check(libfk.load().fk_attention_fwd_masked_f32_debug(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(key_mask), B, H, S,
+                                                                  v.stride(1), v.stride(0), out.stride(1), out.stride(0),
+                                                                  hd ** -0.5 if scale is None else scale, _stream()),
+                    "fk_attention_fwd_masked_f32_debug")
+        return out
     libfk.check(libfk.load().fk_attention_fwd_f32_debug(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, S, v.stride(1),
                                                        v.stride(0), out.stride(1), out.stride(0),
                                                        hd ** -0.5 if scale is None else scale, _stream()),
@@ -852,11 +887,11 @@ def attn_view(t, head_major):
     return v
 
 
-def attention_lse(q, k, v, out, lse, scale=None):
+def attention_lse(q, k, v, out, lse, scale=None, key_mask=None):
     """:func:`attention` that also writes lse [B,H,S] fp32 (log2 domain) for :func:`attention_bwd`."""
     if lse is None:
         raise ValueError("attention_lse needs an lse tensor")
-    return attention(q, k, v, out, scale=scale, lse=lse)
+    return attention(q, k, v, out, scale=scale, lse=lse, key_mask=key_mask)
 
 
 def rowdot(a, c, heads, out=None):
@@ -877,13 +912,21 @@ def attention_bwd_set_mode(mode):
     _set_launch(attn_bwd_passes=0 if int(mode) else 3)
 
 
-def attention_bwd(q, k, v, dout, lse, dsum, dq, dk, dv, scale=None):
-    """dq, dk [B,H,S,128] and dv ([B,S,H*128] view) of softmax(q k^T scale) v given dout ([B,S,H*128] view), lse, dsum."""
-    _need_cuda(q, k, v, dout, lse, dsum, dq, dk, dv)
+def attention_bwd(q, k, v, dout, lse, dsum, dq, dk, dv, scale=None, key_mask=None):
+    """dq, dk [B,H,S,128] and dv ([B,S,H*128] view) of softmax(q k^T scale) v given dout ([B,S,H*128] view), lse, dsum.
+    key_mask: the :func:`pack_key_mask` tensor the forward ran with (fk_attention_bwd_masked_bf16: plain grids; dk / dv rows
+    of masked keys are written as zeros)."""
+    _need_cuda(q, k, v, dout, lse, dsum, dq, dk, dv, key_mask)
     B, H, S, hd = q.shape
     views = [attn_view(q, True), attn_view(k, True), attn_view(v, False), attn_view(dout, False),
              attn_view(dq, True), attn_view(dk, True), attn_view(dv, False)]
     r = [ctypes.byref(x) for x in views]
+    if key_mask is not None:
+        _check_key_mask(key_mask, B, S)
+        libfk.check(libfk.load().fk_attention_bwd_masked_bf16(r[0], r[1], r[2], r[3], _ptr(lse), _ptr(dsum), r[4], r[5], r[6],
+                                                             _ptr(key_mask), B, H, S, hd ** -0.5 if scale is None else scale,
+                                                             LAUNCH.attn_bwd_passes, _stream()), "fk_attention_bwd_masked_bf16")
+        return
     ws = attention_workspace(q.device)      # the forward's stream-K workspace: the dQ pass uses the same scheme
     libfk.check(libfk.load().fk_attention_bwd_ws_bf16(r[0], r[1], r[2], r[3], _ptr(lse), _ptr(dsum), r[4], r[5], r[6], B, H, S,
                                                      hd ** -0.5 if scale is None else scale, _ptr(ws), ws.numel(), LAUNCH.attn_grid,

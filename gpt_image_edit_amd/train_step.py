@@ -14,9 +14,14 @@ With ``projector=`` the ``denoise_projector`` trains along (it is in the referen
 ``HipDenoiseProjector.forward_train``, the optional T5 ``prefix_prompt_embeds`` are appended as the reference's
 ``UnivaDenoiseTower.forward`` does (``modeling_univa_denoise_tower.py:62-70``), and the gradient of ``prompt_embeds``
 that the MMDiT backward returns is carried through both Linears.  Its parameters appear as ``denoise_projector.*``.
-The reference builds a ``joint_attention_kwargs['attention_mask']`` for padded multi-resolution batches
-(``train_denoiser.py:907-916``) but ``UnivaDenoiseTower.forward`` pops it without passing it on
-(``modeling_univa_denoise_tower.py:77``), so no mask ever reaches the attention: there is none here either.
+For padded multi-resolution batches the reference pads every latent to the batch's maximum size, max-pools the ones /
+zeros map to token resolution and passes it as ``joint_attention_kwargs['attention_mask']`` (``train_denoiser.py:907-916``);
+``UnivaDenoiseTower.forward`` then pops it without passing it on (``modeling_univa_denoise_tower.py:77``; the code that would
+have joined it with the text mask is commented out, ``:77-99``), so in the reference no mask ever reaches the attention and
+the padding tokens act as keys of every real token -- a bug, not a specification.  Here ``forward_backward(...,
+attention_mask=...)`` hands the mask to the attention kernels as a key-padding mask (text keys always valid, broadcast over
+heads and queries; ``HipFluxTransformer2DModel.forward`` has the forms).  Without ``attention_mask``, ``weight_mask`` weighs
+the loss only and the attention runs unmasked, as before.
 """
 import torch
 
@@ -117,14 +122,17 @@ class DenoiserTrainStep:
 
     @torch.no_grad()
     def forward_backward(self, model_input, cond_latents, noise, sigmas, prompt_embeds=None, pooled=None, guidance_scale=1.0,
-                         vlm_hidden=None, prefix_prompt_embeds=None, weighting=None, area_mask_weights=None, weight_mask=None):
+                         vlm_hidden=None, prefix_prompt_embeds=None, weighting=None, area_mask_weights=None, weight_mask=None,
+                         attention_mask=None):
         """(loss fp64 [1], grads, d_prompt_embeds) for one batch of equally sized samples; model_input / noise fp32
         [B,16,h,w] (VAE latents already shifted and scaled), cond_latents the same or None, sigmas fp32 [B].
         Either ``prompt_embeds`` (projector frozen / absent) or ``vlm_hidden`` [B,L,3584] (+ optional T5 prefix).
         The loss as the stage-2 config sets it up (``mask_weight_type: 'log'``; train_denoiser.py:1106-1166): ``weighting``
         fp32 [B] (``compute_loss_weighting_for_sd3`` / ``sigmas_as_weight``; None = ones), ``area_mask_weights`` [B,1,H,W]
         (the dataset's per-pixel area weights), ``weight_mask`` [B,1,H,W] (1 inside a padded sample's true extent; with it
-        the sum is divided by ``weight_mask.sum() * C`` instead of the element count)."""
+        the sum is divided by ``weight_mask.sum() * C`` instead of the element count).  ``attention_mask``: bool / 0-1
+        [B, S_img] or [B, C, S_img] over the image tokens (target tokens, then condition tokens), non-zero = a real token
+        -- the attention then runs under that key mask; None: unmasked."""
         n_proj = 0
         if vlm_hidden is not None:
             if self.projector is None or prompt_embeds is not None:
@@ -136,8 +144,11 @@ class DenoiserTrainStep:
         elif prompt_embeds is None:
             raise ValueError("one of prompt_embeds / vlm_hidden is required")
         inp, S_tgt = self.prepare_inputs(model_input, cond_latents, noise, sigmas, prompt_embeds, pooled, guidance_scale)
+        key_mask = None
+        if attention_mask is not None:
+            key_mask = self.model._joint_key_mask(attention_mask, inp["hidden_states"], inp["encoder_hidden_states"])
         pred = self.bw.forward(inp["hidden_states"], inp["encoder_hidden_states"], inp["pooled_projections"], inp["timestep"],
-                               inp["img_ids"], inp["txt_ids"], inp["guidance"])
+                               inp["img_ids"], inp["txt_ids"], inp["guidance"], key_mask=key_mask)
         B, _, h, w = model_input.shape
         dev = pred.device
         if weighting is not None:

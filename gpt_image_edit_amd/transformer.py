@@ -424,27 +424,53 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         training forward), its backward ``FluxBackward.backward`` -- so the reference's ``accelerator.backward(loss)``
         (``train_denoiser.py:1172``) fills ``.grad`` of exactly the parameters it un-froze and any stock optimiser
         can step them.  Otherwise (inference) nothing is recorded.  The training path computes in bf16 whatever
-        ``weight_format`` says: MXFP8 is an inference format."""
+        ``weight_format`` says: MXFP8 is an inference format.
+
+        ``joint_attention_kwargs["attention_mask"]`` (padded batches of samples of different sizes, as the reference's
+        training loop builds them at ``train_denoiser.py:907-916``): bool or 0/1, ``[B, S_img]`` or ``[B, C, S_img]`` (the
+        max-pooled latent map flattened; reduced over ``C`` with ``any``), non-zero = a real image token.  It is a KEY
+        mask, broadcast over heads and queries, with the text keys always valid: padding tokens take no part in any real
+        token's attention.  With a mask the forward takes the per-launch bf16 route with the masked attention kernels;
+        ``weight_format="mxfp8"`` with a mask is a ``ValueError``.  Without a mask nothing changes."""
         if not hidden_states.is_cuda:
             raise RuntimeError("HipFluxTransformer2DModel needs GPU tensors: there is no CPU fallback")
+        key_mask = None
         if joint_attention_kwargs and joint_attention_kwargs.get("attention_mask") is not None:
-            raise NotImplementedError("attention_mask (padded multi-resolution training batches, train_denoiser.py:1086-1091) "
-                                      "is not supported: batch equally sized samples (cfg 5 trains bs 1 per GPU)")
+            key_mask = self._joint_key_mask(joint_attention_kwargs["attention_mask"], hidden_states, encoder_hidden_states)
         if torch.is_grad_enabled():
             names = self.grad_parameter_names()
             if names or (encoder_hidden_states is not None and encoder_hidden_states.requires_grad):
                 sample = self._forward_train(names, hidden_states, encoder_hidden_states, pooled_projections, timestep,
-                                             img_ids, txt_ids, guidance)
+                                             img_ids, txt_ids, guidance, key_mask)
                 return SimpleNamespace(sample=sample) if return_dict else (sample,)
         return self._forward_infer(hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids,
-                                   guidance, return_dict)
+                                   guidance, return_dict, key_mask)
+
+    def _joint_key_mask(self, mask, hidden_states, encoder_hidden_states):
+        """The packed key mask of the joint sequence, ``[ones(B, S_txt) | mask]`` (``ops.pack_key_mask``), built once per
+        forward.  The text keys are always valid and ``S_txt >= 1`` is required, so every sample has a valid key: the
+        attention kernels' precondition holds by construction."""
+        B, S_img = hidden_states.shape[0], hidden_states.shape[1]
+        S_txt = 0 if encoder_hidden_states is None else encoder_hidden_states.shape[1]
+        if not torch.is_tensor(mask) or mask.dim() not in (2, 3) or mask.shape[0] != B or mask.shape[-1] != S_img:
+            raise ValueError(f"attention_mask must be a [B, S_img] = [{B}, {S_img}] or [B, C, S_img] tensor, got "
+                             f"{tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
+        if S_txt < 1:
+            raise ValueError("attention_mask needs a text stream (S_txt >= 1): the text keys are what keeps every sample's key set non-empty")
+        if self.weight_format == "mxfp8":
+            raise ValueError('attention_mask is not available with weight_format="mxfp8": the masked attention runs on the bf16 route')
+        m = mask.to(hidden_states.device) != 0
+        if m.dim() == 3:
+            m = m.any(dim=1)
+        joint = torch.cat([torch.ones((B, S_txt), device=m.device, dtype=torch.bool), m], dim=1)
+        return ops.pack_key_mask(joint)
 
     def grad_parameter_names(self):
         """Names of the parameters with ``requires_grad`` (what the reference's selection loop un-froze)."""
         return [n for n, prm in self._pmap.items() if prm.requires_grad]
 
     def _forward_train(self, names, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids,
-                       guidance):
+                       guidance, key_mask=None):
         from .backward import FluxBackward, FluxTrainFunction
         key = tuple(names)
         bw = self.__dict__.get("_autograd_bw")
@@ -456,11 +482,11 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         bw.store_activations = False if self.gradient_checkpointing else "auto"
         params = [self._pmap[n] for n in names]
         return FluxTrainFunction.apply(bw, names, hidden_states, encoder_hidden_states, pooled_projections, timestep,
-                                       img_ids, txt_ids, guidance, *params)
+                                       img_ids, txt_ids, guidance, key_mask, *params)
 
     @torch.no_grad()
     def _forward_infer(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids,
-                       guidance, return_dict):
+                       guidance, return_dict, key_mask=None):
         c, D, H = self.config, self.inner_dim, self.num_heads
         pk = self.packed()
         B, S_img, _ = hidden_states.shape
@@ -492,7 +518,9 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
 
         block_api = BLOCK_API if (FUSE_QKV and not MLP_FIRST and not (OVERLAP_MLP and (OVERLAP_MLP != "auto" or self._overlap_pays(B, ws.S)))
                                   and S_txt > 0) else 0
-        if pk.format == "mxfp8":
+        if key_mask is not None:   # masked attention: per-launch bf16 route, no block-level entry point, no side stream
+            self._blocks_by_kernel_calls(ws, pk, mod, cos, sin, cs, B, S_txt, key_mask)
+        elif pk.format == "mxfp8":
             if ws.mxq is None:
                 # quantized activations: one launch's operand, at most B * S rows of K = 5D -- and in front of it, in the fused
                 # schedule, the LN output n8 (D per row) that stays live while the block's consumer operand is filled
@@ -522,9 +550,9 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
             return (sample,)
         return SimpleNamespace(sample=sample)
 
-    def _blocks_by_kernel_calls(self, ws, pk, mod, cos, sin, cs, B, S_txt):
+    def _blocks_by_kernel_calls(self, ws, pk, mod, cos, sin, cs, B, S_txt, key_mask=None):
         """The 19 + 38 blocks as one ctypes call per kernel launch (FK_BLOCK_API=0; also the route of the A/B switches
-        FK_FUSE_QKV=0, FK_MLP_FIRST=1, FK_OVERLAP_MLP)."""
+        FK_FUSE_QKV=0, FK_MLP_FIRST=1, FK_OVERLAP_MLP, and of a forward with an attention mask: ``key_mask``, packed)."""
         P, D = self.p, self.inner_dim
         s, n = ws.s, ws.n
         h, cx = s[:, S_txt:], s[:, :S_txt]
@@ -552,7 +580,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
                                   dict(a=n_txt, w=blk.wqkv_txt, bias=blk.bqkv_txt, out=ws.qkv[:, :S_txt])])
                 ops.qkv_post(ws.qkv, ws.q, ws.k, P(p + "attn.norm_q.weight"), P(p + "attn.norm_k.weight"),
                              P(p + "attn.norm_added_q.weight"), P(p + "attn.norm_added_k.weight"), cos, sin, S_txt)
-            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.o)
+            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.o, key_mask=key_mask)
             ops.gemm_grouped([dict(a=ws.o[:, S_txt:], w=P(p + "attn.to_out.0.weight"), bias=P(p + "attn.to_out.0.bias"),
                                    out=h, res=h, gate=chunk(mi, 2)),
                               dict(a=ws.o[:, :S_txt], w=P(p + "attn.to_add_out.weight"), bias=P(p + "attn.to_add_out.bias"),
@@ -573,7 +601,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         # attention's last rounds leave idle; one event pair per block, same kernels, same numbers.  Measured (one box,
         # images/s without / with): S = 2560 0.977 / 0.959, S = 5632 0.355 / 0.370, S = 8704 0.238 / 0.244 -- it pays
         # where the attention grid wastes a good part of its last round, and costs where one round holds everything.
-        use_side = self._overlap_pays(B, ws.S) if OVERLAP_MLP == "auto" else OVERLAP_MLP
+        use_side = key_mask is None and (self._overlap_pays(B, ws.S) if OVERLAP_MLP == "auto" else OVERLAP_MLP)
         side = self._side_stream() if use_side else None
         if side is not None:
             main = torch.cuda.current_stream()
@@ -601,7 +629,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
                 ops.gemm(n, blk.wqkv, blk.bqkv, out=ws.qkv)
                 ops.qkv_post(ws.qkv, ws.q, ws.k, P(p + "attn.norm_q.weight"), P(p + "attn.norm_k.weight"), None, None,
                              cos, sin, 0)
-            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.cat[:, :, :D])
+            ops.attention(ws.q, ws.k, ws.qkv[:, :, 2 * D:], ws.cat[:, :, :D], key_mask=key_mask)
             if side is not None:
                 main.wait_event(ev_mlp)
             elif not MLP_FIRST:

@@ -300,6 +300,30 @@ int fk_attention_fwd_f32_debug(const void* q, const void* k, const void* v, floa
                                int32_t S, int64_t v_ld, int64_t v_batch_stride, int64_t o_ld,
                                int64_t o_batch_stride, float scale, fk_stream_t stream);
 
+/* ---- key-padding mask (padded batches of samples of different sizes) ---------------------------------------------------------
+ * kmask: caller-owned device pointer, uint64 [B, ceil(S / 64)], 8-byte aligned.  Bit j of word (b, t) is 1 when key 64 t + j of
+ * sample b is VALID; bits at positions >= S are ignored.  One word per 64-key tile of the attention kernels (forward and
+ * backward): a wave classifies a tile with one uniform 8-byte load.  The mask is a KEY mask, broadcast over heads and queries
+ * (F.scaled_dot_product_attention(attn_mask = mask[:, None, None, :])); every query row, masked token or not, is an ordinary row.
+ * PRECONDITION (not checked: it would take a device synchronisation): every sample has at least one valid key, and the K / V
+ * rows of masked keys are finite (in the model they come from zero-padded latents).  A sample without a valid key gets NaN
+ * rows; a non-finite masked K / V row may reach the output as NaN.  Nothing is read or written out of bounds either way.
+ *
+ * fk_pack_key_mask: out[b, t] from a byte / bool mask (non-zero = valid), key s of sample b at mask[b * batch_stride + s]. */
+int fk_pack_key_mask(const uint8_t* mask, int64_t batch_stride, int32_t B, int32_t S, uint64_t* out, fk_stream_t stream);
+/* fk_attention_fwd_lse_bf16 over the valid keys only (lse may be NULL; otherwise the log2-domain log-sum-exp over the valid
+ * keys).  The 8-wave kernel on the plain grid, one workgroup per (b, h, 256-row block): no workspace, no `grid`.  A tile whose
+ * word is all ones runs the unmasked tile body, an all-zero tile is taken from the K / V ring and not computed, any other gets
+ * the per-key select that the ragged last tile has always had (score -1e30, numerator exactly 0).  An all-ones mask therefore
+ * gives the bits of fk_attention_fwd_ws_bf16(grid = -1), a prefix mask [0, L) those of a call with S = L. */
+int fk_attention_fwd_masked_bf16(const void* q, const void* k, const void* v, void* o, float* lse, const uint64_t* kmask, int32_t B,
+                                 int32_t H, int32_t S, int64_t v_ld, int64_t v_batch_stride, int64_t o_ld, int64_t o_batch_stride,
+                                 float scale, fk_stream_t stream);
+/* The fp32-output parity form (fk_attention_fwd_f32_debug) with the mask. */
+int fk_attention_fwd_masked_f32_debug(const void* q, const void* k, const void* v, float* o, const uint64_t* kmask, int32_t B,
+                                      int32_t H, int32_t S, int64_t v_ld, int64_t v_batch_stride, int64_t o_ld,
+                                      int64_t o_batch_stride, float scale, fk_stream_t stream);
+
 /* ---- block-level entry points ------------------------------------------------------------------------
  * ONE call enqueues every launch of a FluxTransformerBlock / FluxSingleTransformerBlock (diffusers 0.32.2 as the reference
  * reaches it at flux_pipeline.py:1067-1077), or of all blocks of a forward, on the caller's stream -- the same launches, in
@@ -429,6 +453,15 @@ int fk_attention_bwd_ws_bf16(const fk_attn_view* q, const fk_attn_view* k, const
  * 0 or 2 = two launches, the dQ pass and one pass in which wave pairs produce dK and dV together (7 tile products, default),
  * 3 = three launches (dQ, dV, dK: 8 tile products).  dQ and dV are the same bit for bit in both; dK differs in the last bf16
  * bit (the paired pass forms p (dP - D) from the bf16 p that also enters dV, the three-pass form from the fp32 p). */
+
+/* fk_attention_bwd_bf16 under the key-padding mask of fk_attention_fwd_masked_bf16 (same format, same precondition; lse from
+ * the masked forward).  Plain grids; passes as above (0 / 2 or 3).  dQ pass: masked keys weigh 0, all-masked key tiles are not
+ * computed.  dK / dV: the rows of masked keys are WRITTEN as exact zeros, and a key block without a valid key streams nothing.
+ * Query rows of masked tokens are ordinary rows (in the model their dout is zero: their loss weight is). */
+int fk_attention_bwd_masked_bf16(const fk_attn_view* q, const fk_attn_view* k, const fk_attn_view* v, const fk_attn_view* dout,
+                                 const float* lse, const float* dsum, const fk_attn_view* dq, const fk_attn_view* dk,
+                                 const fk_attn_view* dv, const uint64_t* kmask, int32_t B, int32_t H, int32_t S, float scale,
+                                 int32_t passes, fk_stream_t stream);
 
 /* fp32 elements of workspace `ws` the reductions below need (per-workgroup partial sums, fixed-order finalisation). */
 int64_t fk_bwd_ws_floats(void);
