@@ -56,3 +56,12 @@ def preferred_condition_size(image_height, image_width, multiple_of, auto_resize
         aspect = image_width / image_height
         _, image_width, image_height = min((abs(aspect - w / h), w, h) for w, h in PREFERRED_KONTEXT_RESOLUTIONS)
     return image_height // multiple_of * multiple_of, image_width // multiple_of * multiple_of
+
+
+def strength_t_start(num_inference_steps, strength):
+    """First step of the ``num_inference_steps``-step schedule an edit of the given ``strength`` runs (diffusers'
+    ``get_timesteps``): 1.0 = all of them, from pure noise; smaller values start later, from the re-noised picture."""
+    if not 0.0 < float(strength) <= 1.0:
+        raise ValueError(f"The value of strength should be in (0, 1] but is {strength}")
+    init_timestep = min(num_inference_steps * float(strength), num_inference_steps)
+    return int(max(num_inference_steps - init_timestep, 0))

@@ -726,6 +726,63 @@ def euler_step(x, v, s_tgt, dsigma):
     return x
 
 
+def _token_rows(name, t, B, s_tgt, C):
+    if t.dtype != BF16 or t.dim() != 3 or t.shape[0] != B or t.shape[1] < s_tgt or t.shape[2] != C or \
+            t.stride(2) != 1 or t.stride(1) != C:
+        raise ValueError(f"{name} must be bf16 [{B}, >= {s_tgt}, {C}] with contiguous rows, got {tuple(t.shape)} {t.dtype}")
+
+
+def euler_inpaint_step(x, v, s_tgt, dsigma, sigma_next, x0, noise, mask=None):
+    """In place on x[:, :s_tgt]: the Euler update where ``mask`` is 1, the preserved picture ``x0`` re-noised to
+    ``sigma_next`` with the call's ``noise`` where it is 0 (include/fk.h: fk_euler_inpaint_step_bf16).  ``mask``: the compact
+    [1 or B, s_tgt, 4] bf16 mask of :func:`pack_inpaint_mask`; None = ones, the values of :func:`euler_step`."""
+    _need_cuda(x, v, x0, noise, mask)
+    B, _, C = x.shape
+    for name, t in (("x", x), ("v", v)) + ((("x0", x0), ("noise", noise)) if mask is not None else ()):
+        _token_rows(name, t, B, s_tgt, C)
+    m_bs = 0
+    if mask is not None:
+        if mask.dtype != BF16 or mask.dim() != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (s_tgt, 4) \
+                or not mask.is_contiguous():
+            raise ValueError(f"mask must be contiguous bf16 [1 or {B}, {s_tgt}, 4], got {tuple(mask.shape)} {mask.dtype}")
+        m_bs = mask.stride(0) if mask.shape[0] == B and B > 1 else 0
+    libfk.check(libfk.load().fk_euler_inpaint_step_bf16(
+        _ptr(x), x.stride(0), _ptr(v), v.stride(0), _ptr(x0), 0 if x0 is None else x0.stride(0), _ptr(noise),
+        0 if noise is None else noise.stride(0), _ptr(mask), m_bs, B, s_tgt, C, float(dsigma), float(sigma_next),
+        _stream()), "fk_euler_inpaint_step_bf16")
+    return x
+
+
+def scale_noise(x0, noise, sigma, out=None):
+    """bf16(bf16(sigma) * noise) + bf16(1 - bf16(sigma)) * x0 with one rounding per bf16 tensor op
+    (FlowMatchEulerDiscreteScheduler.scale_noise): the start tokens of an edit that begins inside the schedule."""
+    _need_cuda(x0, noise, out)
+    B, S, C = x0.shape
+    if out is None:
+        out = torch.empty((B, S, C), device=x0.device, dtype=BF16)
+    for name, t in (("x0", x0), ("noise", noise), ("out", out)):
+        _token_rows(name, t, B, S, C)
+    libfk.check(libfk.load().fk_scale_noise_bf16(_ptr(x0), x0.stride(0), _ptr(noise), noise.stride(0), _ptr(out),
+                                                 out.stride(0), B, S, C, float(sigma), _stream()), "fk_scale_noise_bf16")
+    return out
+
+
+def pack_inpaint_mask(mask, h_lat, w_lat):
+    """[Bm, 1, Hm, Wm] mask in [0, 1] (1 = repaint) -> the compact [Bm, (h_lat/2) * (w_lat/2), 4] bf16 token mask of
+    fk_euler_inpaint_step_bf16: binarised at 0.5 (>= 0.5 -> 1), nearest-resized to the latent size, packed 2 x 2 like
+    ``_pack_latents`` packs one channel -- element k of a token's four is the sub-pixel every latent element j with
+    j % 4 == k lies on.  Host-side torch on a few KB, once per call; runs on any device."""
+    if not torch.is_tensor(mask) or mask.dim() != 4 or mask.shape[1] != 1:
+        raise ValueError("mask must be a [B, 1, H, W] tensor")
+    if h_lat % 2 or w_lat % 2:
+        raise ValueError("the latent size must be even (2 x 2 packing)")
+    m = (mask.to(torch.float32) >= 0.5).to(torch.float32)
+    if tuple(m.shape[2:]) != (h_lat, w_lat):
+        m = torch.nn.functional.interpolate(m, size=(h_lat, w_lat), mode="nearest")
+    m = m.view(m.shape[0], h_lat // 2, 2, w_lat // 2, 2).permute(0, 1, 3, 2, 4)
+    return m.reshape(m.shape[0], (h_lat // 2) * (w_lat // 2), 4).to(BF16).contiguous()
+
+
 def transpose(src, dst):
     """dst[b, c, r] = src[b, r, c] for 3-D views with contiguous last dims."""
     _need_cuda(src, dst)

@@ -6,7 +6,8 @@ Mirrors the call surface and semantics of ``univa/utils/flux_pipeline.py::FluxKo
 same argument names and defaults, the ``max_area`` / preferred-resolution quirks, the same
 latent packing, ids, sigma schedule, 28-step Euler loop and VAE decode -- but the loop body is
 
-    transformer (HIP MMDiT)  ->  fused slice + Euler update (one HIP kernel, in place)
+    transformer (HIP MMDiT)  ->  fused slice + Euler update (one HIP kernel, in place; for a masked edit the same launch
+                                 also puts the re-noised preserved picture back outside the mask)
 
 over ONE persistent token buffer [B, S_tgt + S_cond, 64] (target tokens first, condition tokens after:
 the reference's per-step ``torch.cat([latents, image_latents], dim=1)`` disappears), with all per-step
@@ -200,6 +201,61 @@ class FluxKontextPipeline:
             latents = latents.to(device=device, dtype=dtype)
         return latents, image_latents, latent_ids, image_ids
 
+    def _prepare_mask(self, mask_image, batch_size, height, width, device):
+        """``mask_image`` (float [1 or B, 1, Hm, Wm] in [0, 1]; uint8 tensor / numpy / PIL greyscale, 255 = repaint) -> the
+        compact token mask [1 or B, S_tgt, 4] of the fused step: binarised at 0.5, nearest-resized to the latent size."""
+        m = mask_image
+        if hasattr(m, "convert"):
+            m = [m]
+        if isinstance(m, (list, tuple)) and m and hasattr(m[0], "convert"):
+            arrs = [np.asarray(im.convert("L"), dtype=np.uint8) for im in m]
+            if any(a.shape != arrs[0].shape for a in arrs):
+                raise ValueError("mask images must share one size")
+            m = np.stack(arrs)
+        if isinstance(m, np.ndarray):
+            m = torch.from_numpy(np.ascontiguousarray(m))
+        if not torch.is_tensor(m):
+            raise ValueError("pass `mask_image` as a [1 or B, 1, H, W] tensor in [0, 1], or as uint8 / PIL greyscale")
+        m = m.float() / 255.0 if m.dtype == torch.uint8 else m.float()
+        if m.dim() == 2:
+            m = m[None]
+        if m.dim() == 3:
+            m = m[:, None]
+        if m.dim() != 4 or m.shape[1] != 1:
+            raise ValueError(f"`mask_image` must be [1 or B, 1, H, W], got {tuple(m.shape)}")
+        if m.shape[0] not in (1, batch_size):
+            raise ValueError(f"`mask_image` has batch {m.shape[0]}: must be 1 or the batch size {batch_size}")
+        sf = self.vae_scale_factor * 2
+        return ops.pack_inpaint_mask(m, 2 * (int(height) // sf), 2 * (int(width) // sf)).to(device)
+
+    def _encode_init_image(self, init_image, batch_size, num_channels_latents, height, width, device):
+        """Packed latents [B, S_tgt, 64] of the picture a masked edit preserves, at the target size: the condition image's
+        own routes (uint8 pixels through the fused gather, float tensors through resize + preprocess) without the
+        preferred-resolution snap; pre-encoded latents must already have the target's latent size."""
+        h_lat, w_lat = height // self.vae_scale_factor, width // self.vae_scale_factor
+        u8 = image_processor.as_uint8_nhwc(init_image)
+        if u8 is not None:
+            px = image_processor.pixels_to_latent_input(u8, height, width, device)
+            lat = self._encode_vae_image(px.tensor, nhwc=True)
+        elif isinstance(init_image, torch.Tensor) and init_image.dim() == 4 and init_image.size(1) == self.latent_channels:
+            lat = init_image.to(device=device, dtype=BF16)
+        elif isinstance(init_image, torch.Tensor) and init_image.dim() == 4:
+            img = init_image
+            if tuple(img.shape[2:]) != (height, width):
+                img = self.image_processor.resize(img.float(), height, width)
+            lat = self._encode_vae_image(self.image_processor.preprocess(img, height, width).to(device=device))
+        else:
+            raise NotImplementedError("pass the picture to preserve as a [N,3,H,W] tensor in [-1,1], as uint8 pixels "
+                                      "(PIL / numpy / uint8 tensor [N,H,W,3]) or as latents [N,16,h,w]")
+        if tuple(lat.shape[2:]) != (h_lat, w_lat):
+            raise ValueError(f"the preserved picture's latents are {tuple(lat.shape[2:])}, the target's ({h_lat}, {w_lat})")
+        n = lat.shape[0]
+        if batch_size > n and batch_size % n == 0:
+            lat = torch.cat([lat] * (batch_size // n), dim=0)
+        elif batch_size != n:
+            raise ValueError(f"Cannot duplicate the preserved picture of batch size {n} to batch size {batch_size}.")
+        return self._pack_latents(lat, batch_size, num_channels_latents, h_lat, w_lat).contiguous()
+
     @torch.no_grad()
     def __call__(self, image=None, prompt=None, prompt_2=None, negative_prompt=None, negative_prompt_2=None,
                  true_cfg_scale=1.0, height=None, width=None, num_inference_steps=28, sigmas=None,
@@ -207,8 +263,16 @@ class FluxKontextPipeline:
                  pooled_prompt_embeds=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None,
                  output_type="pil", return_dict=True, joint_attention_kwargs=None, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=("latents",), max_sequence_length=512,
-                 max_area=1024 ** 2, _auto_resize=True):
+                 max_area=1024 ** 2, _auto_resize=True, mask_image=None, strength=1.0, init_image=None):
+        """``mask_image`` / ``strength`` / ``init_image`` (diffusers' ``FluxKontextInpaintPipeline``): repaint only where the
+        mask is 1 and keep ``init_image`` (default: ``image``, resized to the target size) elsewhere; ``strength`` < 1 starts
+        the loop inside the schedule from the re-noised ``init_image`` instead of from noise.  ``image`` stays the Kontext
+        condition.  Without the three the call is the plain edit, launch for launch."""
         device = self.device
+        helpers.strength_t_start(num_inference_steps, strength)     # validates strength before any work
+        inpaint = mask_image is not None or init_image is not None or strength < 1.0
+        if (mask_image is not None or strength < 1.0) and image is None and init_image is None:
+            raise ValueError("`mask_image` / `strength` < 1 need a picture to preserve: pass `image` or `init_image`")
         if prompt is not None and prompt_embeds is not None:
             raise ValueError(f"Cannot forward both `prompt`: {prompt} and `prompt_embeds`: {prompt_embeds}. Please make "
                              "sure to only forward one of the two.")   # :510-514
@@ -258,13 +322,17 @@ class FluxKontextPipeline:
             model_embeds, model_pooled = prompt_embeds, pooled_prompt_embeds
         model_batch = model_embeds.shape[0]
 
+        mask = None if mask_image is None else self._prepare_mask(mask_image, batch_size, height, width, device)
+
         # 3. condition image: preferred-resolution snap + nearest resize (VaeImageProcessor tensor path)
+        image_in, cond_hw = image, None             # cond_hw: pixel size the condition latents stand for
         u8 = image_processor.as_uint8_nhwc(image) if image is not None else None
         if u8 is not None:
             # uint8 pixels: cli.prepare_condition_images + resize + preprocess + .to(bf16) as ONE HIP gather
             ih, iw = self.image_processor.get_default_height_width(u8.permute(0, 3, 1, 2))
             ih, iw = helpers.preferred_condition_size(ih, iw, multiple_of, _auto_resize)
             image = image_processor.pixels_to_latent_input(u8, ih, iw, device)
+            cond_hw = (ih, iw)
         elif image is not None and not (isinstance(image, torch.Tensor) and image.size(1) == self.latent_channels):
             if not isinstance(image, torch.Tensor) or image.dim() != 4:
                 raise NotImplementedError("pass the condition image as a [N,3,H,W] tensor in [-1,1] (cli.py:99-116) "
@@ -273,6 +341,9 @@ class FluxKontextPipeline:
             ih, iw = helpers.preferred_condition_size(ih, iw, multiple_of, _auto_resize)
             image = self.image_processor.resize(image.float(), ih, iw) if (ih, iw) != tuple(image.shape[2:]) else image
             image = self.image_processor.preprocess(image, ih, iw)
+            cond_hw = (ih, iw)
+        elif image is not None:
+            cond_hw = (image.shape[2] * self.vae_scale_factor, image.shape[3] * self.vae_scale_factor)
 
         # 4. latents
         num_channels_latents = self.transformer.config.in_channels // 4
@@ -284,6 +355,15 @@ class FluxKontextPipeline:
             tokens = torch.cat([latents, image_latents], dim=1).contiguous()  # built ONCE, updated in place
         else:
             tokens = latents.contiguous().clone()
+        x0 = noise = None
+        if mask is not None or strength < 1.0:
+            # the preserved picture at the target size: the condition latents when they already are that, else one more encode
+            if init_image is None and cond_hw == (height, width):
+                x0 = image_latents
+            else:
+                x0 = self._encode_init_image(image_in if init_image is None else init_image, batch_size,
+                                             num_channels_latents, height, width, device)
+            noise = latents.contiguous()            # a caller-supplied `latents` serves as the noise, as in diffusers
 
         # 5. timesteps (host float32 arithmetic, like diffusers' numpy path)
         sig = np.linspace(1.0, 1 / num_inference_steps, num_inference_steps) if sigmas is None else sigmas
@@ -291,14 +371,18 @@ class FluxKontextPipeline:
         mu = helpers.calculate_shift(S_tgt, cfg.get("base_image_seq_len", 256), cfg.get("max_image_seq_len", 4096),
                                      cfg.get("base_shift", 0.5), cfg.get("max_shift", 1.15))
         self.scheduler.set_timesteps(sigmas=sig, mu=mu, device="cpu")
-        timesteps = self.scheduler.timesteps
+        t_start = helpers.strength_t_start(len(self.scheduler.timesteps), strength)
+        timesteps = self.scheduler.timesteps[t_start:]
         self._num_timesteps = len(timesteps)
         # `t.expand(B).to(bf16)` then `/ 1000` (flux_pipeline.py:1065,1069): all steps prepared up front
         t_model = (timesteps.to(BF16) / 1000)[:, None].expand(-1, model_batch).contiguous().to(device)
         guidance = None
         if self.transformer.config.guidance_embeds:
             guidance = torch.full([model_batch], guidance_scale, device=device, dtype=torch.float32)
-        self.scheduler.set_begin_index(0)
+        self.scheduler.set_begin_index(t_start)
+        if t_start > 0:                             # start inside the schedule: the picture re-noised to sigma[t_start]
+            ops.scale_noise(x0, noise, float(self.scheduler._sigmas_host[t_start]), out=tokens[:, :S_tgt])
+        steps = range(t_start, t_start + len(timesteps))
         model_tokens = torch.empty((model_batch, *tokens.shape[1:]), device=device, dtype=BF16) if do_true_cfg else tokens
 
         # 6. denoising loop: no allocation, no host sync
@@ -306,7 +390,10 @@ class FluxKontextPipeline:
                             embeds=model_embeds, text_ids=text_ids, latent_ids=latent_ids, S_tgt=S_tgt, batch_size=batch_size,
                             do_true_cfg=do_true_cfg, true_cfg_scale=true_cfg_scale, jak=joint_attention_kwargs or {},
                             geom=(height, width, None if image is None else tuple(image.shape[-2:])),
-                            dsigma=[self.scheduler.dsigma(i) for i in range(len(timesteps))])
+                            dsigma=[self.scheduler.dsigma(i) for i in steps], inpaint=inpaint,
+                            sigma_next=[self.scheduler.sigma_next(i) for i in steps] if inpaint else [],
+                            # without a mask the fused step is the Euler update alone and reads neither x0 nor noise
+                            x0=x0 if mask is not None else None, noise=noise if mask is not None else None, mask=mask)
         if self.use_graph and callback_on_step_end is None and not joint_attention_kwargs and not self._interrupt:
             tokens = self._denoise_graph(L)
         else:
@@ -342,13 +429,16 @@ class FluxKontextPipeline:
                 return_dict=False)[0]
             if L.do_true_cfg:
                 noise_pred = ops.true_cfg(noise_pred[:B], noise_pred[B:], L.true_cfg_scale)
-            ops.euler_step(tokens, noise_pred, L.S_tgt, L.dsigma[i])
+            if L.inpaint:   # Euler update where the mask is 1, the preserved picture at sigma[i+1] where it is 0
+                ops.euler_inpaint_step(tokens, noise_pred, L.S_tgt, L.dsigma[i], L.sigma_next[i], L.x0, L.noise, L.mask)
+            else:
+                ops.euler_step(tokens, noise_pred, L.S_tgt, L.dsigma[i])
             if callback_on_step_end is not None:
                 out = callback_on_step_end(self, i, timesteps[i], {"latents": tokens[:, :L.S_tgt]})
                 if out and "latents" in out:
                     tokens[:, :L.S_tgt].copy_(out["latents"])
 
-    _GRAPH_INPUTS = ("tokens", "t_model", "guidance", "pooled", "embeds", "text_ids", "latent_ids")
+    _GRAPH_INPUTS = ("tokens", "t_model", "guidance", "pooled", "embeds", "text_ids", "latent_ids", "x0", "noise", "mask")
 
     def _denoise_graph(self, L):
         """The same work as ONE graph launch.  The captured kernels read and write fixed buffers, so the call's tensors
@@ -362,7 +452,10 @@ class FluxKontextPipeline:
             self.transformer.packed()
         key = (tuple(L.tokens.shape), tuple(L.embeds.shape), tuple(L.latent_ids.shape), L.geom, L.do_true_cfg,
                float(L.true_cfg_scale), tuple(L.dsigma), L.guidance is None, L.S_tgt,
-               getattr(self.transformer, "_pack_serial", 0), ops.launch_config_epoch())
+               getattr(self.transformer, "_pack_serial", 0), ops.launch_config_epoch(),
+               # masked edits: the preserved picture, the noise and the mask are inputs (a new mask of the same shape replays);
+               # their presence, the mask's batch form and the keep region's noise levels are frozen into the graph
+               L.inpaint, None if L.mask is None else tuple(L.mask.shape), tuple(L.sigma_next))
         cur = torch.cuda.current_stream()
         if self._loop_graph is None or self._loop_graph[0] != key:
             self._loop_graph = None

@@ -3,6 +3,8 @@
 Interface used by ``univa/utils/flux_pipeline.py``: ``config.get(...)`` (:994-999),
 ``set_timesteps(sigmas=, mu=, device=)`` via ``retrieve_timesteps`` (:1000-1006), ``timesteps``,
 ``order``, ``set_begin_index(0)`` (:1052), ``step(noise_pred, t, latents, return_dict=False)[0]`` (:1099).
+Masked edits and ``strength`` (diffusers' inpaint pipeline of this model family) add ``scale_noise`` and a begin index
+other than 0.
 The sigma schedule is host arithmetic in float32 (28 numbers); the update itself is
 ``fk_euler_step_bf16`` with the reference's rounding (bf16(dsigma) * v in bf16, sum in fp32 -> bf16).
 """
@@ -61,11 +63,26 @@ class FlowMatchEulerDiscreteScheduler:
         """sigma[i+1] - sigma[i] in float32, as the reference forms it on the device."""
         return float(np.float32(self._sigmas_host[i + 1]) - np.float32(self._sigmas_host[i]))
 
+    def sigma_next(self, i):
+        """sigma[i+1] in float32: the noise level after step i (0 after the last one), which the keep region of a masked
+        edit is re-noised to."""
+        return float(np.float32(self._sigmas_host[i + 1]))
+
+    def index_for_timestep(self, timestep):
+        idx = (self.timesteps.cpu() == float(timestep)).nonzero()
+        return int(idx[1 if len(idx) > 1 else 0])
+
+    def scale_noise(self, sample, timestep, noise):
+        """sigma * noise + (1 - sigma) * sample at the sigma of ``timestep`` (looked up like ``_init_step_index`` does, or
+        the begin index when one is set), in bf16 with one rounding per tensor op: ``fk_scale_noise_bf16``."""
+        if sample.dtype != torch.bfloat16 or noise.dtype != torch.bfloat16:
+            raise TypeError("the HIP scale_noise works on bf16 latents")
+        i = self.index_for_timestep(timestep) if self._begin_index is None else self._begin_index
+        return ops.scale_noise(sample.contiguous(), noise.contiguous(), float(self._sigmas_host[i]))
+
     def _init_step_index(self, timestep):
         if self._begin_index is None:
-            t = float(timestep)
-            idx = (self.timesteps.cpu() == t).nonzero()
-            self._step_index = int(idx[1 if len(idx) > 1 else 0])
+            self._step_index = self.index_for_timestep(timestep)
         else:
             self._step_index = self._begin_index
 

@@ -98,6 +98,18 @@ def prepare_condition_pixels(image_paths):
     return torch.from_numpy(np.stack(arrs))
 
 
+def inpaint_kwargs(args):
+    """``--mask`` / ``--strength`` as the pipeline's ``mask_image`` / ``strength`` (nothing when neither is given: the plain
+    edit).  The mask is read as greyscale, white = repaint; the pipeline binarises it at 0.5 and resizes it."""
+    from PIL import Image
+    kw = {}
+    if getattr(args, "mask", None):
+        kw["mask_image"] = Image.open(args.mask).convert("L")
+    if getattr(args, "strength", None) is not None and args.strength != 1.0:
+        kw["strength"] = args.strength
+    return kw
+
+
 def generate_image(pipe, prompt_embeds, pooled_prompt_embeds, history_image_paths, new_h, new_w, args, fused_pixels=True):
     """The generation call of cli.py:236-248."""
     cond = prepare_condition_pixels(history_image_paths) if fused_pixels else prepare_condition_images(history_image_paths, pipe.device)
@@ -110,6 +122,7 @@ def generate_image(pipe, prompt_embeds, pooled_prompt_embeds, history_image_path
         num_inference_steps=args.num_inference_steps,
         guidance_scale=args.guidance_scale,
         generator=torch.Generator(device="cuda").manual_seed(seed),
+        **inpaint_kwargs(args),
     ).images[0]
 
 
@@ -138,6 +151,7 @@ def run_t5_only(pipe, text_encoders, tokenizers, text, image1=None, image2=None,
         num_inference_steps=args.num_inference_steps,
         guidance_scale=args.guidance_scale,
         num_images_per_prompt=getattr(args, "num_images_per_prompt", 1),
+        **inpaint_kwargs(args),
     ).images
 
 
@@ -165,6 +179,12 @@ def build_parser():
                         help="mxfp8 only: let the long-K block GEMMs run as split-K pairs (FK_MX_SPLITK=1; default off)")
     parser.add_argument("--mx_fused_attn", action="store_true",
                         help="mxfp8 with FK_MX_FUSED_QUANT=1 only: the attention emits MXFP8 itself (FK_MX_FUSED_ATTN=1; default off)")
+    parser.add_argument("--mask", type=str, default=None, metavar="PATH",
+                        help="greyscale mask image, white = repaint, black = keep the first of --images bit for bit in "
+                             "latent space (with --prompt_embeds / --t5_only)")
+    parser.add_argument("--strength", type=float, default=1.0, metavar="F",
+                        help="in (0, 1]: below 1 the edit starts from the re-noised input image instead of from noise and "
+                             "runs the last F of the steps (with --prompt_embeds / --t5_only)")
     return parser
 
 
@@ -174,6 +194,8 @@ def main(args):
         transformer.set_mx_splitk(True)
     if getattr(args, "mx_fused_attn", False):
         transformer.set_mx_fused_attn(True)
+    if (getattr(args, "mask", None) or getattr(args, "strength", 1.0) != 1.0) and not (args.prompt_embeds or args.t5_only):
+        raise SystemExit("--mask / --strength go with --prompt_embeds or --t5_only")
     pipe, tokenizers, text_encoders = load_pipe(args.model_path, args.flux_path, device,
                                                 weight_format=getattr(args, "weight_format", "bf16"))
     if args.prompt_embeds:

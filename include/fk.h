@@ -638,6 +638,25 @@ int fk_adamw_step_scaled(float* master, void* param_bf16, const void* grad, int3
  * (reference univa/utils/flux_pipeline.py:1078,1099) */
 int fk_euler_step_bf16(void* x, int64_t x_batch_stride, const void* v, int64_t v_batch_stride,
                        int32_t B, int32_t S_tgt, int32_t C, float dsigma, fk_stream_t stream);
+/* The same step for a masked (inpaint) edit, fused with the keep-region blend of diffusers' inpaint loop; every bf16(...)
+ * is one fp32 evaluation rounded once, as torch rounds per bf16 tensor op.  For s < S_tgt, element j of a token:
+ *   p    = bf16(x + bf16(bf16(dsigma) * v))                                        (fk_euler_step_bf16)
+ *   sb   = bf16(sigma_next)
+ *   keep = bf16(bf16(sb * noise) + bf16(bf16(1 - sb) * x0))                        (scale_noise; x0 when sigma_next == 0)
+ *   x    = bf16(bf16(bf16(1 - mask[j % 4]) * keep) + bf16(mask[j % 4] * p))
+ * mask: bf16 [1 or B, S_tgt, 4], one value per sub-pixel of the 2x2-packed token (element j is channel j / 4, sub-pixel
+ * j % 4), 1 = repaint, 0 = keep; mask_batch_stride == 0 broadcasts one mask over the batch.  x0, noise: [B, S_tgt, C] rows
+ * at their batch strides.  mask NULL = a mask of ones: the values of fk_euler_step_bf16; x0 and noise are then not read.
+ * C % 8 == 0; pointers and batch strides 16-byte aligned, the mask and its stride 8-byte aligned. */
+int fk_euler_inpaint_step_bf16(void* x, int64_t x_batch_stride, const void* v, int64_t v_batch_stride,
+                               const void* x0, int64_t x0_batch_stride, const void* noise, int64_t noise_batch_stride,
+                               const void* mask, int64_t mask_batch_stride, int32_t B, int32_t S_tgt, int32_t C,
+                               float dsigma, float sigma_next, fk_stream_t stream);
+/* FlowMatchEulerDiscreteScheduler.scale_noise on bf16 tensors -- the start tokens of an edit that begins inside the schedule:
+ *   out[b, s, :] = bf16(bf16(bf16(sigma) * noise) + bf16(bf16(1 - bf16(sigma)) * x0))   for s < S_tgt
+ * (the `keep` of fk_euler_inpaint_step_bf16, one device function). */
+int fk_scale_noise_bf16(const void* x0, int64_t x0_batch_stride, const void* noise, int64_t noise_batch_stride, void* out,
+                        int64_t out_batch_stride, int32_t B, int32_t S_tgt, int32_t C, float sigma, fk_stream_t stream);
 /* dst[r, c] = src[c, r] for a [R, C] bf16 matrix with leading dimensions lds/ldd (elements);
  * batched over `batch` with the given batch strides. */
 int fk_transpose_bf16(const void* src, int64_t lds, int64_t src_batch_stride, void* dst, int64_t ldd,
