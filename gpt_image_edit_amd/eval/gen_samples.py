@@ -124,6 +124,8 @@ def build_parser():
                    help="mxfp8 only: let the long-K block GEMMs run as split-K pairs (FK_MX_SPLITK=1; default off)")
     p.add_argument("--mx_fused_attn", action="store_true",
                    help="mxfp8 with FK_MX_FUSED_QUANT=1 only: the attention emits MXFP8 itself (FK_MX_FUSED_ATTN=1; default off)")
+    from ..serve.cli import add_step_cache_arguments
+    add_step_cache_arguments(p)
     return p
 
 
@@ -162,6 +164,7 @@ def main(args):
     torch.cuda.set_device(device)
     set_seed(args.seed, rank)
     from ..serve import cli
+    cli.step_cache_kwargs(args)      # validates the three options before the weights load
     if getattr(args, "mx_splitk", False):
         cli.transformer.set_mx_splitk(True)
     if getattr(args, "mx_fused_attn", False):
@@ -195,7 +198,8 @@ def main(args):
                 prompt_embeds = torch.cat([lvlm, t5_embeds.to(lvlm.device, lvlm.dtype)], dim=1) if args.joint_with_t5 else lvlm
             out = pipe(image=cli.prepare_condition_pixels(image_paths), prompt_embeds=prompt_embeds,
                        pooled_prompt_embeds=pooled, height=gen_h, width=gen_w, num_inference_steps=args.num_inference_steps,
-                       guidance_scale=args.guidance_scale, num_images_per_prompt=args.num_images_per_prompt)
+                       guidance_scale=args.guidance_scale, num_images_per_prompt=args.num_images_per_prompt,
+                       **cli.step_cache_kwargs(args))
             return out.images[0], out.latents[:1]
     res = run(args, edit_fn, rank, world)
     print(f"[rank {rank}/{world}] edited {len(res['done'])}, skipped {len(res['skipped'])} existing", flush=True)

@@ -189,6 +189,10 @@ SIGNATURES = {
     "fk_euler_inpaint_step_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32,
                                            c_f32, c_f32, c_vp]),
     "fk_scale_noise_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp]),
+    "fk_absdiff_ws_floats": (c_i64, []),
+    "fk_absdiff_sums_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "fk_residual_save_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_vp, Rows, c_i64, c_i32, c_i32, c_vp]),
+    "fk_residual_apply_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_vp, Rows, c_i64, c_i32, c_i32, c_vp]),
     "fk_transpose_bf16": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "fk_attention_hd512_bf16": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
     "fk_softmax_rows": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp]),

@@ -783,6 +783,58 @@ def pack_inpaint_mask(mask, h_lat, w_lat):
     return m.reshape(m.shape[0], (h_lat // 2) * (w_lat // 2), 4).to(BF16).contiguous()
 
 
+# ---- step cache (include/fk.h: fk_absdiff_sums_bf16, fk_residual_save_bf16, fk_residual_apply_bf16) -------------------
+def _step_cache_views(what, *ts):
+    """(M, D, is_bf16, [Rows]) of [B, R, D] (or [M, D]) views of one shape and dtype with contiguous rows.  The dtype travels
+    with the call: the library refuses anything but bf16 (FK_EUNSUPPORTED)."""
+    _need_cuda(*ts)
+    t0 = ts[0]
+    for t in ts:
+        if t.dim() not in (2, 3) or t.shape != t0.shape or t.dtype != t0.dtype:
+            raise ValueError(f"{what} takes [B, R, D] views of one shape and dtype, got "
+                             f"{[(tuple(t.shape), t.dtype) for t in ts]}")
+    rows = [rows_of(t) for t in ts]
+    return rows[0][0], t0.shape[-1], int(t0.dtype == BF16), [r for _, r in rows]
+
+
+def absdiff_ws(device):
+    """The partials workspace of :func:`absdiff_sums` (fp32): one per stream of ordered launches."""
+    return torch.empty(libfk.load().fk_absdiff_ws_floats(), device=device, dtype=torch.float32)
+
+
+def absdiff_sums(a, b, out=None, ws=None):
+    """fp32 [2]: (sum |a - b|, sum |b|) over two bf16 [B, R, D] views with contiguous rows (a row and a batch stride of their
+    own), fixed summation order: two calls on the same data give the same bits.  ``ws``: :func:`absdiff_ws` (allocated per call
+    when None -- the hot path owns one)."""
+    M, D, eb, (ra, rb) = _step_cache_views("absdiff_sums", a, b)
+    if out is None:
+        out = torch.empty(2, device=a.device, dtype=torch.float32)
+    if ws is None:
+        ws = absdiff_ws(a.device)
+    _need_cuda(out, ws)
+    if out.dtype != torch.float32 or out.numel() < 2 or not out.is_contiguous() or ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError("out must be fp32 [2], ws a contiguous fp32 workspace")
+    libfk.check(libfk.load().fk_absdiff_sums_bf16(_ptr(a), ra, _ptr(b), rb, M, D, eb, _ptr(out), _ptr(ws), ws.numel(), _stream()),
+                "fk_absdiff_sums_bf16")
+    return out
+
+
+def residual_save(h_out, h0, r):
+    """r = bf16(float(h_out) - float(h0)) over bf16 [B, R, D] views with contiguous rows; no two may overlap."""
+    M, D, eb, (ro, r0, rr) = _step_cache_views("residual_save", h_out, h0, r)
+    libfk.check(libfk.load().fk_residual_save_bf16(_ptr(h_out), ro, _ptr(h0), r0, _ptr(r), rr, M, D, eb, _stream()),
+                "fk_residual_save_bf16")
+    return r
+
+
+def residual_apply(h0, r, out):
+    """out = bf16(float(h0) + float(r)) over bf16 [B, R, D] views with contiguous rows; ``out`` may be ``h0`` itself."""
+    M, D, eb, (r0, rr, ro) = _step_cache_views("residual_apply", h0, r, out)
+    libfk.check(libfk.load().fk_residual_apply_bf16(_ptr(h0), r0, _ptr(r), rr, _ptr(out), ro, M, D, eb, _stream()),
+                "fk_residual_apply_bf16")
+    return out
+
+
 def transpose(src, dst):
     """dst[b, c, r] = src[b, r, c] for 3-D views with contiguous last dims."""
     _need_cuda(src, dst)

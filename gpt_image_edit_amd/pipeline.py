@@ -55,6 +55,8 @@ class FluxKontextPipeline:
         self._interrupt = False
         self._guidance_scale = None
         self._num_timesteps = 0
+        self._cache_state = None      # eager step-cache buffers of the latest call shape (transformer.step_cache_state)
+        self._said_adaptive_is_eager = False
 
     # static helpers the training script reaches for directly (train_denoiser.py:925,1009,1021,1098)
     _pack_latents = staticmethod(helpers._pack_latents)
@@ -263,13 +265,21 @@ class FluxKontextPipeline:
                  pooled_prompt_embeds=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None,
                  output_type="pil", return_dict=True, joint_attention_kwargs=None, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=("latents",), max_sequence_length=512,
-                 max_area=1024 ** 2, _auto_resize=True, mask_image=None, strength=1.0, init_image=None):
+                 max_area=1024 ** 2, _auto_resize=True, mask_image=None, strength=1.0, init_image=None, step_cache=None):
         """``mask_image`` / ``strength`` / ``init_image`` (diffusers' ``FluxKontextInpaintPipeline``): repaint only where the
         mask is 1 and keep ``init_image`` (default: ``image``, resized to the target size) elsewhere; ``strength`` < 1 starts
         the loop inside the schedule from the re-noised ``init_image`` instead of from noise.  ``image`` stays the Kontext
-        condition.  Without the three the call is the plain edit, launch for launch."""
+        condition.  Without the three the call is the plain edit, launch for launch.
+
+        ``step_cache`` (a ``step_cache.StepCache``): skip the MMDiT blocks on the steps its rule or schedule says, adding the
+        residual kept at the last computed step instead (one decision per step for the whole model batch).  A schedule is
+        sync-free and graph-capturable; the adaptive rule reads 8 bytes back per step and therefore runs the eager loop.
+        ``None`` is today's call, launch for launch."""
         device = self.device
         helpers.strength_t_start(num_inference_steps, strength)     # validates strength before any work
+        if step_cache is not None:                                  # ... and the schedule against the executed step count
+            n_all = num_inference_steps if sigmas is None else len(sigmas)
+            step_cache.validate(n_all - helpers.strength_t_start(n_all, strength))
         inpaint = mask_image is not None or init_image is not None or strength < 1.0
         if (mask_image is not None or strength < 1.0) and image is None and init_image is None:
             raise ValueError("`mask_image` / `strength` < 1 need a picture to preserve: pass `image` or `init_image`")
@@ -393,8 +403,17 @@ class FluxKontextPipeline:
                             dsigma=[self.scheduler.dsigma(i) for i in steps], inpaint=inpaint,
                             sigma_next=[self.scheduler.sigma_next(i) for i in steps] if inpaint else [],
                             # without a mask the fused step is the Euler update alone and reads neither x0 nor noise
-                            x0=x0 if mask is not None else None, noise=noise if mask is not None else None, mask=mask)
-        if self.use_graph and callback_on_step_end is None and not joint_attention_kwargs and not self._interrupt:
+                            x0=x0 if mask is not None else None, noise=noise if mask is not None else None, mask=mask,
+                            step_cache=step_cache, cache_state=None)
+        graphable = self.use_graph and callback_on_step_end is None and not joint_attention_kwargs and not self._interrupt
+        if graphable and step_cache is not None and step_cache.adaptive:
+            # the adaptive rule needs the step's two sums on the host before it can choose the step's launches
+            if not self._said_adaptive_is_eager:
+                print("step cache: the adaptive mode reads its measure back once per step, so this call runs the eager loop; "
+                      "replay its decisions through the graph with StepCache(schedule=step_cache.computed_steps)")
+                self._said_adaptive_is_eager = True
+            graphable = False
+        if graphable:
             tokens = self._denoise_graph(L)
         else:
             self._denoise(L, callback_on_step_end, timesteps)
@@ -416,17 +435,27 @@ class FluxKontextPipeline:
         if hasattr(self.transformer, "prepare_conditioning"):  # all steps' modulation vectors in one pass
             self.transformer.prepare_conditioning(L.t_model, L.guidance, L.pooled)
         tokens, B = L.tokens, L.batch_size
+        sc, st = L.step_cache, None
+        if sc is not None:
+            st = self._step_cache_state(L)
+            sc.begin(len(L.dsigma))
         for i in range(len(L.dsigma)):
             if self._interrupt:
                 continue
             if L.do_true_cfg:
                 L.model_tokens[:B].copy_(tokens)
                 L.model_tokens[B:].copy_(tokens)
-            noise_pred = self.transformer(
-                hidden_states=L.model_tokens, timestep=L.t_model[i], guidance=L.guidance,
-                pooled_projections=L.pooled, encoder_hidden_states=L.embeds,
-                txt_ids=L.text_ids, img_ids=L.latent_ids, joint_attention_kwargs=L.jak,
-                return_dict=False)[0]
+            fwd = dict(hidden_states=L.model_tokens, timestep=L.t_model[i], guidance=L.guidance,
+                       pooled_projections=L.pooled, encoder_hidden_states=L.embeds,
+                       txt_ids=L.text_ids, img_ids=L.latent_ids, joint_attention_kwargs=L.jak)
+            if sc is None:
+                noise_pred = self.transformer(**fwd, return_dict=False)[0]
+            else:
+                # two phases: embed (+ the measure), then the blocks or the cached residual; the adaptive rule's read of
+                # state.sums (8 bytes) is the one host sync per step the mode needs
+                self.transformer.step_cache_begin(st, **fwd)
+                compute = sc.step(i, st.sums.tolist() if sc.adaptive and i > 0 else None)
+                noise_pred = self.transformer.step_cache_end(st, compute)
             if L.do_true_cfg:
                 noise_pred = ops.true_cfg(noise_pred[:B], noise_pred[B:], L.true_cfg_scale)
             if L.inpaint:   # Euler update where the mask is 1, the preserved picture at sigma[i+1] where it is 0
@@ -437,6 +466,22 @@ class FluxKontextPipeline:
                 out = callback_on_step_end(self, i, timesteps[i], {"latents": tokens[:, :L.S_tgt]})
                 if out and "latents" in out:
                     tokens[:, :L.S_tgt].copy_(out["latents"])
+        if sc is not None:
+            sc.block_passes = st.block_passes
+
+    def _step_cache_state(self, L):
+        """The loop's cache state, reset for a new call: the graph route keeps one among the graph's own buffers
+        (``L.cache_state``), the eager loop one per pipeline whose buffers last while the call shape does."""
+        tr = self.transformer
+        if not hasattr(tr, "step_cache_begin"):
+            raise ValueError("`step_cache` needs a transformer with the two-phase forward (HipFluxTransformer2DModel)")
+        st = L.cache_state if L.cache_state is not None else self._cache_state
+        if st is None or st.measure != L.step_cache.adaptive:
+            st = tr.step_cache_state(measure=L.step_cache.adaptive)
+        if L.cache_state is None:
+            self._cache_state = st
+        st.steps, st.block_passes, st.have_residual, st.f = 0, 0, False, None
+        return st
 
     _GRAPH_INPUTS = ("tokens", "t_model", "guidance", "pooled", "embeds", "text_ids", "latent_ids", "x0", "noise", "mask")
 
@@ -455,7 +500,9 @@ class FluxKontextPipeline:
                getattr(self.transformer, "_pack_serial", 0), ops.launch_config_epoch(),
                # masked edits: the preserved picture, the noise and the mask are inputs (a new mask of the same shape replays);
                # their presence, the mask's batch form and the keep region's noise levels are frozen into the graph
-               L.inpaint, None if L.mask is None else tuple(L.mask.shape), tuple(L.sigma_next))
+               L.inpaint, None if L.mask is None else tuple(L.mask.shape), tuple(L.sigma_next),
+               # step cache: which steps run the blocks is frozen into the graph
+               None if L.step_cache is None else L.step_cache.schedule)
         cur = torch.cuda.current_stream()
         if self._loop_graph is None or self._loop_graph[0] != key:
             self._loop_graph = None
@@ -464,6 +511,8 @@ class FluxKontextPipeline:
                 t = getattr(L, n)
                 setattr(G, n, None if t is None else t.clone())
             G.model_tokens = torch.empty_like(L.model_tokens) if L.do_true_cfg else G.tokens
+            if L.step_cache is not None:    # the cache state (h0, the residual) belongs to the graph's own buffers
+                G.cache_state = self.transformer.step_cache_state(measure=False)
             side = torch.cuda.Stream(device=L.tokens.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):       # eager warm-up off the capture: kernel attributes, workspaces, RoPE cache
@@ -474,6 +523,10 @@ class FluxKontextPipeline:
                 self._denoise(G)
             self._loop_graph = (key, G, graph)
         _, G, graph = self._loop_graph
+        if L.step_cache is not None:        # a replay makes the decisions the capture froze: record them for this call's cache
+            L.step_cache.begin(len(L.dsigma))
+            L.step_cache.computed_steps = list(L.step_cache.schedule)
+            L.step_cache.block_passes = G.cache_state.block_passes = len(L.step_cache.schedule)
         for n in self._GRAPH_INPUTS:
             t = getattr(L, n)
             if t is not None:

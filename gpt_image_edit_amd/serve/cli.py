@@ -110,6 +110,26 @@ def inpaint_kwargs(args):
     return kw
 
 
+def step_cache_kwargs(args):
+    """``--step_cache_threshold`` / ``--step_cache_schedule`` / ``--step_cache_coefficients`` as the pipeline's ``step_cache``
+    (nothing when neither mode is given: every step runs the blocks).  A fresh ``StepCache`` per call."""
+    from ..step_cache import from_args
+    sc = from_args(getattr(args, "step_cache_threshold", None), getattr(args, "step_cache_schedule", None),
+                   getattr(args, "step_cache_coefficients", None))
+    return {} if sc is None else {"step_cache": sc}
+
+
+def add_step_cache_arguments(parser):
+    parser.add_argument("--step_cache_threshold", type=float, default=None, metavar="F",
+                        help="adaptive step cache: skip the MMDiT blocks while the accumulated relative L1 change of the first "
+                             "block's modulated input stays below F (no default: which F is acceptable depends on the checkpoint)")
+    parser.add_argument("--step_cache_schedule", type=str, default=None, metavar="0,1,3,...",
+                        help="fixed step cache: the executed-step indices that run the blocks (must start with 0); sync-free, "
+                             "goes through the graph route")
+    parser.add_argument("--step_cache_coefficients", type=str, default=None, metavar="a0,a1,...",
+                        help="with --step_cache_threshold: rescaling polynomial of the measure, lowest order first (default 0,1)")
+
+
 def generate_image(pipe, prompt_embeds, pooled_prompt_embeds, history_image_paths, new_h, new_w, args, fused_pixels=True):
     """The generation call of cli.py:236-248."""
     cond = prepare_condition_pixels(history_image_paths) if fused_pixels else prepare_condition_images(history_image_paths, pipe.device)
@@ -123,6 +143,7 @@ def generate_image(pipe, prompt_embeds, pooled_prompt_embeds, history_image_path
         guidance_scale=args.guidance_scale,
         generator=torch.Generator(device="cuda").manual_seed(seed),
         **inpaint_kwargs(args),
+        **step_cache_kwargs(args),
     ).images[0]
 
 
@@ -152,6 +173,7 @@ def run_t5_only(pipe, text_encoders, tokenizers, text, image1=None, image2=None,
         guidance_scale=args.guidance_scale,
         num_images_per_prompt=getattr(args, "num_images_per_prompt", 1),
         **inpaint_kwargs(args),
+        **step_cache_kwargs(args),
     ).images
 
 
@@ -185,6 +207,7 @@ def build_parser():
     parser.add_argument("--strength", type=float, default=1.0, metavar="F",
                         help="in (0, 1]: below 1 the edit starts from the re-noised input image instead of from noise and "
                              "runs the last F of the steps (with --prompt_embeds / --t5_only)")
+    add_step_cache_arguments(parser)
     return parser
 
 
@@ -196,6 +219,7 @@ def main(args):
         transformer.set_mx_fused_attn(True)
     if (getattr(args, "mask", None) or getattr(args, "strength", 1.0) != 1.0) and not (args.prompt_embeds or args.t5_only):
         raise SystemExit("--mask / --strength go with --prompt_embeds or --t5_only")
+    step_cache_kwargs(args)      # a bad threshold / schedule / coefficient list fails before the weights load
     pipe, tokenizers, text_encoders = load_pipe(args.model_path, args.flux_path, device,
                                                 weight_format=getattr(args, "weight_format", "bf16"))
     if args.prompt_embeds:

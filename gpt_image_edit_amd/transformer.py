@@ -487,7 +487,22 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
     @torch.no_grad()
     def _forward_infer(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids,
                        guidance, return_dict, key_mask=None):
-        c, D, H = self.config, self.inner_dim, self.num_heads
+        f = self._infer_frame(hidden_states, encoder_hidden_states, pooled_projections, img_ids, txt_ids)
+        P = self.p
+        # -- embedders -------------------------------------------------------------------------------
+        ops.gemm(f.hs, P("x_embedder.weight"), P("x_embedder.bias"), out=f.h)
+        ops.gemm(f.enc, P("context_embedder.weight"), P("context_embedder.bias"), out=f.cx)
+        mod = self._infer_modulation(f, timestep, guidance, pooled_projections)
+        self._infer_blocks(f, mod, key_mask)
+        sample = self._infer_head(f, mod)
+        if not return_dict:
+            return (sample,)
+        return SimpleNamespace(sample=sample)
+
+    # The inference forward in three parts -- embed (the two embedder GEMMs above + _infer_modulation), blocks, head -- over
+    # one "frame": the call's workspace, RoPE tables and cast inputs.  _forward_infer strings them together; the step cache
+    # (step_cache_begin / step_cache_end) runs the blocks only on the steps that compute.
+    def _infer_frame(self, hidden_states, encoder_hidden_states, pooled_projections, img_ids, txt_ids):
         pk = self.packed()
         B, S_img, _ = hidden_states.shape
         S_txt = encoder_hidden_states.shape[1]
@@ -496,26 +511,28 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         cs = self._rope(txt_ids, img_ids, packed=True)   # (cos, sin) per rotary pair: what the fused QKV epilogue reads
         if cos.shape[0] != ws.S:
             raise ValueError(f"txt_ids + img_ids give {cos.shape[0]} positions for a sequence of {ws.S}")
-        hs = hidden_states.to(BF16).contiguous()
-        enc = encoder_hidden_states.to(BF16).contiguous()
-        pooled = pooled_projections.to(BF16).contiguous()
-        P = self.p
         s, n = ws.s, ws.n
-        h, cx = s[:, S_txt:], s[:, :S_txt]          # image / text residual streams (views)
-        n_img, n_txt = n[:, S_txt:], n[:, :S_txt]
+        return SimpleNamespace(pk=pk, ws=ws, B=B, S_img=S_img, S_txt=S_txt, cos=cos, sin=sin, cs=cs,
+                               hs=hidden_states.to(BF16).contiguous(), enc=encoder_hidden_states.to(BF16).contiguous(),
+                               pooled=pooled_projections.to(BF16).contiguous(),
+                               h=s[:, S_txt:], cx=s[:, :S_txt],          # image / text residual streams (views)
+                               n_img=n[:, S_txt:])
 
-        # -- embedders -------------------------------------------------------------------------------
-        ops.gemm(hs, P("x_embedder.weight"), P("x_embedder.bias"), out=h)
-        ops.gemm(enc, P("context_embedder.weight"), P("context_embedder.bias"), out=cx)
+    def _infer_modulation(self, f, timestep, guidance, pooled_projections):
+        """The step's modulation vectors [B, mod_total]: a row of the prepared conditioning, else computed into the workspace."""
         mod = self._cached_modulation(timestep, guidance, pooled_projections)
         if mod is None:
-            self._conditioning(timestep, guidance, pooled, ws.tproj, ws.e1, ws.t_emb, ws.g_emb, ws.p_emb, ws.temb,
+            ws = f.ws
+            self._conditioning(timestep, guidance, f.pooled, ws.tproj, ws.e1, ws.t_emb, ws.g_emb, ws.p_emb, ws.temb,
                                ws.act, ws.mod)
             mod = ws.mod
+        return mod
 
-        def chunk(off, j):
-            return mod[:, off + j * D: off + (j + 1) * D]
-
+    def _infer_blocks(self, f, mod, key_mask=None):
+        """The 19 + 38 blocks on the workspace's residual stream, on whichever route applies."""
+        D = self.inner_dim
+        pk, ws, B, S_txt, S_img, cos, sin, cs = f.pk, f.ws, f.B, f.S_txt, f.S_img, f.cos, f.sin, f.cs
+        s = ws.s
         block_api = BLOCK_API if (FUSE_QKV and not MLP_FIRST and not (OVERLAP_MLP and (OVERLAP_MLP != "auto" or self._overlap_pays(B, ws.S)))
                                   and S_txt > 0) else 0
         if key_mask is not None:   # masked attention: per-launch bf16 route, no block-level entry point, no side stream
@@ -540,15 +557,76 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         else:
             self._blocks_by_kernel_calls(ws, pk, mod, cos, sin, cs, B, S_txt)
 
-        # -- output head: AdaLayerNormContinuous (scale first, then shift) + proj_out -----------------------
-        ops.ln_modulate(h, chunk(pk.mod_out, 1), chunk(pk.mod_out, 0), out=n_img)
+    def _infer_head(self, f, mod):
+        """Output head: AdaLayerNormContinuous (scale first, then shift) + proj_out on the image stream."""
+        D, off = self.inner_dim, f.pk.mod_out
+        ops.ln_modulate(f.h, mod[:, off + D: off + 2 * D], mod[:, off: off + D], out=f.n_img)
         # the result is a FRESH tensor every call (64 channels per token: tiny; the caching allocator serves it without
         # a device sync): callers such as the reference pipeline's true-CFG branch keep one call's output while
         # making the next (flux_pipeline.py:1067-1095), which a persistent workspace buffer would silently alias
-        sample = ops.gemm(n_img, P("proj_out.weight"), P("proj_out.bias"))
-        if not return_dict:
-            return (sample,)
-        return SimpleNamespace(sample=sample)
+        return ops.gemm(f.n_img, self.p("proj_out.weight"), self.p("proj_out.bias"))
+
+    # ---- step cache: one forward in two phases (pipeline._denoise; step_cache.py holds the decision) ------------------------
+    def step_cache_state(self, measure):
+        """State of one cached denoise loop.  ``measure``: adaptive mode -- every ``step_cache_begin`` also writes the first
+        block's modulated image input and launches the distance to the previous step's into ``state.sums`` (fp32 [2])."""
+        return SimpleNamespace(measure=bool(measure), key=None, f=None, mod=None, key_mask=None, block_passes=0, steps=0,
+                               have_residual=False, h0=None, r=None, cur=None, prev=None, sums=None, absdiff_ws=None)
+
+    @torch.no_grad()
+    def step_cache_begin(self, state, hidden_states, encoder_hidden_states=None, pooled_projections=None, timestep=None,
+                         img_ids=None, txt_ids=None, guidance=None, joint_attention_kwargs=None):
+        """First phase of an inference forward (the arguments of :meth:`forward`): ``x_embedder`` into ``state.h0``
+        [B, S_img, D] and the step's modulation; with ``state.measure`` also LN-modulate(h0; block 0's image shift / scale) into
+        ``state.cur``, ``ops.absdiff_sums(cur, prev)`` into ``state.sums`` (from the second step on: the first has nothing to
+        compare with) and the swap of the two.  Nothing of the blocks runs; :meth:`step_cache_end` finishes the forward."""
+        if not hidden_states.is_cuda:
+            raise RuntimeError("HipFluxTransformer2DModel needs GPU tensors: there is no CPU fallback")
+        state.key_mask = None
+        if joint_attention_kwargs and joint_attention_kwargs.get("attention_mask") is not None:
+            state.key_mask = self._joint_key_mask(joint_attention_kwargs["attention_mask"], hidden_states, encoder_hidden_states)
+        f = self._infer_frame(hidden_states, encoder_hidden_states, pooled_projections, img_ids, txt_ids)
+        D, dev = self.inner_dim, f.ws.s.device
+        key = (f.B, f.S_img, D, dev, state.measure)
+        if state.key != key:        # buffers once per call shape; a new shape starts a new loop
+            e = lambda: torch.empty((f.B, f.S_img, D), device=dev, dtype=BF16)  # noqa: E731
+            state.key, state.h0, state.r, state.have_residual, state.steps = key, e(), e(), False, 0
+            if state.measure:
+                state.cur, state.prev = e(), e()
+                state.sums = torch.zeros(2, device=dev, dtype=torch.float32)
+                state.absdiff_ws = ops.absdiff_ws(dev)
+        ops.gemm(f.hs, self.p("x_embedder.weight"), self.p("x_embedder.bias"), out=state.h0)
+        state.f, state.mod = f, self._infer_modulation(f, timestep, guidance, pooled_projections)
+        if state.measure:
+            pk, mod = f.pk, state.mod
+            off = pk.double[0].mod_img if pk.double else pk.single[0].mod      # chunks: shift, scale, ...
+            ops.ln_modulate(state.h0, mod[:, off: off + D], mod[:, off + D: off + 2 * D], out=state.cur)
+            if state.steps > 0:
+                ops.absdiff_sums(state.cur, state.prev, out=state.sums, ws=state.absdiff_ws)
+            state.cur, state.prev = state.prev, state.cur       # the previous modulated input is replaced at EVERY step
+        state.steps += 1
+
+    @torch.no_grad()
+    def step_cache_end(self, state, compute):
+        """Second phase.  ``compute=True``: h0 into the workspace stream, ``context_embedder``, the blocks (on the route the
+        plain forward would take), ``state.r = h - h0``, the head.  ``compute=False``: ``h = h0 + state.r`` and the head with
+        THIS step's ``norm_out`` modulation -- no ``context_embedder``, no block.  Returns the sample (a fresh tensor)."""
+        f, mod = state.f, state.mod
+        if f is None:
+            raise RuntimeError("step_cache_end without step_cache_begin")
+        state.f = None
+        if compute:
+            f.h.copy_(state.h0)
+            ops.gemm(f.enc, self.p("context_embedder.weight"), self.p("context_embedder.bias"), out=f.cx)
+            self._infer_blocks(f, mod, state.key_mask)
+            ops.residual_save(f.h, state.h0, state.r)
+            state.have_residual = True
+            state.block_passes += 1
+        else:
+            if not state.have_residual:
+                raise RuntimeError("step cache: a skipped step before any computed one has no residual to add")
+            ops.residual_apply(state.h0, state.r, out=f.h)
+        return self._infer_head(f, mod)
 
     def _blocks_by_kernel_calls(self, ws, pk, mod, cos, sin, cs, B, S_txt, key_mask=None):
         """The 19 + 38 blocks as one ctypes call per kernel launch (FK_BLOCK_API=0; also the route of the A/B switches

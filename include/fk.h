@@ -657,6 +657,27 @@ int fk_euler_inpaint_step_bf16(void* x, int64_t x_batch_stride, const void* v, i
  * (the `keep` of fk_euler_inpaint_step_bf16, one device function). */
 int fk_scale_noise_bf16(const void* x0, int64_t x0_batch_stride, const void* noise, int64_t noise_batch_stride, void* out,
                         int64_t out_batch_stride, int32_t B, int32_t S_tgt, int32_t C, float sigma, fk_stream_t stream);
+/* ---- step cache: residual caching across denoise steps (csrc/step_cache.hip; gpt_image_edit_amd/step_cache.py) ----
+ * All views are bf16 [B, R, D] with contiguous rows, M = B * R rows addressed through fk_rows (strides in elements, >= D and
+ * >= 0), e.g. the image part n[:, S_txt:] of a joint buffer.  is_bf16 states the type of the caller's tensors (as fk_sumsq's g_is_bf16
+ * does): 0 is FK_EUNSUPPORTED.  NULL pointers, M < 1, D < 1, a row stride below D: FK_EINVAL, nothing launched.  Rows that are
+ * 16-byte aligned move as 16-byte vectors, a cut last chunk (D % 8 != 0) and unaligned views element by element; any size.
+ *
+ * out[0] = sum |float(a) - float(b)|, out[1] = sum |float(b)| over all M * D elements, in fp32 and in a FIXED order: per
+ * 8-element chunk a pairwise tree, per thread its chunks in increasing order, a 256-wide halving tree per block, then one
+ * finalising block over the per-block partials in ws (a second launch).  No floating-point atomics: two launches on the same
+ * data give the same bits.  ws: fk_absdiff_ws_floats() floats owned by the caller (ws_floats says how many there are; fewer
+ * than 2 per block of the launch is FK_EINVAL); launches that share one must be ordered. */
+int64_t fk_absdiff_ws_floats(void);
+int fk_absdiff_sums_bf16(const void* a, fk_rows ra, const void* b, fk_rows rb, int64_t M, int32_t D, int32_t is_bf16,
+                         float* out, float* ws, int64_t ws_floats, fk_stream_t stream);
+/* r = bf16(float(h_out) - float(h0)): what the blocks added to their input, kept for the steps that skip them.  r must not
+ * overlap h_out or h0, nor they each other (tested on the byte range a view spans from its first to its last row: FK_EINVAL). */
+int fk_residual_save_bf16(const void* h_out, fk_rows ro, const void* h0, fk_rows r0, void* r, fk_rows rr, int64_t M, int32_t D,
+                          int32_t is_bf16, fk_stream_t stream);
+/* out = bf16(float(h0) + float(r)).  out may BE h0 (same pointer and strides); any other overlap of the three is FK_EINVAL. */
+int fk_residual_apply_bf16(const void* h0, fk_rows r0, const void* r, fk_rows rr, void* out, fk_rows ro, int64_t M, int32_t D,
+                           int32_t is_bf16, fk_stream_t stream);
 /* dst[r, c] = src[c, r] for a [R, C] bf16 matrix with leading dimensions lds/ldd (elements);
  * batched over `batch` with the given batch strides. */
 int fk_transpose_bf16(const void* src, int64_t lds, int64_t src_batch_stride, void* dst, int64_t ldd,
