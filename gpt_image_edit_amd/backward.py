@@ -103,6 +103,9 @@ class FluxBackward:
             raise NotImplementedError(
                 "FluxBackward has no weight gradient for " + ", ".join(unsupported[:6]) + (" ..." if len(unsupported) > 6 else "")
                 + ": trainable parameters must belong to transformer_blocks.* / single_transformer_blocks.*")
+        if getattr(model, "lora_loaded", None) is not None and model.lora_loaded():
+            raise RuntimeError("FluxBackward: the model has LoRA adapters merged into its weights; training through LoRA is not "
+                               "built -- unload_lora() first")
         if not model._train_packs:     # from now on the model fuses nothing an optimiser rewrites (transformer.pack_weights)
             model._train_packs, model._packed = True, None
         self._wT = {}          # name -> (W^T (bf16 [in, out]) for the data gradients, stamp of its source)

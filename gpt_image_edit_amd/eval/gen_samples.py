@@ -126,6 +126,8 @@ def build_parser():
                    help="mxfp8 with FK_MX_FUSED_QUANT=1 only: the attention emits MXFP8 itself (FK_MX_FUSED_ATTN=1; default off)")
     from ..serve.cli import add_step_cache_arguments
     add_step_cache_arguments(p)
+    from ..lora import add_cli_arguments
+    add_cli_arguments(p)
     return p
 
 
@@ -171,6 +173,7 @@ def main(args):
         cli.transformer.set_mx_fused_attn(True)
     pipe, tokenizers, text_encoders = cli.load_pipe(args.model_path, args.flux_path, device,
                                                     weight_format=getattr(args, "weight_format", "bf16"))
+    cli.lora.load_cli_adapters(pipe, getattr(args, "lora", None))
     if args.t5_only:
         def edit_fn(prompt, image_path):
             return cli.run_t5_only(pipe, text_encoders, tokenizers, prompt, image1=image_path, args=args)[0], None
@@ -199,7 +202,7 @@ def main(args):
             out = pipe(image=cli.prepare_condition_pixels(image_paths), prompt_embeds=prompt_embeds,
                        pooled_prompt_embeds=pooled, height=gen_h, width=gen_w, num_inference_steps=args.num_inference_steps,
                        guidance_scale=args.guidance_scale, num_images_per_prompt=args.num_images_per_prompt,
-                       **cli.step_cache_kwargs(args))
+                       **cli.step_cache_kwargs(args), **cli.lora_kwargs(args))
             return out.images[0], out.latents[:1]
     res = run(args, edit_fn, rank, world)
     print(f"[rank {rank}/{world}] edited {len(res['done'])}, skipped {len(res['skipped'])} existing", flush=True)

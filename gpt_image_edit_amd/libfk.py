@@ -135,6 +135,12 @@ class MxWs(ctypes.Structure):                 # fk_mx_ws
                 ("quantize_launches", ctypes.POINTER(c_i32)), ("splitk", c_i32)]
 
 
+class LoraTerm(ctypes.Structure):              # fk_lora_term
+    _fields_ = [("up", c_vp), ("ld_up", c_i64), ("down", c_vp), ("ld_down", c_i64), ("rank", c_i32), ("scale", c_f32)]
+
+
+FK_LORA_MAX_TERMS, FK_LORA_MAX_RANK = 4, 128
+
 # symbol -> (restype, argtypes); must list every entry point of include/fk.h
 SIGNATURES = {
     "fk_gemm_bf16": (c_i32, [ctypes.POINTER(GemmArgs), c_vp]),
@@ -193,6 +199,7 @@ SIGNATURES = {
     "fk_absdiff_sums_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "fk_residual_save_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_vp, Rows, c_i64, c_i32, c_i32, c_vp]),
     "fk_residual_apply_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_vp, Rows, c_i64, c_i32, c_i32, c_vp]),
+    "fk_lora_merge_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(LoraTerm), c_i32, c_vp]),
     "fk_transpose_bf16": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "fk_attention_hd512_bf16": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
     "fk_softmax_rows": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp]),

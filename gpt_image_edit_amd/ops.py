@@ -835,6 +835,33 @@ def residual_apply(h0, r, out):
     return out
 
 
+# ---- LoRA merge (include/fk.h: fk_lora_merge_bf16) ---------------------------------------------------------------------
+def lora_merge(base, terms, out=None):
+    """out = bf16(float(base) + sum_t scale_t * (up_t @ down_t)) over a bf16 weight [N, K] (fp32 accumulation, terms added in
+    order).  ``terms``: a list of ``(up [N, r], down [r, K], scale)``.  ``out=None`` merges in place.  2-D views with a
+    contiguous last dimension; every refusal comes from the library."""
+    if out is None:
+        out = base
+    terms = list(terms)
+    ts = [base, out] + [t for up, down, _ in terms for t in (up, down)]
+    _need_cuda(*ts)
+    for t in ts:
+        if t.dim() != 2 or t.stride(-1) != 1 or t.dtype != BF16:
+            raise ValueError(f"lora_merge takes 2-D bf16 views with a contiguous last dimension, got {tuple(t.shape)} {t.dtype} "
+                             f"strides {t.stride()}")
+    N, K = base.shape
+    if out.shape != base.shape:
+        raise ValueError(f"out is {tuple(out.shape)}, base {tuple(base.shape)}")
+    arr = (libfk.LoraTerm * max(len(terms), 1))()
+    for i, (up, down, scale) in enumerate(terms):
+        if up.shape[0] != N or down.shape[1] != K or up.shape[1] != down.shape[0]:
+            raise ValueError(f"term {i}: up {tuple(up.shape)} / down {tuple(down.shape)} do not fit the weight [{N}, {K}]")
+        arr[i] = libfk.LoraTerm(up.data_ptr(), up.stride(0), down.data_ptr(), down.stride(0), up.shape[1], float(scale))
+    libfk.check(libfk.load().fk_lora_merge_bf16(_ptr(base), base.stride(0), _ptr(out), out.stride(0), N, K, arr, len(terms),
+                                                _stream()), "fk_lora_merge_bf16")
+    return out
+
+
 def transpose(src, dst):
     """dst[b, c, r] = src[b, r, c] for 3-D views with contiguous last dims."""
     _need_cuda(src, dst)

@@ -155,6 +155,29 @@ class FluxKontextPipeline:
         text_ids = torch.zeros(prompt_embeds.shape[1], 3).to(device=device, dtype=dtype)
         return prompt_embeds, pooled_prompt_embeds, text_ids
 
+    # ---- LoRA adapters for the denoiser (diffusers' FluxLoraLoaderMixin names; lora.py: merged into the weights) -----------
+    def _lora_model(self):
+        if not hasattr(self.transformer, "load_lora_adapter"):
+            raise ValueError("LoRA adapters need a transformer with the adapter API (HipFluxTransformer2DModel)")
+        return self.transformer
+
+    def load_lora_weights(self, path_or_dict, adapter_name="default", weight=1.0):
+        """A diffusers / PEFT LoRA (``transformer.<module>.lora_A.weight`` ...) merged into the denoiser.  Text-encoder keys
+        are ignored (returned); any other unknown key is a ``ValueError``."""
+        return self._lora_model().load_lora_adapter(path_or_dict, adapter_name=adapter_name, weight=weight)
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        self._lora_model().set_adapters(adapter_names, adapter_weights)
+
+    def delete_adapters(self, adapter_names):
+        self._lora_model().delete_adapters(adapter_names)
+
+    def unload_lora_weights(self):
+        self._lora_model().unload_lora()
+
+    def get_active_adapters(self):
+        return self._lora_model().active_adapters()
+
     def _encode_vae_image(self, image, nhwc=False):
         """(mode(vae.encode(image)) - shift) * scale, the affine fused into the layout kernel (:600-613)."""
         cfg = self.vae.config
@@ -274,8 +297,19 @@ class FluxKontextPipeline:
         ``step_cache`` (a ``step_cache.StepCache``): skip the MMDiT blocks on the steps its rule or schedule says, adding the
         residual kept at the last computed step instead (one decision per step for the whole model batch).  A schedule is
         sync-free and graph-capturable; the adaptive rule reads 8 bytes back per step and therefore runs the eager loop.
-        ``None`` is today's call, launch for launch."""
+        ``None`` is today's call, launch for launch.
+
+        ``joint_attention_kwargs["scale"]`` (default 1.0): the call scale of the loaded LoRA adapters (``load_lora_weights``)."""
         device = self.device
+        if joint_attention_kwargs and "scale" in joint_attention_kwargs:
+            # the LoRA call scale: merged into the weights before the loop and left there until another scale is asked for;
+            # without adapters it is ignored.  It is no argument of the transformer call, so it leaves the kwargs here
+            joint_attention_kwargs = dict(joint_attention_kwargs)
+            scale = joint_attention_kwargs.pop("scale")
+            if getattr(self.transformer, "lora_loaded", None) is not None and self.transformer.lora_loaded():
+                self.transformer.set_lora_scale(1.0 if scale is None else scale)
+        elif getattr(self.transformer, "lora_loaded", None) is not None and self.transformer.lora_loaded():
+            self.transformer.set_lora_scale(1.0)
         helpers.strength_t_start(num_inference_steps, strength)     # validates strength before any work
         if step_cache is not None:                                  # ... and the schedule against the executed step count
             n_all = num_inference_steps if sigmas is None else len(sigmas)

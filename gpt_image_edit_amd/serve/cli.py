@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from .. import checkpoint, flux_spec
+from .. import checkpoint, flux_spec, lora
 from ..anyres_util import dynamic_resize
 from ..pipeline import FluxKontextPipeline
 from ..scheduler import FlowMatchEulerDiscreteScheduler
@@ -119,6 +119,13 @@ def step_cache_kwargs(args):
     return {} if sc is None else {"step_cache": sc}
 
 
+def lora_kwargs(args):
+    """``--lora_scale`` as the pipeline's ``joint_attention_kwargs["scale"]`` (nothing without ``--lora``: the plain edit)."""
+    if not getattr(args, "lora", None):
+        return {}
+    return {"joint_attention_kwargs": {"scale": getattr(args, "lora_scale", 1.0)}}
+
+
 def add_step_cache_arguments(parser):
     parser.add_argument("--step_cache_threshold", type=float, default=None, metavar="F",
                         help="adaptive step cache: skip the MMDiT blocks while the accumulated relative L1 change of the first "
@@ -144,6 +151,7 @@ def generate_image(pipe, prompt_embeds, pooled_prompt_embeds, history_image_path
         generator=torch.Generator(device="cuda").manual_seed(seed),
         **inpaint_kwargs(args),
         **step_cache_kwargs(args),
+        **lora_kwargs(args),
     ).images[0]
 
 
@@ -174,6 +182,7 @@ def run_t5_only(pipe, text_encoders, tokenizers, text, image1=None, image2=None,
         num_images_per_prompt=getattr(args, "num_images_per_prompt", 1),
         **inpaint_kwargs(args),
         **step_cache_kwargs(args),
+        **lora_kwargs(args),
     ).images
 
 
@@ -208,6 +217,7 @@ def build_parser():
                         help="in (0, 1]: below 1 the edit starts from the re-noised input image instead of from noise and "
                              "runs the last F of the steps (with --prompt_embeds / --t5_only)")
     add_step_cache_arguments(parser)
+    lora.add_cli_arguments(parser)
     return parser
 
 
@@ -222,6 +232,7 @@ def main(args):
     step_cache_kwargs(args)      # a bad threshold / schedule / coefficient list fails before the weights load
     pipe, tokenizers, text_encoders = load_pipe(args.model_path, args.flux_path, device,
                                                 weight_format=getattr(args, "weight_format", "bf16"))
+    lora.load_cli_adapters(pipe, getattr(args, "lora", None))
     if args.prompt_embeds:
         blob = torch.load(args.prompt_embeds, map_location="cpu", weights_only=True)
         urls = [u.strip() for u in args.images.split(",") if u.strip()]

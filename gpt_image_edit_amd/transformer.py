@@ -26,6 +26,7 @@ import torch
 from torch import nn
 
 from . import flux_spec, ops
+from .lora import LoraMixin
 from .param_tree import ParamTreeMixin, build_param_tree
 
 BF16 = torch.bfloat16
@@ -102,7 +103,7 @@ def rope_tables(ids, axes_dim=(16, 56, 56), theta=10000.0):
     return torch.cat(cos_parts, dim=1).contiguous(), torch.cat(sin_parts, dim=1).contiguous()
 
 
-class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
+class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
     """Module tree = the diffusers ``FluxTransformer2DModel``'s: ``transformer_blocks.{i}.attn.to_q`` ... are
     parameter-holding sub-modules (``param_tree.ParamNode``), so the reference's ``named_modules()`` selection
     (``train_denoiser.py:538-543``), ``named_parameters()`` and ``state_dict()`` see the names of Appendix C."""
@@ -132,6 +133,7 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         self._rope_cache = {}
         self._freqs = None
         self._cond = None
+        self._lora_init()             # lora.LoraMixin: load_lora_adapter / set_adapters / set_lora_scale / unload_lora
         self.weight_format = "bf16"
         self.set_weight_format(weight_format)
 
@@ -169,6 +171,11 @@ class HipFluxTransformer2DModel(ParamTreeMixin, nn.Module):
         self._rope_cache = {}
         self._freqs = None
         self._cond = None
+        for name, t in self._lora_base.items():          # the adapters and the saved bases move with the parameters
+            self._lora_base[name] = fn(t)
+        for entries in self._lora_adapters.values():
+            for e in entries.values():
+                e.up, e.down = fn(e.up), fn(e.down)
         return super()._apply(fn, *a, **k)
 
     # ---- one-time weight packing (fused QKV, all-block modulation) -----------------------------------------

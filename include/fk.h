@@ -787,6 +787,28 @@ int fk_pixels_u8_to_nhwc_bf16(const void* src, void* dst, int32_t B, int32_t Hin
 int fk_image_to_u8_nhwc(const void* src, int32_t src_is_fp32, void* dst, int32_t B, int32_t C, int32_t H, int32_t W,
                         fk_stream_t stream);
 
+/* ---- LoRA merge (transformer.py: load_lora_adapter / set_adapters / set_lora_scale; the reference's pipeline is a
+ * FluxLoraLoaderMixin, univa/utils/flux_pipeline.py:195).  Adapters become part of a bf16 weight [N, K]:
+ *   out[n, k] = bf16_rne( float(base[n, k]) + sum_t scale_t * acc_t[n, k] ),  acc_t[n, k] = sum_j up_t[n, j] * down_t[j, k]
+ * acc_t accumulated in fp32 on the bf16 MFMA, the terms added in ascending t (one fp32 fma each).  Row strides in elements,
+ * rows contiguous.  out may BE base (same pointer and row stride: every element is read and written by one lane); otherwise
+ * out overlaps nothing.  base, up and down are never written.  A term whose scale is 0 adds nothing: all scales 0 gives
+ * base's bits.  Supported: N >= 1; K >= 8, K % 8 == 0; ld_* >= the row length; 1 <= rank <= FK_LORA_MAX_RANK;
+ * 1 <= n_terms <= FK_LORA_MAX_TERMS; anything else returns FK_EINVAL / FK_EUNSUPPORTED and writes nothing.  `terms` is a
+ * HOST array, copied into the launch by value. ---- */
+#define FK_LORA_MAX_TERMS 4
+#define FK_LORA_MAX_RANK 128
+typedef struct fk_lora_term {
+  const void* up;   /* bf16 [N, rank]  (lora_B) */
+  int64_t ld_up;
+  const void* down; /* bf16 [rank, K]  (lora_A) */
+  int64_t ld_down;
+  int32_t rank;
+  float scale;
+} fk_lora_term;
+int fk_lora_merge_bf16(const void* base, int64_t ld_base, void* out, int64_t ld_out, int32_t N, int32_t K,
+                       const fk_lora_term* terms, int32_t n_terms, fk_stream_t stream);
+
 const char* fk_last_error(void);
 /* Build identification: "fk <version> gfx950". */
 const char* fk_version(void);
