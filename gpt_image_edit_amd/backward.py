@@ -87,14 +87,19 @@ def wgrad(buf, dy, x, out=None):
 class FluxBackward:
     """Training forward / backward around a ``HipFluxTransformer2DModel`` (which keeps owning the parameters)."""
 
-    def __init__(self, model, trainable=None, store_activations="auto", activation_budget_bytes=96 << 30):
+    def __init__(self, model, trainable=None, store_activations="auto", activation_budget_bytes=96 << 30, lora=None):
         """store_activations: True = keep every block's intermediates from the forward (no recomputation: 37 GB at
         1024^2, bs 1 -- sized for 288 GB of HBM, where the reference's 80 GB GPUs force checkpointing); False = one
-        checkpoint per block + recomputation in the backward; "auto" = store when it fits ``activation_budget_bytes``."""
+        checkpoint per block + recomputation in the backward; "auto" = store when it fits ``activation_budget_bytes``.
+        lora: the name of a loaded adapter that is being trained (``train_step.DenoiserTrainStep(lora=...)``) -- permits a model
+        with adapters merged into its weights; ``trainable`` then defaults to the WEIGHTS that adapter touches, so only their
+        wgrad GEMMs run and ``backward`` emits the gradient w.r.t. the merged weight.  Without it such a model is refused."""
         from . import training
         self.store_activations, self.activation_budget = store_activations, activation_budget_bytes
         self.m = model
         names = list(model._pmap.keys())
+        if lora is not None and trainable is None:
+            trainable = model.lora_backward_weights(lora)
         self.trainable = set(trainable if trainable is not None else training.trainable_names(names))
         # every parameter of the 57 blocks has a weight gradient here; the embedders, norm_out and the output
         # projection do not (the reference never un-freezes them: train_denoiser.py:74-76, :93-95 are commented out)
@@ -103,9 +108,9 @@ class FluxBackward:
             raise NotImplementedError(
                 "FluxBackward has no weight gradient for " + ", ".join(unsupported[:6]) + (" ..." if len(unsupported) > 6 else "")
                 + ": trainable parameters must belong to transformer_blocks.* / single_transformer_blocks.*")
-        if getattr(model, "lora_loaded", None) is not None and model.lora_loaded():
-            raise RuntimeError("FluxBackward: the model has LoRA adapters merged into its weights; training through LoRA is not "
-                               "built -- unload_lora() first")
+        if lora is None and getattr(model, "lora_loaded", None) is not None and model.lora_loaded():
+            raise RuntimeError("FluxBackward: the model has LoRA adapters merged into its weights; a full-weight step would train "
+                               "the merged weights -- unload_lora() first, or train the adapter (DenoiserTrainStep(lora=...))")
         if not model._train_packs:     # from now on the model fuses nothing an optimiser rewrites (transformer.pack_weights)
             model._train_packs, model._packed = True, None
         self._wT = {}          # name -> (W^T (bf16 [in, out]) for the data gradients, stamp of its source)

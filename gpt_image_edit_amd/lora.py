@@ -12,8 +12,22 @@ Exactness rules
     of ``set_adapters`` (default: load order);
   * a weight is re-merged only when its tuple of (adapter, effective scale) changed since its last merge.
 
+Training (``train_step.DenoiserTrainStep(model, lora=adapter_name)``) keeps that function: the forward and backward over a
+model with a trainable adapter are launch for launch the training forward and backward on the merged weights, and the chain
+rule through the merge, straight through its one bf16 rounding, gives the factors' gradients from the ``dW`` the backward
+already computes: ``d_up = s dW down^T``, ``d_down = s up^T dW`` (``ops.lora_grad``, ``fk_lora_grad_bf16``), block by block, so
+one block's ``dW`` is alive at a time.  AdamW runs on fp32 masters of the factors and rewrites the bf16 factors; the touched
+weights are then marked stale (``lora_mark_stale``) and re-merged from their bases, one launch each.  ``add_lora_adapter``
+creates an adapter (``up = 0``: the model is unchanged until the first step), ``lora_state_dict`` /
+``pipe.save_lora_weights`` write it in the layout ``parse_lora_state`` reads.  The merged design still pays for the full wgrad
+GEMM; it saves the fp32 optimiser state and the kept gradients of the full step and changes no forward or backward kernel.
+
 Not built: text-encoder LoRA (the encoders are stock transformers models; such keys are reported as ignored), BFL / kohya
-fused-qkv key formats, bias / norm deltas, LoRA training, more than ``FK_LORA_MAX_TERMS`` active adapters on one weight.
+fused-qkv key formats, bias / norm deltas, more than ``FK_LORA_MAX_TERMS`` active adapters on one weight, ranks above
+``FK_LORA_MAX_RANK`` = 128.  Training, not built: the ZeRO / data-parallel exchange of adapter gradients (``sharded=True``
+with ``lora=`` is refused), micro-batch accumulation (every ``forward_backward`` overwrites the adapter gradients), a
+side-branch backward that never forms ``dW`` (it would save the wgrad flops as well), an fp32-output wgrad in front of the
+projection (``dW`` is rounded to bf16 first, as in the full step), bias / norm deltas, text-encoder adapters.
 
 ``state_dict()`` / ``save_pretrained`` of a model with active adapters hold the MERGED weights (diffusers after
 ``fuse_lora``); ``unload_lora()`` first to save the plain ones.
@@ -168,6 +182,114 @@ class LoraMixin:
             del self._lora_adapters[adapter_name], self._lora_active[adapter_name]
             raise
         return ignored
+
+    # ---- training (train_step.DenoiserTrainStep(model, lora=adapter_name)) ---------------------------------------------------
+    QKV_GROUPS = (("to_q", "to_k", "to_v"), ("add_q_proj", "add_k_proj", "add_v_proj"))
+
+    def _lora_default_targets(self):
+        """The Linear weights among ``training.trainable_names``: image-stream ``attn.to_q / to_k / to_v / to_out.0`` of the
+        double blocks, ``attn.to_q / to_k / to_v`` of the single blocks."""
+        from . import training
+        leaves = ("attn.to_q.weight", "attn.to_k.weight", "attn.to_v.weight", "attn.to_out.0.weight")
+        return [k[:-len(".weight")] for k in training.trainable_names(list(self._pmap.keys())) if k.endswith(leaves)]
+
+    def _lora_resolve_targets(self, target_modules):
+        """Module names (no ``.weight``) of ``target_modules``: full names or PEFT-style suffixes (``"to_q"``, ``"ff.net.2"``);
+        the q / k / v of an attention named in part are completed to the three."""
+        from .backward import FluxBackward
+        mods = [k[:-len(".weight")] for k in self._pmap if k.endswith(".weight")]
+        chosen, bad = [], []
+        for t in target_modules:
+            t = t[:-len(".weight")] if t.endswith(".weight") else t
+            hit = [m for m in mods if m == t or m.endswith("." + t)]
+            if not hit:
+                bad.append(t)
+            for m in hit:
+                if not FluxBackward.producible(m + ".weight") or self.p(m + ".weight").dim() != 2:
+                    bad.append(m + ".weight")
+                elif m not in chosen:
+                    chosen.append(m)
+        if bad:
+            raise ValueError("LoRA targets must be 2-D weights of transformer_blocks.* / single_transformer_blocks.* (the "
+                             "backward produces no other weight gradient): " + _name_some(set(bad)))
+        for m in list(chosen):
+            stem, _, leaf = m.rpartition(".")
+            for group in self.QKV_GROUPS:
+                if leaf in group:
+                    chosen += [f"{stem}.{g}" for g in group if f"{stem}.{g}" not in chosen]
+        return sorted(chosen)
+
+    def add_lora_adapter(self, adapter_name="default", rank=16, alpha=None, target_modules=None, seed=0, weight=1.0):
+        """Create a trainable adapter instead of loading one and activate it after the current adapters: ``up`` (lora_B) = 0,
+        ``down`` (lora_A) uniform in +-1/sqrt(K) (PEFT's ``kaiming_uniform_(a=sqrt(5))``) from a generator seeded with ``seed``,
+        stored bf16 -- the merged weights stay the base weights bit for bit until the first optimiser step.  ``alpha``
+        defaults to ``rank``.  ``target_modules``: module names or PEFT-style suffixes (``"to_q"``, ``"ff.net.2"``,
+        ``"proj_mlp"``); default: the Linear weights among ``training.trainable_names``.  Every target must be a 2-D weight of
+        ``transformer_blocks.*`` / ``single_transformer_blocks.*``.  ``to_q / to_k / to_v`` (and ``add_q_proj / add_k_proj /
+        add_v_proj``) of one attention come as a group -- the backward computes their gradient as one [3D, D] GEMM -- so naming
+        one of them selects the three.  Returns the parameter names touched."""
+        if self._train_packs:
+            raise RuntimeError("add_lora_adapter: the model is under training (FluxBackward owns its packs); add or load adapters "
+                               "before the train step is built")
+        if adapter_name in self._lora_adapters:
+            raise ValueError(f"adapter {adapter_name!r} is already loaded: delete_adapters([{adapter_name!r}]) first")
+        rank = int(rank)
+        if not 1 <= rank <= FK_LORA_MAX_RANK:
+            raise ValueError(f"rank {rank}: supported 1 to {FK_LORA_MAX_RANK}")
+        mods = self._lora_default_targets() if target_modules is None else self._lora_resolve_targets(
+            [target_modules] if isinstance(target_modules, str) else list(target_modules))
+        if not mods:
+            raise ValueError("add_lora_adapter: no target modules")
+        alpha = float(rank if alpha is None else alpha)
+        g = torch.Generator().manual_seed(int(seed))
+        entries = OrderedDict()
+        for mod in sorted(mods):
+            w = self.p(mod + ".weight")
+            N, K = w.shape
+            lim = torch.tensor(K ** -0.5, dtype=torch.float32).to(BF16)
+            if float(lim) > K ** -0.5:          # the largest bf16 number inside the interval: the rounding stays within +-1/sqrt(K)
+                lim = (lim.view(torch.int16) - 1).view(BF16)
+            down = ((torch.rand(rank, K, generator=g, dtype=torch.float32) * 2 - 1) / K ** 0.5).to(BF16).clamp(-lim, lim)
+            entries[mod + ".weight"] = SimpleNamespace(up=torch.zeros(N, rank, device=w.device, dtype=BF16),
+                                                       down=down.to(w.device).contiguous(), alpha=alpha, rank=rank)
+        self._lora_adapters[adapter_name] = entries
+        self._lora_active[adapter_name] = float(weight)
+        try:
+            self._lora_sync()
+        except Exception:
+            del self._lora_adapters[adapter_name], self._lora_active[adapter_name]
+            raise
+        return list(entries)
+
+    def lora_mark_stale(self, adapter_name):
+        """The factors of ``adapter_name`` were rewritten (an optimiser step): forget the last merge of the weights it touches, so
+        the next ``_lora_sync()`` re-merges exactly those, one launch each, from their saved bases."""
+        for pname in self._lora_adapters[adapter_name]:
+            self._lora_merged.pop(pname, None)
+
+    def lora_state_dict(self, adapter_name="default", prefix="transformer."):
+        """The adapter in the diffusers / PEFT layout ``parse_lora_state`` reads: ``<prefix><module>.lora_A.weight`` (down),
+        ``.lora_B.weight`` (up), ``.alpha`` -- the bf16 factors the model runs with, on the CPU."""
+        if adapter_name not in self._lora_adapters:
+            raise ValueError(f"lora_state_dict: not loaded: {adapter_name!r}")
+        sd = OrderedDict()
+        for pname, e in self._lora_adapters[adapter_name].items():
+            mod = prefix + pname[:-len(".weight")]
+            sd[mod + ".lora_A.weight"] = e.down.detach().cpu().clone()
+            sd[mod + ".lora_B.weight"] = e.up.detach().cpu().clone()
+            sd[mod + ".alpha"] = torch.tensor(float(e.alpha))
+        return sd
+
+    def lora_backward_weights(self, adapter_name):
+        """The weights whose wgrad GEMMs a backward for ``adapter_name`` has to run: its targets, the q / k / v of an attention
+        completed to the three (their gradient is gated on the first of them)."""
+        names = set(self._lora_adapters[adapter_name])
+        for pname in list(names):
+            stem, _, leaf = pname[:-len(".weight")].rpartition(".")
+            for group in self.QKV_GROUPS:
+                if leaf in group:
+                    names |= {f"{stem}.{g}.weight" for g in group}
+        return names
 
     def set_adapters(self, names, weights=None):
         """Activate exactly ``names`` (a name or a list), in this order, with ``weights`` (default 1.0 each)."""

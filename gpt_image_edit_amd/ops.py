@@ -862,6 +862,47 @@ def lora_merge(base, terms, out=None):
     return out
 
 
+# ---- LoRA gradient projection (include/fk.h: fk_lora_grad_bf16) ----------------------------------------------------------
+def lora_grad_ws(N, K, rank, device):
+    """The partials workspace of :func:`lora_grad` for a weight [N, K] at ``rank`` (fp32; empty when the kernel splits
+    nothing): one per stream of ordered launches."""
+    return torch.empty(libfk.load().fk_lora_grad_ws_floats(N, K, rank), device=device, dtype=torch.float32)
+
+
+def lora_grad(dw, up, down, scale, d_up=None, d_down=None, ws=None):
+    """(d_up [N, r], d_down [r, K]) in fp32: ``scale * dw @ down^T`` and ``scale * up^T @ dw`` for the weight gradient
+    ``dw`` bf16 [N, K] of a weight merged as ``base + scale * up @ down`` (fp32 accumulation, fixed summation order: two calls
+    give the same bits).  ``dw``, ``up`` [N, r], ``down`` [r, K]: 2-D bf16 views with a contiguous last dimension; the
+    outputs contiguous fp32.  ``ws``: :func:`lora_grad_ws` (allocated per call when None -- the hot path owns one)."""
+    ins = [dw, up, down]
+    _need_cuda(*ins)
+    for t in ins:
+        if t.dim() != 2 or t.stride(-1) != 1 or t.dtype != BF16:
+            raise ValueError(f"lora_grad takes 2-D bf16 views with a contiguous last dimension, got {tuple(t.shape)} {t.dtype} "
+                             f"strides {t.stride()}")
+    N, K = dw.shape
+    r = up.shape[1]
+    if up.shape[0] != N or down.shape[1] != K or down.shape[0] != r:
+        raise ValueError(f"up {tuple(up.shape)} / down {tuple(down.shape)} do not fit the gradient [{N}, {K}]")
+    if d_up is None:
+        d_up = torch.empty(N, r, device=dw.device, dtype=torch.float32)
+    if d_down is None:
+        d_down = torch.empty(r, K, device=dw.device, dtype=torch.float32)
+    need = libfk.load().fk_lora_grad_ws_floats(N, K, r)
+    if ws is None:
+        ws = torch.empty(need, device=dw.device, dtype=torch.float32)
+    _need_cuda(d_up, d_down, ws)
+    for t, shape in ((d_up, (N, r)), (d_down, (r, K))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"lora_grad writes contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+    if ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError("ws must be a contiguous fp32 workspace")
+    libfk.check(libfk.load().fk_lora_grad_bf16(_ptr(dw), dw.stride(0), _ptr(up), up.stride(0), _ptr(down), down.stride(0), N, K, r,
+                                               float(scale), _ptr(d_up), _ptr(d_down), _ptr(ws) if ws.numel() else None,
+                                               ws.numel(), _stream()), "fk_lora_grad_bf16")
+    return d_up, d_down
+
+
 def transpose(src, dst):
     """dst[b, c, r] = src[b, r, c] for 3-D views with contiguous last dims."""
     _need_cuda(src, dst)

@@ -172,6 +172,21 @@ class FluxKontextPipeline:
     def delete_adapters(self, adapter_names):
         self._lora_model().delete_adapters(adapter_names)
 
+    def save_lora_weights(self, path, adapter_name="default"):
+        """Write adapter ``adapter_name`` (trained through ``DenoiserTrainStep(lora=...)``, or loaded) as one safetensors file
+        in the layout ``load_lora_weights`` reads.  ``path``: the file, or a directory (then
+        ``pytorch_lora_weights.safetensors`` in it, diffusers' name).  Returns the file's path."""
+        import os
+        from .checkpoint import _safetensors
+        st, _ = _safetensors()
+        path = os.fspath(path)
+        if os.path.isdir(path) or not path.endswith(".safetensors"):
+            os.makedirs(path, exist_ok=True)
+            path = os.path.join(path, "pytorch_lora_weights.safetensors")
+        sd = self._lora_model().lora_state_dict(adapter_name)
+        st.save_file({k: v.contiguous() for k, v in sd.items()}, path, metadata={"format": "pt"})
+        return path
+
     def unload_lora_weights(self):
         self._lora_model().unload_lora()
 

@@ -22,6 +22,11 @@ the padding tokens act as keys of every real token -- a bug, not a specification
 attention_mask=...)`` hands the mask to the attention kernels as a key-padding mask (text keys always valid, broadcast over
 heads and queries; ``HipFluxTransformer2DModel.forward`` has the forms).  Without ``attention_mask``, ``weight_mask`` weighs
 the loss only and the attention runs unmasked, as before.
+
+With ``lora=adapter_name`` the step trains a LoRA adapter's factors instead of the weights (``lora.py``, "Training"): the same
+forward and backward on the merged weights, each target weight's ``dW`` projected onto ``up`` / ``down`` as its block emits it
+(``fk_lora_grad_bf16``), AdamW on fp32 masters of the factors, then one re-merge per touched weight from its saved base.  The
+optimiser state is 12 bytes per ADAPTER parameter and only one block's ``dW`` is alive at a time.
 """
 import torch
 
@@ -33,15 +38,35 @@ BF16 = torch.bfloat16
 
 class DenoiserTrainStep:
     def __init__(self, model, lr=1e-6, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, trainable=None,
-                 sharded=False, group=None, store_activations="auto", projector=None, keep_grads=True, bucket_numel=None):
+                 sharded=False, group=None, store_activations="auto", projector=None, keep_grads=True, bucket_numel=None,
+                 lora=None):
         """sharded=True: the optimiser state lives in ``zero.ShardedAdamW`` (ZeRO-2: one flat bf16 parameter buffer the
         model's trainable tensors become views of, fp32 gradients reduce-scattered over the data-parallel ranks, this
         rank's slice of master + moments updated, parameters all-gathered); works unchanged with one process.
         keep_grads=False (sharded only): ``forward_backward`` hands every block's gradients to the optimiser's buckets and
-        does not keep them (saves the 8 GB of bf16 gradients; ``step()['grads']`` is then empty)."""
+        does not keep them (saves the 8 GB of bf16 gradients; ``step()['grads']`` is then empty).
+        lora=adapter_name: train that adapter's factors instead of the weights (``lora.py``; created by ``add_lora_adapter`` or
+        loaded from a file -- the same code).  The forward and backward are launch for launch the ones above on the merged
+        weights, with only the adapter's target weights in the wgrad set; each block's ``dW`` is projected onto the factors as it is
+        emitted (``fk_lora_grad_bf16``) and dropped.  The trainable parameters are ``<module>.lora_A.weight`` (down) and
+        ``<module>.lora_B.weight`` (up); other active adapters stay merged and frozen.  Not with ``sharded=True``."""
         self.model = model
         self.projector = projector
-        self.bw = FluxBackward(model, trainable, store_activations=store_activations)
+        self.lora = lora
+        if lora is not None:
+            if sharded:
+                raise ValueError("DenoiserTrainStep: lora= with sharded=True is not built (no ZeRO / data-parallel exchange of "
+                                 "adapter gradients)")
+            if trainable is not None:
+                raise ValueError("DenoiserTrainStep: lora= trains the adapter's factors; trainable= selects full weights")
+            if lora not in model._lora_adapters or lora not in model._lora_active:
+                raise ValueError(f"DenoiserTrainStep: adapter {lora!r} is not loaded and active (add_lora_adapter / "
+                                 "load_lora_adapter / set_adapters before the train step is built)")
+            model.set_lora_scale(1.0)          # the scale of the projection is the one the weights were merged with
+            self._lora_entries = model._lora_adapters[lora]
+            self._lora_grads = {}              # parameter name -> (d_up, d_down): persistent fp32 gradient buffers
+            self._lora_ws = None
+        self.bw = FluxBackward(model, trainable, store_activations=store_activations, lora=lora)
         self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
         self.step_count = 0
         self.state = {}     # name -> (fp32 master, exp_avg, exp_avg_sq)
@@ -62,8 +87,13 @@ class DenoiserTrainStep:
 
     PROJ = "denoise_projector."
 
+    LORA_A, LORA_B = ".lora_A.weight", ".lora_B.weight"
+
     def trainable_names(self):
-        names = set(self.bw.trainable)
+        if self.lora is not None:
+            names = {k[:-len(".weight")] + sfx for k in self._lora_entries for sfx in (self.LORA_A, self.LORA_B)}
+        else:
+            names = set(self.bw.trainable)
         if self.projector is not None:
             names |= {self.PROJ + k for k in self.projector.state_dict()}
         return names
@@ -71,7 +101,36 @@ class DenoiserTrainStep:
     def _param(self, name):
         if name.startswith(self.PROJ):
             return self.projector.p(name[len(self.PROJ):])
+        if self.lora is not None:
+            for sfx, slot in ((self.LORA_A, "down"), (self.LORA_B, "up")):
+                if name.endswith(sfx):
+                    return getattr(self._lora_entries[name[:-len(sfx)] + ".weight"], slot)
+            raise KeyError(f"{name} is no factor of adapter {self.lora!r}")
         return self.model.p(name)
+
+    def _lora_sink(self, out):
+        """The sink of ``FluxBackward.backward`` under ``lora=``: every emitted ``dW`` of a target weight is projected onto
+        its two factors (one ``fk_lora_grad_bf16`` call) into the persistent fp32 buffers; ``out`` collects them by name."""
+        scales = {p: next(s for a, s, _ in ts if a == self.lora) for p, ts in self.model._lora_wanted().items()
+                  if any(a == self.lora for a, _, _ in ts)}
+        if self._lora_ws is None:
+            dev = self.model.device
+            need = max(ops.lora_grad_ws(e.up.shape[0], e.down.shape[1], e.rank, dev).numel() for e in self._lora_entries.values())
+            self._lora_ws = torch.empty(need, device=dev, dtype=torch.float32)
+
+        def sink(block_grads):
+            for pname, dw in block_grads.items():
+                e = self._lora_entries.get(pname)
+                if e is None:                  # the rest of a q / k / v group, a bias: not this adapter's
+                    continue
+                bufs = self._lora_grads.get(pname)
+                if bufs is None:
+                    bufs = self._lora_grads[pname] = (torch.empty(e.up.shape, device=dw.device, dtype=torch.float32),
+                                                      torch.empty(e.down.shape, device=dw.device, dtype=torch.float32))
+                ops.lora_grad(dw, e.up, e.down, scales[pname], d_up=bufs[0], d_down=bufs[1], ws=self._lora_ws)
+                mod = pname[:-len(".weight")]
+                out[mod + self.LORA_B], out[mod + self.LORA_A] = bufs
+        return sink
 
     def _state(self, name):
         st = self.state.get(name)
@@ -168,7 +227,15 @@ class DenoiserTrainStep:
                 self.opt.accumulate(block_grads)
                 for k, g in block_grads.items():
                     self._sunk[k] = (g.data_ptr(), g._version)
-        grads, d_enc = self.bw.backward(dsample, sink=sink, keep=self.keep_grads or self.opt is None)
+        if self.lora is not None:
+            lora_grads = {}
+            _, d_enc = self.bw.backward(dsample, sink=self._lora_sink(lora_grads), keep=False)
+            missing = sorted(k for k in self.trainable_names() if not k.startswith(self.PROJ) and k not in lora_grads)
+            if missing:
+                raise RuntimeError("the backward emitted no weight gradient for " + ", ".join(missing[:4]))
+            grads = lora_grads
+        else:
+            grads, d_enc = self.bw.backward(dsample, sink=sink, keep=self.keep_grads or self.opt is None)
         if n_proj:
             pg = {self.PROJ + k: g for k, g in self.projector.backward(d_enc[:, :n_proj]).items()}
             if sink is not None:
@@ -207,8 +274,19 @@ class DenoiserTrainStep:
             master, m1, m2 = self._state(k)
             ops.adamw_step(master, grads[k].contiguous(), m1, m2, self.step_count, self.lr, self.betas, self.eps,
                            self.weight_decay, grad_sumsq=sumsq, max_grad_norm=self.max_grad_norm, param_bf16=self._param(k).data)
+        self._lora_remerge()
         self.bw.refresh()
         return sumsq
+
+    def _lora_remerge(self):
+        """The factors changed: re-merge exactly the weights the trained adapter touches, one launch each, from their bases.  The
+        model's packs are kept -- ``bw.refresh()`` re-copies, in place, the fused operands built from those weights."""
+        if self.lora is None:
+            return
+        pk = self.model._packed
+        self.model.lora_mark_stale(self.lora)
+        self.model._lora_sync()
+        self.model._packed = pk
 
     def discard(self):
         """Drop the gradients of the backward passes since the last optimiser step (a step that is deliberately skipped, e.g.
@@ -225,7 +303,7 @@ class DenoiserTrainStep:
         this rank (``zero.ShardedAdamW.state_dict``) or, unsharded, the per-tensor fp32 masters and moments."""
         if self.opt is not None:
             return dict(kind="sharded", opt=self.opt.state_dict())
-        return dict(kind="per_tensor", step=self.step_count,
+        return dict(kind="lora" if self.lora is not None else "per_tensor", step=self.step_count,
                     state={k: tuple(t.detach().cpu().clone() for t in st) for k, st in self.state.items()})
 
     @torch.no_grad()
@@ -234,6 +312,8 @@ class DenoiserTrainStep:
         the fp32 masters, so the next step continues bit for bit."""
         if (sd.get("kind") == "sharded") != (self.opt is not None):
             raise ValueError("optimiser state was saved with another `sharded` setting")
+        if (sd.get("kind") == "lora") != (self.lora is not None):
+            raise ValueError("optimiser state was saved with another `lora` setting")
         self._sunk = {}
         if self.opt is not None:
             self.opt.load_state_dict(sd["opt"])
@@ -245,6 +325,7 @@ class DenoiserTrainStep:
                 p = self._param(k)
                 self.state[k] = tuple(t.to(p.device) for t in (master, m1, m2))
                 p.data.copy_(self.state[k][0])
+        self._lora_remerge()
         self.bw.refresh()
         self.model._packed = None
 

@@ -809,6 +809,22 @@ typedef struct fk_lora_term {
 int fk_lora_merge_bf16(const void* base, int64_t ld_base, void* out, int64_t ld_out, int32_t N, int32_t K,
                        const fk_lora_term* terms, int32_t n_terms, fk_stream_t stream);
 
+/* ---- LoRA gradient projection (train_step.py: DenoiserTrainStep(lora=...)).  The chain rule through the merge
+ * W = bf16(W_base + scale * up . down), straight through its one bf16 rounding, from the weight gradient dw [N, K]:
+ *   d_up  [n, j] = scale * sum_k dw[n, k] * down[j, k]          d_down[j, k] = scale * sum_n up[n, j] * dw[n, k]
+ * dw, up [N, rank] (lora_B), down [rank, K] (lora_A): bf16, rows contiguous, row strides in elements (dw may be a row block of a
+ * wider buffer).  d_up [N, rank] and d_down [rank, K]: fp32, contiguous.  Products on the bf16 MFMA with fp32 accumulation, the
+ * rank zero-padded to 32, the reduction index to the kernel's step; scale multiplies the finished sum once.  No atomics: every
+ * output element is written once by a sum whose order is fixed by (N, K, rank) alone (csrc/lora_grad.hip states it).  When a
+ * reduction is split over workgroups the unscaled partials go through `ws`, fk_lora_grad_ws_floats(N, K, rank) floats (0 when
+ * nothing is split: ws may then be NULL); one workspace per stream of ordered launches.  The inputs are never written; outputs
+ * and workspace overlap nothing.  Supported: N >= 1, K >= 1, ld_* >= the row length, 1 <= rank <= FK_LORA_MAX_RANK, a finite
+ * scale; anything else returns FK_EINVAL / FK_EUNSUPPORTED and writes nothing. ---- */
+int64_t fk_lora_grad_ws_floats(int32_t N, int32_t K, int32_t rank);
+int fk_lora_grad_bf16(const void* dw, int64_t ld_dw, const void* up, int64_t ld_up, const void* down, int64_t ld_down,
+                      int32_t N, int32_t K, int32_t rank, float scale, float* d_up, float* d_down, float* ws,
+                      int64_t ws_floats, fk_stream_t stream);
+
 const char* fk_last_error(void);
 /* Build identification: "fk <version> gfx950". */
 const char* fk_version(void);

@@ -1,0 +1,158 @@
+"""Timing of LoRA training on one MI355X (development aid; bench.py is the contract benchmark).
+
+    python tools/bench_lora_train.py [--ranks 16,64,128] [--steps 3] [--warmup 2] [--out profiles/lora_train.json]
+
+Full-size model (19 + 38 blocks, synthetic weights) at the cfg 5 shape (1024^2, batch 1: 512 text + 4096 target + 4096 condition
+tokens), ready ``prompt_embeds`` (no projector on either side):
+
+1. the full stage-2 step, ``DenoiserTrainStep(model)`` on the reference's trainable set with per-tensor fp32 state -- the code of
+   the commit before LoRA training, unchanged by it -- ms per step and ``torch.cuda.max_memory_allocated``;
+2. per rank, the LoRA step ``DenoiserTrainStep(model, lora=...)`` on the default targets: the same two figures;
+3. per rank, the summed time of the ``fk_lora_grad_bf16`` launches of one step (one per target weight, on the q / k / v row blocks
+   of a [3D, D] gradient as the step issues them) beside the wgrad GEMMs they follow (``backward.wgrad`` at the step's token
+   count), both on random operands, each list timed as one bracket of events.
+
+Every phase builds its own model and frees it; peak memory is reset in between.  No threshold is asserted anywhere.
+"""
+import argparse
+import gc
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+BF = torch.bfloat16
+
+
+def batch_of(device):
+    g = torch.Generator(device=device).manual_seed(7)
+    B, h, w, S_txt = 1, 128, 128, 512
+    return dict(model_input=torch.randn(B, 16, h, w, generator=g, device=device),
+                cond_latents=torch.randn(B, 16, h, w, generator=g, device=device),
+                noise=torch.randn(B, 16, h, w, generator=g, device=device),
+                sigmas=torch.rand(B, generator=g, device=device) * 0.8 + 0.1,
+                prompt_embeds=torch.randn(B, S_txt, 4096, generator=g, device=device).to(BF),
+                pooled=torch.randn(B, 768, generator=g, device=device).to(BF)), S_txt + 2 * (h // 2) * (w // 2)
+
+
+def timed_steps(ts, batch, steps, warmup):
+    for _ in range(warmup):
+        out = ts.step(**batch)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        out = ts.step(**batch)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    assert torch.isfinite(out["loss"]).all()
+    return ms
+
+
+def phase(build, steps, warmup, device):
+    from gpt_image_edit_amd import flux_spec
+    from gpt_image_edit_amd.transformer import HipFluxTransformer2DModel
+    gc.collect()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats(device)
+    model = HipFluxTransformer2DModel(dict(flux_spec.FLUX_KONTEXT_CONFIG), device=device, init="synthetic", seed=0)
+    ts = build(model)
+    batch, _ = batch_of(device)
+    ms = timed_steps(ts, batch, steps, warmup)
+    n_train = sum(ts._param(k).numel() for k in ts.trainable_names())
+    res = dict(ms_per_step_median=statistics.median(ms), ms_per_step=ms, trainable_params=n_train,
+               peak_memory_gb=torch.cuda.max_memory_allocated(device) / 1e9)
+    del ts, model, batch
+    return res
+
+
+def bracket_ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def kernels(rank, S, device, reps, D=3072, n_double=19, n_single=38):
+    """One step's projection launches beside the wgrad GEMMs in front of them, on random operands."""
+    from gpt_image_edit_amd import backward, ops
+    g = torch.Generator(device=device).manual_seed(rank)
+    rnd = lambda *shape, s=1.0: (s * torch.randn(*shape, generator=g, device=device)).to(BF)  # noqa: E731
+    dy3, dy1, x = rnd(1, S, 3 * D, s=0.02), rnd(1, S, D, s=0.02), rnd(1, S, D)
+    bufs = {}
+
+    def buf(name, shape, zero=False):
+        if name not in bufs:
+            bufs[name] = (torch.zeros if zero else torch.empty)(shape, device=device, dtype=BF)
+        return bufs[name]
+    dw3, dw1 = torch.empty(3 * D, D, device=device, dtype=BF), torch.empty(D, D, device=device, dtype=BF)
+    up, down = rnd(D, rank, s=0.02), rnd(rank, D, s=0.02)
+    d_up, d_down = torch.empty(D, rank, device=device), torch.empty(rank, D, device=device)
+    ws = ops.lora_grad_ws(D, D, rank, device)
+
+    def wgrads():
+        for _ in range(n_double + n_single):
+            backward.wgrad(buf, dy3, x, out=dw3)
+        for _ in range(n_double):
+            backward.wgrad(buf, dy1, x, out=dw1)
+
+    def projections():
+        for _ in range(n_double + n_single):
+            for k in range(3):
+                ops.lora_grad(dw3[k * D:(k + 1) * D], up, down, 1.0, d_up=d_up, d_down=d_down, ws=ws)
+        for _ in range(n_double):
+            ops.lora_grad(dw1, up, down, 1.0, d_up=d_up, d_down=d_down, ws=ws)
+    w, p = bracket_ms(wgrads, reps), bracket_ms(projections, reps)
+    n = 3 * (n_double + n_single) + n_double
+    return dict(launches=n, wgrad_ms_median=statistics.median(w), lora_grad_ms_median=statistics.median(p),
+                lora_grad_us_per_launch=1e3 * statistics.median(p) / n,
+                lora_grad_gb_per_s=n * 4 * D * D / 1e9 / (statistics.median(p) / 1e3),       # dW read twice: 4 B per element
+                lora_grad_over_wgrad=statistics.median(p) / statistics.median(w), wgrad_ms=w, lora_grad_ms=p,
+                note="projection bracket includes the host loop (one ctypes call per launch)")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ranks", default="16,64,128")
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--skip_full", action="store_true", help="leave out the full stage-2 step (48 GB of optimiser state)")
+    ap.add_argument("--out", default="profiles/lora_train.json")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("needs a GPU: a timing from anything else says nothing")
+    from gpt_image_edit_amd.train_step import DenoiserTrainStep
+    dev = "cuda"
+    _, S = batch_of(dev)
+    res = dict(device=torch.cuda.get_device_name(0), shape="cfg5 1024x1024 bs1", seq_len=S, steps=args.steps, warmup=args.warmup, ranks=[])
+    if not args.skip_full:
+        res["full_step"] = phase(lambda m: DenoiserTrainStep(m), args.steps, args.warmup, dev)
+        print(json.dumps({"full_step": {k: v for k, v in res["full_step"].items() if k != "ms_per_step"}}), flush=True)
+    for rank in [int(r) for r in args.ranks.split(",")]:
+        def build(m, rank=rank):
+            m.add_lora_adapter("bench", rank=rank)
+            return DenoiserTrainStep(m, lora="bench")
+        entry = dict(rank=rank, lora_step=phase(build, args.steps, args.warmup, dev), kernels=kernels(rank, S, dev, args.reps))
+        res["ranks"].append(entry)
+        print(json.dumps({"rank": rank, "lora_step": {k: v for k, v in entry["lora_step"].items() if k != "ms_per_step"},
+                          "kernels": {k: v for k, v in entry["kernels"].items() if not k.endswith("_ms")}}), flush=True)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
