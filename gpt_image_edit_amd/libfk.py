@@ -12,6 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FK_LIB_PATH") or os.path.join(_HERE, "libfk_gfx950.so")
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+c_f64 = ctypes.c_double
+
+# include/fk.h: slots of the Prodigy state buffer (fp64, on the device)
+FK_PRODIGY_SLOTS = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "dlr", "k", "skipped", "sum_dot", "sum_abs")
 
 FK_SPLITK_SLOT_BYTES = 256 * 256 * 4 + 8   # include/fk.h: one fp32 partial tile + its (counter, flag) words
 FK_EPI_NONE, FK_EPI_GELU_TANH, FK_EPI_SILU, FK_EPI_GATE_RES, FK_EPI_RES, FK_EPI_SCALE, FK_EPI_QKV = range(7)
@@ -191,6 +195,12 @@ SIGNATURES = {
     "fk_sumsq": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "fk_adamw_step": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp] + [c_f32] * 6 + [c_i32, c_i64, c_vp]),
     "fk_adamw_step_scaled": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp] + [c_f32] * 7 + [c_i32, c_i64, c_vp]),
+    "fk_prodigy_ws_doubles": (c_i64, []),
+    "fk_prodigy_begin": (c_i32, [c_vp] + [c_f64] * 4 + [c_i32, c_vp]),
+    "fk_prodigy_moments": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp] + [c_f32] * 6 + [c_f64, c_i32, c_i32,
+                                                                                                         c_i64, c_vp, c_vp]),
+    "fk_prodigy_update_d": (c_i32, [c_vp, c_f64, c_f64, c_f64, c_vp]),
+    "fk_prodigy_apply": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_i32, c_i64, c_vp]),
     "fk_euler_step_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "fk_euler_inpaint_step_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32,
                                            c_f32, c_f32, c_vp]),

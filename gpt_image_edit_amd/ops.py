@@ -1451,3 +1451,104 @@ def adamw_step(master, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), 
     if param_bf16 is not None:
         param_tree.note_raw_write()      # a parameter changed behind torch's version counters
     return master
+
+
+# ---- Prodigy (include/fk.h "Prodigy"; csrc/prodigy.hip): begin, moments per tensor, update_d, apply per tensor ----------
+def _as_f32(x):
+    return ctypes.c_float(float(x)).value
+
+
+def prodigy_beta3(betas, beta3=None):
+    """beta3 (None: sqrt(beta2)) as the kernels see it.  Betas cross the ABI as fp32 in the streaming kernels, so the scalar kernel is
+    given the same fp32 values: the whole step runs with ONE set of numbers."""
+    import math
+    return _as_f32(math.sqrt(float(betas[1])) if beta3 is None else beta3)
+
+
+def prodigy_init_state(d0=1e-6, device="cuda"):
+    """The fp64 scalar buffer of a fresh optimiser: d = d_max = d0, everything else 0 (slots: ``libfk.FK_PRODIGY_SLOTS``)."""
+    if not d0 > 0:
+        raise ValueError("prodigy: d0 must be positive")
+    buf = torch.zeros(len(libfk.FK_PRODIGY_SLOTS), dtype=torch.float64)
+    buf[0] = buf[1] = float(d0)
+    return buf.to(device)
+
+
+def prodigy_ws(device):
+    """The fp64 workspace of ``prodigy_moments`` (per-block partials); calls that share one must be ordered on one stream."""
+    return torch.empty(libfk.load().fk_prodigy_ws_doubles(), dtype=torch.float64, device=device)
+
+
+def _prodigy_buf(state):
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.numel() < len(libfk.FK_PRODIGY_SLOTS):
+        raise TypeError(f"the Prodigy state buffer is a contiguous fp64 tensor of >= {len(libfk.FK_PRODIGY_SLOTS)} elements")
+
+
+def prodigy_begin(state, lr=1.0, betas=(0.9, 0.99), beta3=None, use_bias_correction=True):
+    """Step 1: dlr = d * lr * bias correction (from the device-side step count), numerator decay, running sums zeroed."""
+    _need_cuda(state)
+    _prodigy_buf(state)
+    libfk.check(libfk.load().fk_prodigy_begin(_ptr(state), float(lr), _as_f32(betas[0]), _as_f32(betas[1]), prodigy_beta3(betas, beta3),
+                                              int(bool(use_bias_correction)), _stream()), "fk_prodigy_begin")
+    return state
+
+
+def prodigy_moments(master, p0, grad, m, v, s, state, betas=(0.9, 0.99), beta3=None, weight_decay=0.0, d0=1e-6, decouple=True,
+                    safeguard_warmup=True, grad_sumsq=None, max_grad_norm=1.0, grad_scale=1.0, ws=None):
+    """Step 2 for one tensor / chunk: ``m``, ``v``, ``s`` in place, this tensor's ``sum g (p0 - p)`` and ``sum |s|`` added to the
+    running sums of ``state`` (fixed order, no atomics).  ``grad_sumsq`` / ``max_grad_norm`` / ``grad_scale`` as ``adamw_step``."""
+    _need_cuda(master, p0, grad, m, v, s, state, grad_sumsq, ws)
+    _prodigy_buf(state)
+    for t, what in ((master, "master"), (p0, "p0"), (m, "m"), (v, "v"), (s, "s")):
+        _f32c(t, what)
+        if t.numel() != master.numel():
+            raise ValueError(f"{what}: {t.numel()} elements, the parameter has {master.numel()}")
+    if grad.dtype not in (torch.float32, BF16) or not grad.is_contiguous() or grad.numel() != master.numel():
+        raise TypeError("grad must be a contiguous fp32 / bf16 tensor of the parameter's size")
+    lib = libfk.load()
+    if ws is None:
+        ws = torch.empty(lib.fk_prodigy_ws_doubles(), dtype=torch.float64, device=master.device)
+    elif ws.dtype != torch.float64 or ws.numel() < lib.fk_prodigy_ws_doubles():
+        raise ValueError("ws: fk_prodigy_ws_doubles() fp64 elements")
+    libfk.check(lib.fk_prodigy_moments(_ptr(master), _ptr(p0), _ptr(grad), int(grad.dtype == BF16), _ptr(m), _ptr(v), _ptr(s),
+                                       _ptr(state), _ptr(grad_sumsq), float(max_grad_norm), float(grad_scale), float(betas[0]),
+                                       float(betas[1]), prodigy_beta3(betas, beta3), float(weight_decay), float(d0),
+                                       int(bool(decouple)), int(bool(safeguard_warmup)), master.numel(), _ptr(ws), _stream()),
+                "fk_prodigy_moments")
+    return state
+
+
+def prodigy_update_d(state, d0=1e-6, d_coef=1.0, growth_rate=float("inf")):
+    """Steps 3 and 4 on the running sums (after an all-reduce: the global ones); sets the skipped flag on a zero denominator."""
+    _need_cuda(state)
+    _prodigy_buf(state)
+    libfk.check(libfk.load().fk_prodigy_update_d(_ptr(state), float(d0), float(d_coef), float(growth_rate), _stream()),
+                "fk_prodigy_update_d")
+    return state
+
+
+def prodigy_apply(master, m, v, state, eps=1e-8, weight_decay=0.0, decouple=True, param_bf16=None):
+    """Step 5 for one tensor / chunk: the fp32 ``master`` and its bf16 copy together; a no-op when the step was skipped."""
+    _need_cuda(master, m, v, state, param_bf16)
+    _prodigy_buf(state)
+    for t, what in ((master, "master"), (m, "m"), (v, "v")):
+        _f32c(t, what)
+        if t.numel() != master.numel():
+            raise ValueError(f"{what}: {t.numel()} elements, the parameter has {master.numel()}")
+    if param_bf16 is not None and (param_bf16.dtype != BF16 or not param_bf16.is_contiguous() or param_bf16.numel() != master.numel()):
+        raise TypeError("param_bf16 must be a contiguous bf16 tensor of the parameter's size")
+    libfk.check(libfk.load().fk_prodigy_apply(_ptr(master), _ptr(param_bf16), _ptr(m), _ptr(v), _ptr(state), float(eps),
+                                              float(weight_decay), int(bool(decouple)), master.numel(), _stream()), "fk_prodigy_apply")
+    if param_bf16 is not None:
+        param_tree.note_raw_write()      # a parameter changed behind torch's version counters
+    return master
+
+
+def prodigy_state(buf):
+    """The scalars of a Prodigy state buffer as a dict of python floats (``d``, ``d_max``, ``d_numerator``, ``d_denom``, ``d_hat``,
+    ``dlr``, ``k``, ``skipped``, ``sum_dot``, ``sum_abs``) -- the ONE call of the family that synchronises, for logging ``d * lr``
+    as the reference does (train_denoiser.py:1364-1373)."""
+    vals = buf.detach().cpu().tolist()
+    out = dict(zip(libfk.FK_PRODIGY_SLOTS, vals))
+    out["k"], out["skipped"] = int(out["k"]), bool(out["skipped"])
+    return out

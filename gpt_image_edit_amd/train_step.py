@@ -27,19 +27,25 @@ With ``lora=adapter_name`` the step trains a LoRA adapter's factors instead of t
 forward and backward on the merged weights, each target weight's ``dW`` projected onto ``up`` / ``down`` as its block emits it
 (``fk_lora_grad_bf16``), AdamW on fp32 masters of the factors, then one re-merge per touched weight from its saved base.  The
 optimiser state is 12 bytes per ADAPTER parameter and only one block's ``dW`` is alive at a time.
+
+With ``optimizer="prodigy"`` the optimiser pass is Prodigy instead of AdamW (the reference's ``optimizer: 'prodigy'``,
+``train_denoiser.py:603-624``; ``csrc/prodigy.hip``): ``fk_sumsq``, ``fk_prodigy_begin``, ``fk_prodigy_moments`` over the sorted names,
+``fk_prodigy_update_d``, ``fk_prodigy_apply`` over the same names.  The step size ``d`` and every other scalar stay on the device;
+the state per tensor is ``(master, m, v, s, p0)``.  The same code serves ``lora=`` and ``sharded=True``.
 """
 import torch
 
 from . import helpers, ops
 from .backward import FluxBackward
+from .zero import PRODIGY_SLOTS, resolve_optimizer
 
 BF16 = torch.bfloat16
 
 
 class DenoiserTrainStep:
-    def __init__(self, model, lr=1e-6, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, trainable=None,
+    def __init__(self, model, lr=None, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, trainable=None,
                  sharded=False, group=None, store_activations="auto", projector=None, keep_grads=True, bucket_numel=None,
-                 lora=None):
+                 lora=None, optimizer="adamw", prodigy=None):
         """sharded=True: the optimiser state lives in ``zero.ShardedAdamW`` (ZeRO-2: one flat bf16 parameter buffer the
         model's trainable tensors become views of, fp32 gradients reduce-scattered over the data-parallel ranks, this
         rank's slice of master + moments updated, parameters all-gathered); works unchanged with one process.
@@ -49,7 +55,13 @@ class DenoiserTrainStep:
         loaded from a file -- the same code).  The forward and backward are launch for launch the ones above on the merged
         weights, with only the adapter's target weights in the wgrad set; each block's ``dW`` is projected onto the factors as it is
         emitted (``fk_lora_grad_bf16``) and dropped.  The trainable parameters are ``<module>.lora_A.weight`` (down) and
-        ``<module>.lora_B.weight`` (up); other active adapters stay merged and frozen.  Not with ``sharded=True``."""
+        ``<module>.lora_B.weight`` (up); other active adapters stay merged and frozen.  Not with ``sharded=True``.
+        optimizer="adamw" | "prodigy" (the reference's ``optimizer`` key, train_denoiser.py:595-624): Prodigy estimates its step
+        size ``d`` on the fly (``csrc/prodigy.hip``; two more fp32 state tensors, ``s`` and the initial point ``p0``);
+        ``prodigy=dict(beta3=, d0=, d_coef=, growth_rate=, use_bias_correction=, safeguard_warmup=, decouple=)`` overrides its
+        defaults (the reference config's: the three flags True).  ``lr=None`` is 1e-6 for AdamW and 1.0 for Prodigy; Prodigy
+        with ``lr <= 0.1`` is refused as the reference refuses it (:609-612)."""
+        self.optimizer, lr, self.prodigy = resolve_optimizer(optimizer, lr, prodigy)
         self.model = model
         self.projector = projector
         self.lora = lora
@@ -69,7 +81,9 @@ class DenoiserTrainStep:
         self.bw = FluxBackward(model, trainable, store_activations=store_activations, lora=lora)
         self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
         self.step_count = 0
-        self.state = {}     # name -> (fp32 master, exp_avg, exp_avg_sq)
+        self.state = {}     # name -> (fp32 master, exp_avg, exp_avg_sq); Prodigy: (master, m, v, s, p0)
+        self.pstate = None  # Prodigy: the fp64 scalar buffer on the device (include/fk.h FK_PRODIGY_*), created at the first step
+        self._pws = None
         self.opt = None
         self.keep_grads = keep_grads
         self._sunk = {}     # name -> (data_ptr, version) of the gradients already handed to the sharded optimiser
@@ -80,7 +94,8 @@ class DenoiserTrainStep:
             # its last block is done and runs under the backward of the earlier blocks (zero2.json: overlap_comm)
             self.opt = ShardedAdamW({k: self._param(k).data for k in names}, lr=lr, betas=betas, eps=eps,
                                     weight_decay=weight_decay, max_grad_norm=max_grad_norm, group=group,
-                                    order=backward_order(names), bucket_numel=bucket_numel or DEFAULT_BUCKET)
+                                    order=backward_order(names), bucket_numel=bucket_numel or DEFAULT_BUCKET,
+                                    **({} if self.optimizer == "adamw" else dict(optimizer=self.optimizer, prodigy=self.prodigy)))
             for k in names:
                 self._param(k).data = self.opt.params[k]     # the forward now reads views of the flat buffer
             model._packed = None
@@ -138,6 +153,8 @@ class DenoiserTrainStep:
             p = self._param(name)
             st = (p.detach().float().contiguous(), torch.zeros(p.shape, device=p.device, dtype=torch.float32),
                   torch.zeros(p.shape, device=p.device, dtype=torch.float32))
+            if self.optimizer == "prodigy":     # + s and the point the distance estimate is measured from
+                st = st + (torch.zeros(p.shape, device=p.device, dtype=torch.float32), st[0].clone())
             self.state[name] = st
         return st
 
@@ -270,6 +287,11 @@ class DenoiserTrainStep:
             return norm * norm
         sumsq = ops.sumsq([grads[k].contiguous() for k in names])
         self.step_count += 1
+        if self.optimizer == "prodigy":
+            self._prodigy_step(names, grads, sumsq)
+            self._lora_remerge()
+            self.bw.refresh()
+            return sumsq
         for k in names:
             master, m1, m2 = self._state(k)
             ops.adamw_step(master, grads[k].contiguous(), m1, m2, self.step_count, self.lr, self.betas, self.eps,
@@ -277,6 +299,40 @@ class DenoiserTrainStep:
         self._lora_remerge()
         self.bw.refresh()
         return sumsq
+
+    def _prodigy_step(self, names, grads, sumsq):
+        """begin, moments over the sorted names (their two sums accumulate on the device in that order), update_d, apply over the
+        same names.  Nothing is read back: ``d``, the step count of the bias correction and the zero-gradient rule are device-side."""
+        hp = self.prodigy
+        dev = grads[names[0]].device
+        if self.pstate is None:
+            self.pstate = ops.prodigy_init_state(hp["d0"], dev)
+        if self._pws is None:
+            self._pws = ops.prodigy_ws(dev)
+        ops.prodigy_begin(self.pstate, self.lr, self.betas, hp["beta3"], hp["use_bias_correction"])
+        for k in names:
+            master, m, v, s, p0 = self._state(k)
+            ops.prodigy_moments(master, p0, grads[k].contiguous(), m, v, s, self.pstate, betas=self.betas, beta3=hp["beta3"],
+                                weight_decay=self.weight_decay, d0=hp["d0"], decouple=hp["decouple"],
+                                safeguard_warmup=hp["safeguard_warmup"], grad_sumsq=sumsq, max_grad_norm=self.max_grad_norm,
+                                ws=self._pws)
+        ops.prodigy_update_d(self.pstate, hp["d0"], hp["d_coef"], hp["growth_rate"])
+        for k in names:
+            master, m, v, _, _ = self._state(k)
+            ops.prodigy_apply(master, m, v, self.pstate, eps=self.eps, weight_decay=self.weight_decay, decouple=hp["decouple"],
+                              param_bf16=self._param(k).data)
+
+    def prodigy_state(self):
+        """The Prodigy scalars (``d``, ``dlr``, ``k``, ...; ``ops.prodigy_state``) as python numbers -- this synchronises; log
+        ``d * lr`` from it as the reference does (train_denoiser.py:1364-1373)."""
+        if self.optimizer != "prodigy":
+            raise RuntimeError("prodigy_state(): the optimiser is " + self.optimizer)
+        if self.opt is not None:
+            return self.opt.prodigy_state()
+        if self.pstate is None:
+            d0 = float(self.prodigy["d0"])
+            return dict(zip(PRODIGY_SLOTS, [d0, d0] + [0.0] * 4 + [0, False, 0.0, 0.0]))
+        return ops.prodigy_state(self.pstate)
 
     def _lora_remerge(self):
         """The factors changed: re-merge exactly the weights the trained adapter touches, one launch each, from their bases.  The
@@ -303,8 +359,13 @@ class DenoiserTrainStep:
         this rank (``zero.ShardedAdamW.state_dict``) or, unsharded, the per-tensor fp32 masters and moments."""
         if self.opt is not None:
             return dict(kind="sharded", opt=self.opt.state_dict())
-        return dict(kind="lora" if self.lora is not None else "per_tensor", step=self.step_count,
-                    state={k: tuple(t.detach().cpu().clone() for t in st) for k, st in self.state.items()})
+        sd = dict(kind="lora" if self.lora is not None else "per_tensor", step=self.step_count,
+                  state={k: tuple(t.detach().cpu().clone() for t in st) for k, st in self.state.items()})
+        if self.optimizer == "prodigy":      # an AdamW state keeps exactly the keys it had
+            sd.update(optimizer="prodigy", hp=dict(self.prodigy, lr=self.lr, betas=tuple(self.betas), eps=self.eps,
+                                                   weight_decay=self.weight_decay),
+                      scalars=None if self.pstate is None else self.pstate.detach().cpu().clone())
+        return sd
 
     @torch.no_grad()
     def load_state_dict(self, sd):
@@ -314,6 +375,9 @@ class DenoiserTrainStep:
             raise ValueError("optimiser state was saved with another `sharded` setting")
         if (sd.get("kind") == "lora") != (self.lora is not None):
             raise ValueError("optimiser state was saved with another `lora` setting")
+        saved_opt = (sd["opt"] if self.opt is not None else sd).get("optimizer", "adamw")
+        if saved_opt != self.optimizer:
+            raise ValueError(f"optimiser state was saved by optimizer={saved_opt!r}, this step runs optimizer={self.optimizer!r}")
         self._sunk = {}
         if self.opt is not None:
             self.opt.load_state_dict(sd["opt"])
@@ -321,10 +385,14 @@ class DenoiserTrainStep:
         else:
             self.step_count = int(sd["step"])
             self.state = {}
-            for k, (master, m1, m2) in sd["state"].items():
+            for k, st in sd["state"].items():
                 p = self._param(k)
-                self.state[k] = tuple(t.to(p.device) for t in (master, m1, m2))
+                if len(st) != (5 if self.optimizer == "prodigy" else 3):
+                    raise ValueError(f"{k}: {len(st)} state tensors do not fit optimizer={self.optimizer!r}")
+                self.state[k] = tuple(t.to(p.device) for t in st)
                 p.data.copy_(self.state[k][0])
+            if self.optimizer == "prodigy":
+                self.pstate = None if sd["scalars"] is None else sd["scalars"].to(self.model.device)
         self._lora_remerge()
         self.bw.refresh()
         self.model._packed = None

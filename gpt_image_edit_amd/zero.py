@@ -22,6 +22,10 @@ This module is that exchange written for one process per GPU over ``torch.distri
     the bf16 chunk straight into its place in the flat parameter buffer; ``all_gather_into_tensor`` per bucket, IN
     PLACE (the send buffer is the rank's chunk of the receive buffer; nothing is cloned).
 
+  * ``optimizer="prodigy"``: two more fp32 chunks per rank (``s`` and the initial point ``p0``) and a fp64 scalar buffer;
+    ``step()`` runs ``fk_prodigy_moments`` per bucket chunk, sums the two running sums over the ranks as ONE 2-double
+    all-reduce, then ``fk_prodigy_update_d`` (every rank computes the same ``d``) and ``fk_prodigy_apply`` per chunk.
+
 The tensors the forward pass reads are views of the flat bf16 buffer.  The arithmetic is injected (``kernels``): the
 default is ``gpt_image_edit_amd.ops`` (HIP, no fallback); the world-size-2 CPU tests pass a torch stand-in of their own.
 Unmeasured on hardware so far: no multi-GPU node was available to the builder.
@@ -29,10 +33,40 @@ Unmeasured on hardware so far: no multi-GPU node was available to the builder (D
 import torch
 import torch.distributed as dist
 
-__all__ = ["FlatLayout", "ShardedAdamW", "backward_order"]
+__all__ = ["FlatLayout", "ShardedAdamW", "backward_order", "resolve_optimizer"]
 
 ALIGN = 64                      # elements: every chunk starts on a 256-byte (fp32) boundary
 DEFAULT_BUCKET = 540_000_000    # zero2.json: reduce_bucket_size 5.4e8
+
+
+PRODIGY_SLOTS = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "dlr", "k", "skipped", "sum_dot", "sum_abs")   # include/fk.h
+PRODIGY_DEFAULTS = dict(beta3=None, d0=1e-6, d_coef=1.0, growth_rate=float("inf"), use_bias_correction=True,
+                        safeguard_warmup=True, decouple=True)     # the reference config's (configuration_denoise.py:49-55)
+
+
+def resolve_optimizer(optimizer, lr, prodigy):
+    """(optimizer, lr, Prodigy hyper-parameters or None) after the defaults and refusals of the training seam
+    (train_denoiser.py:595-624): ``lr=None`` is 1e-6 for AdamW and 1.0 for Prodigy, Prodigy wants ``lr`` around 1."""
+    if optimizer not in ("adamw", "prodigy"):
+        raise ValueError(f"optimizer must be 'adamw' or 'prodigy', got {optimizer!r}")
+    if optimizer == "adamw":
+        if prodigy is not None:
+            raise ValueError("prodigy= holds Prodigy's hyper-parameters; the optimiser is 'adamw'")
+        return optimizer, (1e-6 if lr is None else lr), None
+    lr = 1.0 if lr is None else lr
+    if lr <= 0.1:
+        raise ValueError(f"optimizer='prodigy' estimates the step size itself and wants lr around 1.0; lr = {lr} (<= 0.1) would "
+                         "scale that estimate down")
+    hp = dict(PRODIGY_DEFAULTS)
+    unknown = sorted(set(prodigy or {}) - set(hp))
+    if unknown:
+        raise ValueError("prodigy=: unknown keys " + ", ".join(unknown) + "; known: " + ", ".join(sorted(hp)))
+    hp.update(prodigy or {})
+    if not hp["d0"] > 0 or not hp["d_coef"] > 0 or not hp["growth_rate"] > 1.0:
+        raise ValueError("prodigy=: d0 and d_coef must be positive and growth_rate above 1")
+    if hp["beta3"] is not None and not 0.0 <= hp["beta3"] < 1.0:
+        raise ValueError("prodigy=: beta3 must lie in [0, 1)")
+    return optimizer, lr, hp
 
 
 def backward_order(names):
@@ -119,15 +153,21 @@ class _Done:
 
 
 class ShardedAdamW:
-    def __init__(self, params, lr=1e-6, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, kernels=None,
-                 group=None, order=None, bucket_numel=DEFAULT_BUCKET, stage_always=False, average_micro_batches=True):
+    def __init__(self, params, lr=None, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, kernels=None,
+                 group=None, order=None, bucket_numel=DEFAULT_BUCKET, stage_always=False, average_micro_batches=True,
+                 optimizer="adamw", prodigy=None):
         """``params``: dict name -> bf16 tensor (the trainable subset, e.g. ``training.trainable_names``).  After
         construction ``self.params`` holds views of ONE flat bf16 buffer that replace them in the model.  ``order``:
         the names in the order their gradients become available (``backward_order``); default: sorted.
         ``stage_always``: keep the staging buffers on one rank too (tests of the multi-rank intake on one process).
         ``average_micro_batches``: with gradient accumulation (``begin_micro_batch`` between backward passes, the
         reference's ``gradient_accumulation_steps``) the step uses the MEAN over the micro-batches, as
-        ``accelerator.backward`` does by dividing every loss by the accumulation count; False: their sum."""
+        ``accelerator.backward`` does by dividing every loss by the accumulation count; False: their sum.
+        ``optimizer="prodigy"`` (+ ``prodigy=dict(...)``, ``resolve_optimizer``): two more fp32 chunks per rank (``s`` and the
+        initial point ``p0``) and a fp64 scalar buffer; ``step()`` then runs ``prodigy_begin``, ``prodigy_moments`` per bucket chunk,
+        ONE all-reduce (SUM) of the two running sums, ``prodigy_update_d``, ``prodigy_apply`` per chunk and the all-gather as for
+        AdamW.  ``lr=None``: 1e-6 for AdamW, 1.0 for Prodigy."""
+        self.optimizer, lr, self.prodigy = resolve_optimizer(optimizer, lr, prodigy)
         self.group = group
         on = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(group) if on else 1
@@ -148,6 +188,11 @@ class ShardedAdamW:
         self.exp_avg = torch.zeros_like(self.master)
         self.exp_avg_sq = torch.zeros_like(self.master)
         self.grad_slice = torch.zeros_like(self.master)
+        self.s = self.p0 = self.pstate = self._pws = None
+        if self.optimizer == "prodigy":
+            self.s, self.p0 = torch.zeros_like(self.master), self.master.clone()
+            self.pstate = self._fresh_pstate(dev)
+            self._pws = self.k.prodigy_ws(dev) if hasattr(self.k, "prodigy_ws") else None
         # two alternating fp32 staging buffers: bucket b fills while bucket b - 1 is on the wire.  One rank: nothing goes on a
         # wire and a bucket's chunk is the bucket -- gradients are cast straight into `grad_slice`, no staging, no copy
         self.direct = self.world == 1 and not stage_always
@@ -162,6 +207,19 @@ class ShardedAdamW:
         self._host_staged = self.world > 1 and dev.type == "cuda" and dist.get_backend(group) == "gloo"
         self._acc_tmp = []            # world > 1, micro-batch >= 2: reduce-scatter targets that are then ADDED to grad_slice
         self._begin()
+
+    def _fresh_pstate(self, dev):
+        buf = torch.zeros(len(PRODIGY_SLOTS), dtype=torch.float64)
+        buf[0] = buf[1] = float(self.prodigy["d0"])
+        return buf.to(dev)
+
+    def prodigy_state(self):
+        """The Prodigy scalars as python numbers (a host synchronisation; identical on every rank after a step)."""
+        if self.optimizer != "prodigy":
+            raise RuntimeError("prodigy_state(): the optimiser is " + self.optimizer)
+        out = dict(zip(PRODIGY_SLOTS, self.pstate.detach().cpu().tolist()))
+        out["k"], out["skipped"] = int(out["k"]), bool(out["skipped"])
+        return out
 
     # ---- gradient intake ---------------------------------------------------------------------------------------------
     def _begin(self):
@@ -332,9 +390,13 @@ class ShardedAdamW:
         """THIS RANK's shard of the optimiser state (``accelerator.save_state`` under ZeRO-2 writes one file per rank too,
         train_denoiser.py:1229): fp32 master chunk, both Adam moments, the step count, hyper-parameters and the layout
         signature.  The bf16 parameters are not part of it -- they are bf16(master) and are rebuilt on load."""
-        return dict(version=1, rank=self.rank, signature=self.layout_signature(), step=self.step_count,
-                    master=self.master.detach().cpu().clone(), exp_avg=self.exp_avg.detach().cpu().clone(),
-                    exp_avg_sq=self.exp_avg_sq.detach().cpu().clone(), hp=dict(self.hp), max_grad_norm=self.max_grad_norm)
+        sd = dict(version=1, rank=self.rank, signature=self.layout_signature(), step=self.step_count,
+                  master=self.master.detach().cpu().clone(), exp_avg=self.exp_avg.detach().cpu().clone(),
+                  exp_avg_sq=self.exp_avg_sq.detach().cpu().clone(), hp=dict(self.hp), max_grad_norm=self.max_grad_norm)
+        if self.optimizer == "prodigy":      # + the two further chunks and the scalars; an AdamW shard keeps exactly its keys
+            sd.update(optimizer="prodigy", prodigy=dict(self.prodigy), s=self.s.detach().cpu().clone(),
+                      p0=self.p0.detach().cpu().clone(), scalars=self.pstate.detach().cpu().clone())
+        return sd
 
     @torch.no_grad()
     def load_state_dict(self, sd):
@@ -351,8 +413,11 @@ class ShardedAdamW:
                              f"now world {self.world} / {len(self.layout.names)} tensors; re-sharding is not supported")
         if sd["rank"] != self.rank:
             raise ValueError(f"shard of rank {sd['rank']} loaded on rank {self.rank}")
+        if sd.get("optimizer", "adamw") != self.optimizer:
+            raise ValueError(f"optimiser shard was saved by optimizer={sd.get('optimizer', 'adamw')!r}, this one runs "
+                             f"optimizer={self.optimizer!r}")
         self.zero_grad()
-        for name in ("master", "exp_avg", "exp_avg_sq"):
+        for name in ("master", "exp_avg", "exp_avg_sq") + (("s", "p0") if self.optimizer == "prodigy" else ()):
             t = sd[name]
             if t.shape != getattr(self, name).shape or t.dtype != torch.float32:
                 raise ValueError(f"{name}: saved {tuple(t.shape)} {t.dtype}, expected {tuple(getattr(self, name).shape)} float32")
@@ -360,6 +425,11 @@ class ShardedAdamW:
         self.step_count = int(sd["step"])
         self.hp = dict(sd["hp"])
         self.max_grad_norm = sd["max_grad_norm"]
+        if self.optimizer == "prodigy":
+            if sd["scalars"].shape != self.pstate.shape or sd["scalars"].dtype != torch.float64:
+                raise ValueError("scalars: not a Prodigy state buffer")
+            self.prodigy = dict(sd["prodigy"])
+            self.pstate.copy_(sd["scalars"])
         L = self.layout
         works = []
         for b, bk in enumerate(L.buckets):
@@ -387,8 +457,10 @@ class ShardedAdamW:
         self.load_state_dict(torch.load(self.shard_file(directory, self.rank, self.world), map_location="cpu", weights_only=False))
 
     def state_bytes(self):
-        """(replicated, sharded) bytes this rank holds for the optimiser: flat bf16 params + fp32 staging | 4 fp32 chunks."""
-        return self.layout.total * 2 + sum(s.numel() for s in self.staging) * 4, self.layout.slice_numel * 4 * 4
+        """(replicated, sharded) bytes this rank holds for the optimiser: flat bf16 params + fp32 staging | 4 fp32 chunks
+        (master, both moments, the reduced gradient); Prodigy: 6 (+ ``s`` and ``p0``)."""
+        chunks = 6 if self.optimizer == "prodigy" else 4
+        return self.layout.total * 2 + sum(s.numel() for s in self.staging) * 4, self.layout.slice_numel * 4 * chunks
 
     @torch.no_grad()
     def step(self):
@@ -409,9 +481,18 @@ class ShardedAdamW:
         self.last_grad_norm = sumsq.sqrt() * scale
         self.step_count += 1
         works = []
+        if self.optimizer == "prodigy":
+            self._prodigy_moments_and_d(sumsq, scale)
         for b, bk in enumerate(L.buckets):
             so, ch = bk["state_offset"], bk["chunk"]
             mine = L.chunk_of(self.flat_param, b, self.rank)
+            if self.optimizer == "prodigy":
+                self.k.prodigy_apply(self.master[so:so + ch], self.exp_avg[so:so + ch], self.exp_avg_sq[so:so + ch], self.pstate,
+                                     eps=self.hp["eps"], weight_decay=self.hp["weight_decay"], decouple=self.prodigy["decouple"],
+                                     param_bf16=mine)
+                if self.world > 1:
+                    works.append(self._all_gather(L.bucket_view(self.flat_param, b), mine))
+                continue
             self.k.adamw_step(self.master[so:so + ch], self.grad_slice[so:so + ch], self.exp_avg[so:so + ch],
                               self.exp_avg_sq[so:so + ch], self.step_count,
                               grad_sumsq=sumsq if self.max_grad_norm is not None else None,
@@ -423,3 +504,28 @@ class ShardedAdamW:
             w.wait()
         self._begin()
         return self.last_grad_norm
+
+    def _prodigy_moments_and_d(self, sumsq, scale):
+        """The first pass of a Prodigy step and the scalar update between the passes: the two running sums of this rank's chunks
+        (padding elements have a zero gradient, zero ``s`` and ``p0 == p``: they add nothing) are summed over the ranks as ONE
+        2-double all-reduce, so every rank computes the same ``d``."""
+        hp, pr = self.hp, self.prodigy
+        self.k.prodigy_begin(self.pstate, hp["lr"], hp["betas"], pr["beta3"], pr["use_bias_correction"])
+        for bk in self.layout.buckets:
+            so, ch = bk["state_offset"], bk["chunk"]
+            self.k.prodigy_moments(self.master[so:so + ch], self.p0[so:so + ch], self.grad_slice[so:so + ch],
+                                   self.exp_avg[so:so + ch], self.exp_avg_sq[so:so + ch], self.s[so:so + ch], self.pstate,
+                                   betas=hp["betas"], beta3=pr["beta3"], weight_decay=hp["weight_decay"], d0=pr["d0"],
+                                   decouple=pr["decouple"], safeguard_warmup=pr["safeguard_warmup"],
+                                   grad_sumsq=sumsq if self.max_grad_norm is not None else None,
+                                   max_grad_norm=self.max_grad_norm if self.max_grad_norm is not None else 0.0,
+                                   grad_scale=scale, ws=self._pws)
+        if self.world > 1:
+            sums = self.pstate[PRODIGY_SLOTS.index("sum_dot"): PRODIGY_SLOTS.index("sum_abs") + 1]
+            if self._host_staged:
+                h = sums.cpu()
+                dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
+                sums.copy_(h)
+            else:
+                dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
+        self.k.prodigy_update_d(self.pstate, pr["d0"], pr["d_coef"], pr["growth_rate"])

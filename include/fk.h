@@ -631,6 +631,49 @@ int fk_adamw_step_scaled(float* master, void* param_bf16, const void* grad, int3
                          float* exp_avg_sq, const double* grad_sumsq, float max_grad_norm, float grad_scale, float lr,
                          float beta1, float beta2, float eps, float weight_decay, int32_t step, int64_t n,
                          fk_stream_t stream);
+/* ---- Prodigy (csrc/prodigy.hip): the reference's second optimiser (train_denoiser.py:595-624, `optimizer: 'prodigy'`) on the
+ * same fp32 masters.  One step = fk_prodigy_begin, fk_prodigy_moments per tensor / chunk, [all-reduce of the two running sums
+ * under data parallelism], fk_prodigy_update_d, fk_prodigy_apply per tensor / chunk.  Every scalar lives in a caller-owned
+ * DEVICE buffer of FK_PRODIGY_STATE_DOUBLES doubles; a step reads nothing back to the host.  Initial contents: D = D_MAX = d0,
+ * every other slot 0.  The step (k = state[K], d = state[D]):
+ *   begin     bc = use_bias_correction ? sqrt(1 - beta2^(k+1)) / (1 - beta1^(k+1)) : 1;  DLR = d * lr * bc;
+ *             D_NUMERATOR *= beta3;  SUM_DOT = SUM_ABS = SKIPPED = 0
+ *   moments   g = grad * coef (fk_adamw_step_scaled's clipping / grad_scale coefficient, same arithmetic);  !decouple: g += wd * p;
+ *             SUM_DOT += sum g * (p0 - p);  m = beta1 m + d (1 - beta1) g;  v = beta2 v + d^2 (1 - beta2) g^2;
+ *             s = beta3 s + (d / d0) (safeguard_warmup ? d : DLR) g;  SUM_ABS += sum |s_new|
+ *   update_d  D_NUMERATOR += (d / d0) DLR SUM_DOT;  D_DENOM = SUM_ABS;  D_DENOM == 0: SKIPPED = 1 and nothing else changes; else
+ *             D_HAT = d_coef D_NUMERATOR / D_DENOM;  d == d0: d = max(d, D_HAT);  D_MAX = max(D_MAX, D_HAT);
+ *             D = min(D_MAX, d * growth_rate);  K += 1
+ *   apply     SKIPPED: nothing.  decouple: p += p * (-wd DLR);  p -= DLR * (m / (sqrt(v) + D eps));  bf16 copy of p
+ * Element arithmetic is fp32, the scalar factors are formed in double and rounded once, the sums are double.  The sums have a
+ * fixed order (per-block partials in ws, one finishing block) and use no atomics: two runs give the same bits, and successive
+ * fk_prodigy_moments calls accumulate in call order.  Pointers that are all 16-byte aligned (bf16 ones 8-byte) move as 16-byte
+ * vectors with a scalar tail; anything else goes element by element; any n >= 1.  NULL pointers, n <= 0, grad_scale <= 0,
+ * d0 <= 0, a beta outside [0, 1): FK_EINVAL, nothing launched. */
+enum {
+  FK_PRODIGY_D = 0,           /* step-size estimate */
+  FK_PRODIGY_D_MAX = 1,
+  FK_PRODIGY_D_NUMERATOR = 2,
+  FK_PRODIGY_D_DENOM = 3,
+  FK_PRODIGY_D_HAT = 4,
+  FK_PRODIGY_DLR = 5,         /* d * lr * bias correction of the CURRENT step (what fk_prodigy_apply uses) */
+  FK_PRODIGY_K = 6,           /* steps taken (skipped ones do not count) */
+  FK_PRODIGY_SKIPPED = 7,     /* 1 after fk_prodigy_update_d met D_DENOM == 0 */
+  FK_PRODIGY_SUM_DOT = 8,     /* running sum of g * (p0 - p) of this step */
+  FK_PRODIGY_SUM_ABS = 9,     /* running sum of |s| of this step */
+  FK_PRODIGY_STATE_DOUBLES = 10
+};
+/* Doubles of workspace fk_prodigy_moments needs (two partials per block). */
+int64_t fk_prodigy_ws_doubles(void);
+int fk_prodigy_begin(double* state, double lr, double beta1, double beta2, double beta3, int32_t use_bias_correction,
+                     fk_stream_t stream);
+int fk_prodigy_moments(const float* master, const float* p0, const void* grad, int32_t grad_is_bf16, float* m, float* v,
+                       float* s, double* state, const double* grad_sumsq, float max_grad_norm, float grad_scale, float beta1,
+                       float beta2, float beta3, float weight_decay, double d0, int32_t decouple, int32_t safeguard_warmup,
+                       int64_t n, double* ws, fk_stream_t stream);
+int fk_prodigy_update_d(double* state, double d0, double d_coef, double growth_rate, fk_stream_t stream);
+int fk_prodigy_apply(float* master, void* param_bf16, const float* m, const float* v, const double* state, float eps,
+                     float weight_decay, int32_t decouple, int64_t n, fk_stream_t stream);
 
 /* FlowMatchEulerDiscreteScheduler.step fused with the pipeline's `noise_pred[:, :S_tgt]` slice:
  *   x[b, s, :] = bf16(float(x) + float(bf16(bf16(dsigma) * v[b, s, :])))   for s < S_tgt
