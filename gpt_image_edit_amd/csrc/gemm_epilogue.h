@@ -13,15 +13,18 @@ constexpr int BM = 256;
 // The launcher guarantees that every offset relative to the tile's first row fits 31 bits (in bytes).
 struct TileRows {
   int ld, wrap, rpb, b0, r0;
+  int rf;       // row of the tile's first row inside its batch b0 (= r0, except that one unbatched view counts rows from r0 = 0)
   float inv;    // 1 / rpb when a batch is shorter than a tile
   bool big;     // rpb >= BM (or no batching): a tile crosses at most one batch boundary
-  FK_DEV TileRows(const fk_rows& r, int m0) {
+  // flat (the launcher's mark: row m lies at m * ld, all of the problem in batch 0): no division
+  FK_DEV TileRows(const fk_rows& r, int m0, bool flat = false) {
     ld = (int)r.ld;
-    if (r.rows_per_batch <= 0) { rpb = 0x7fffffff; wrap = 0; b0 = 0; r0 = 0; big = true; inv = 0.f; }
+    if (flat) { rpb = 0x7fffffff; wrap = 0; b0 = 0; r0 = rf = m0; big = true; inv = 0.f; }
+    else if (r.rows_per_batch <= 0) { rpb = 0x7fffffff; wrap = 0; b0 = 0; r0 = 0; rf = m0; big = true; inv = 0.f; }
     else {
       rpb = (int)(r.rows_per_batch > 0x7fffffff ? 0x7fffffff : r.rows_per_batch);
       b0 = (unsigned)m0 / (unsigned)rpb;
-      r0 = m0 - b0 * rpb;
+      r0 = rf = m0 - b0 * rpb;
       wrap = (int)(r.batch_stride - (int64_t)rpb * r.ld);
       big = rpb >= BM;
       inv = 1.0f / (float)rpb;
@@ -37,6 +40,11 @@ struct TileRows {
   }
   // element offset of row ml of the tile relative to its first row
   FK_DEV int off(int ml) const { return ml * ld + crossed(ml) * wrap; }
+  // element offset of the tile's first row: fk_row_offset(r, m0) from this tile's 32-bit quotient (no 64-bit division);
+  // r: what the object was made from
+  FK_DEV int64_t first(const fk_rows& r) const {
+    return (int64_t)b0 * r.batch_stride + (int64_t)rf * r.ld;
+  }
 };
 
 // sum over the 16 lanes of a DPP row, every lane receiving the total: four row-rotate adds on the VALU (no LDS
@@ -95,9 +103,11 @@ FK_DEV void quad_set(f32x16_t& v, int q, const f32x4_t& c) {
 // m-blocks [HALF MF / 2, + MF / 2) are exactly those rows (Cfg8).  -1: the whole tile.  The half-tile forms add the partner's
 // partial sums on the way: other[nf * 2 MF + (mf - first m-block) * 4 + q] = its quad q of block (nf, mf), own + other.
 // UB: chunks per batch of the output loop (gemm_mxfp8.hip's split-K pairs take 4: their accumulators stay allocated beside it).
+// flat: bit 1 / 2 / 3 (gemm_tile_map.h: TM_C_FLAT, TM_R_FLAT, TM_G_FLAT) -- the launcher found the rows of C / the residual at
+// m * ld / every gate row to be row 0: the per-tile divisions of their addressing are skipped.  0: fk_rows addressing throughout.
 template <int EPI, int BN, class C, int HALF = -1, int UB = 8>
 FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& p, char* smem, int m0, int n0,
-                       int wm, int wn, const u32x4_t* other = nullptr) {
+                       int wm, int wn, const u32x4_t* other = nullptr, int flat = 0) {
   constexpr int MF0 = HALF > 0 ? C::MF / 2 : 0, MF1 = HALF == 0 ? C::MF / 2 : C::MF;   // m-blocks stored
   constexpr int row0 = HALF > 0 ? BM / 2 : 0;                                           // first tile row stored
   int tid = threadIdx.x;
@@ -187,14 +197,15 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
   constexpr int U = (EPI == FK_EPI_QKV && (ITERS > 8 || HALF >= 0)) ? 4 : UB;
   static_assert(ITERS % U == 0 && C::NTHREADS % CPR == 0, "epilogue batching");
   // per-tile (scalar) row addressing of the output, the residual and the gate
-  const TileRows crow(p.c, m0);
-  bf16_t* const cbase = (bf16_t*)p.C + fk_row_offset(p.c, m0);
-  const TileRows rrow = (EPI == FK_EPI_GATE_RES || EPI == FK_EPI_RES) ? TileRows(p.r, m0) : crow;
-  const bf16_t* const rbase =
-      (EPI == FK_EPI_GATE_RES || EPI == FK_EPI_RES) ? (const bf16_t*)p.res + fk_row_offset(p.r, m0) : nullptr;
+  constexpr bool HAS_RES = EPI == FK_EPI_GATE_RES || EPI == FK_EPI_RES;
+  const bool cflat = flat & 2, rflat = flat & 4, gflat = flat & 8;
+  const TileRows crow(p.c, m0, cflat);
+  bf16_t* const cbase = (bf16_t*)p.C + crow.first(p.c);
+  const TileRows rrow = HAS_RES ? TileRows(p.r, m0, rflat) : crow;
+  const bf16_t* const rbase = HAS_RES ? (const bf16_t*)p.res + rrow.first(p.r) : nullptr;
   fk_rows gr = {0, 0, 0};
   if constexpr (EPI == FK_EPI_GATE_RES) gr.rows_per_batch = p.gate_rows_per_batch;
-  const TileRows grow(gr, m0);   // b0 + crossed(ml) = the gate row of tile row ml
+  const TileRows grow(gr, m0, gflat);   // b0 + crossed(ml) = the gate row of tile row ml
   const int D = EPI == FK_EPI_QKV ? p.qkv_heads * 128 : 1;
   const int which = EPI == FK_EPI_QKV ? n0 / D : 0;   // 0 = q, 1 = k, 2 = v: a tile never straddles q | k | v
   // a thread keeps its chunk column over the iterations (NTHREADS % CPR == 0): only the row advances

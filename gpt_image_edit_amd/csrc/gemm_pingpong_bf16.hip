@@ -35,7 +35,10 @@
 
 namespace {
 
-#include "gemm_epilogue.h"   // BM, TileRows, row16_sum, xcd_chunk_index, FragMap, store_tile
+#include "gemm_epilogue.h"   // BM, TileRows, row16_sum, FragMap, store_tile
+#define FK_TM_FN __host__ __device__ __forceinline__
+#include "gemm_tile_map.h"   // TileEntry, ProbEntry, tm_tile, tm_xcd_chunk: the tile order as launch constants
+static_assert(TM_MAX_GROUP == FK_MAX_GROUP && TM_BM == BM, "gemm_tile_map.h mirrors fk.h / gemm_epilogue.h");
 #ifndef FK_GROUP_M
 #define FK_GROUP_M 8
 #endif
@@ -49,23 +52,45 @@ constexpr int GROUP_M = FK_GROUP_M;
 // GroupArgs.sk_mode: how the two workgroups of a split-K pair exchange their partial tiles (gemm8_body's rendezvous)
 enum { SK_WHOLE = 0, SK_SYM = 1, SK_SYM_UNANNOUNCED = 2 };
 
+// The kernel arguments.  A workgroup finds its tile from `e` alone (the first cache lines of the segment: one fetch), then
+// fetches pe[pi] -- what its prologue requests need -- and issues them; p[pi] (the epilogue's fields: bias, C, residual,
+// gate, the QKV pointers, alpha) and the split-K words are first read behind those requests.
 struct GroupArgs {
+  TileEntry e;
+  ProbEntry pe[FK_MAX_GROUP];
   fk_gemm_args p[FK_MAX_GROUP];
-  int tiles_before[FK_MAX_GROUP + 1];  // prefix sums of tile counts (mixed launch: of the 256 x 256 tiles)
-  int n;
-  // mixed launch (gemm_mix_kernel): column tiles [0, big_cols) of width 256 are 256 x 256 tiles, the columns from
-  // big_cols * 256 on are 256 x 128 tiles; per XCD (blockIdx % 8) the chunk of each class it works off
-  int big_cols;
-  int small_before[FK_MAX_GROUP + 1];
-  int xcd_big_start[8], xcd_big_cnt[8], xcd_small_start[8];
   // split-K launch (gemm8_kernel<.., SPLITK>): two workgroups per 256 x 256 tile, each over half of K; fp32 partial
   // tiles (256 KiB apiece) and one (ticket, flag) word pair per tile in a caller-owned workspace
   float* sk_partials;
   unsigned* sk_ctl;
   int sk_mode;         // split-K pairs' exchange (SK_* below): whole tile one way, or each workgroup finishes a 128-row half
   int sk_min_part;     // stream-K launch (gemm8_streamk_kernel): the shortest part (in K-tiles) a cut may leave
-  int group_m;         // depth (in row tiles) of the grouped tile order; >= the row-tile count: every XCD owns a column range
 };
+
+
+// ---- diagnostic build only (-DFK_ENTRY_STAMPS; never the shipped library): shader-clock stamps of a workgroup's life ------
+// Wave 0 of every workgroup keeps s_memtime at (0) the kernel's first instruction, (1) behind its first LDS-DMA request, (2) in
+// front of its first MFMA phase, (3) at the K loop's exit and (4) behind its last store, and writes them, with the hardware
+// id, to a buffer of its own (fk_entry_stamps_set; 8 words per workgroup) at the very end.  tools/gemm_entry_stamps.py reads it.
+#ifdef FK_ENTRY_STAMPS
+__device__ unsigned long long* fk_entry_stamp_buf = nullptr;
+struct EntryStamps {
+  unsigned long long t[5];
+  template <int I> FK_DEV void mark() { t[I] = __builtin_amdgcn_s_memtime(); }
+  FK_DEV void flush() const {
+    if (threadIdx.x == 0 && fk_entry_stamp_buf) {
+      unsigned long long* r = fk_entry_stamp_buf + (size_t)blockIdx.x * 8;
+      for (int i = 0; i < 5; ++i) r[i] = t[i];
+      r[5] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);   // HW_ID, XCC_ID
+    }
+  }
+};
+#else
+struct EntryStamps {
+  template <int I> FK_DEV void mark() {}
+  FK_DEV void flush() const {}
+};
+#endif
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;
@@ -106,28 +131,61 @@ FK_DEV void wait_vmcnt() {
 }
 
 
-// tile t of a class of tiles that covers the column tiles [col0 / BN, col0 / BN + nbn) of every problem
-template <int BN>
-FK_DEV void tile_of(const GroupArgs& ga, const int (&before)[FK_MAX_GROUP + 1], int t, int nbn, int col0, int& pi, int& m0,
-                    int& n0) {
-  pi = 0;
-#pragma unroll
-  for (int i = 1; i < FK_MAX_GROUP; ++i)
-    if (i < ga.n && t >= before[i]) pi = i;
-  const fk_gemm_args& p = ga.p[pi];
-  t -= before[pi];
-  const int nbm = (p.M + BM - 1) / BM;
-  const int per_group = ga.group_m * nbn;
-  const int g = t / per_group;
-  const int first_m = g * ga.group_m;
-  const int gm = min(nbm - first_m, ga.group_m);
-  const int rem = t - g * per_group;
-  m0 = (first_m + rem % gm) * BM;
-  n0 = col0 + (rem / gm) * BN;
+// ---- workgroup entry: two fetches ----------------------------------------------------------------------------------------
+// Left to itself hipcc fetches every kernel argument where it is first used, one dependent s_load + wait after the other
+// (7-8 dependent scalar-load waits before the first operand request by tools/gemm_entry_census.py).  These helpers read everything a step
+// needs into plain values FIRST and then hand the values through an empty asm statement: all loads are issued together, one
+// wait, and nothing that follows can be turned back into a load.
+struct Hot {
+  TmHot h;
+  uint32_t xq, xr, grid;
+  int nk;
+};
+#define FK_PIN_CLASS(h)                                                                                                   \
+  "+s"((h).before[0]), "+s"((h).before[1]), "+s"((h).before[2]), "+s"((h).nbm[0]), "+s"((h).nbm[1]), "+s"((h).nbm[2]),       \
+      "+s"((h).nbm[3]), "+s"((h).last_mul[0]), "+s"((h).last_mul[1]), "+s"((h).last_mul[2]), "+s"((h).last_mul[3]),          \
+      "+s"((h).per_group), "+s"((h).col0), "+s"((h).per_group_mul), "+s"((h).group_m_mul)
+#define FK_PIN_HEAD(x) "+s"((x).h.n), "+s"((x).h.group_m), "+s"((x).xq), "+s"((x).xr), "+s"((x).grid), "+s"((x).nk)
+FK_DEV Hot load_hot(const GroupArgs& ga) {
+  Hot x;
+  x.h = tm_hot(ga.e, ga.e.cls[0]);
+  x.xq = ga.e.xq; x.xr = ga.e.xr; x.grid = ga.e.grid; x.nk = ga.e.nk;
+  asm volatile("" : FK_PIN_HEAD(x), FK_PIN_CLASS(x.h));   // ONE statement: one wait for all of it
+  return x;
+}
+// what the prologue requests of a tile need from its problem: the second (and last) fetch in front of them
+FK_DEV ProbEntry load_prob(const GroupArgs& ga, int pi) {
+  ProbEntry q = ga.pe[pi];
+  asm volatile("" : "+s"(q.A), "+s"(q.W), "+s"(q.lda), "+s"(q.ldw), "+s"(q.M), "+s"(q.N), "+s"(q.K), "+s"(q.flags));
+  return q;
 }
 template <int BN>
-FK_DEV void select_tile(const GroupArgs& ga, int t, int& pi, int& m0, int& n0) {
-  tile_of<BN>(ga, ga.tiles_before, t, (ga.p[0].N + BN - 1) / BN, 0, pi, m0, n0);
+FK_DEV void select_tile(const Hot& x, int t, int& pi, int& m0, int& n0) { tm_tile_hot(x.h, BN, t, pi, m0, n0); }
+FK_DEV int xcd_chunk_of(const Hot& x) { return tm_xcd_chunk(x.xq, x.xr, blockIdx.x); }
+
+// Behind a tile's prologue requests: the problem index as a value the compiler cannot trace back, so that no field of
+// p[pi] (the epilogue's) is fetched in front of them.
+FK_DEV int behind_requests(int pi) {
+  pi = __builtin_amdgcn_readfirstlane(pi);   // uniform already; hipcc may have computed it on the vector side (K-major forms)
+  asm volatile("" : "+s"(pi) :: "memory");
+  return pi;
+}
+
+// Element offsets of NR tile rows of A relative to the tile's first row, and that row's offset from A.  Flat rows (one
+// batch, or batches without gaps: the host's ProbEntry.flags): a product per row; otherwise fk_rows addressing from p[pi].a.
+template <int NR>
+FK_DEV int64_t tile_a_rows(const GroupArgs& ga, int pi, const ProbEntry& q, int m0, const int (&rl)[NR], int (&off)[NR]) {
+#pragma unroll
+  for (int i = 0; i < NR; ++i) off[i] = min(rl[i], q.M - 1 - m0) * q.lda;
+  int64_t first = (int64_t)m0 * q.lda;
+  if (__builtin_expect(!(q.flags & TM_A_FLAT), 0)) {
+    const fk_rows& a = ga.p[pi].a;
+    const TileRows arow(a, m0);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) off[i] = arow.off(min(rl[i], q.M - 1 - m0));
+    first = arow.first(a);
+  }
+  return first;
 }
 
 // one 32 (n) x 32 (m) x 32 (k) step on a 32 x 32 accumulator block as four 16 x 16 x 32 MFMAs: w16[n16], a16[m16]
@@ -191,45 +249,51 @@ struct Cfg8 {
 // the sums are those of the LAY 0 kernel on transposed copies bit for bit (attention_fwd.hip's V^T operand is the recipe).
 // SYM (split-K pairs only): this workgroup is part sk_part (0 / 1) of its tile and may finish the 128-row half sk_part of it.
 template <int EPI, int BN, int LAY = 0, bool M16 = false, bool SYM = false>
-FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, int kt_first, int nk, int sk_slot, int sk_part = 0) {
+FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, int kt_first, int nk, int sk_slot, int sk_part = 0, EntryStamps* st = nullptr) {
+  EntryStamps st_none;
+  if (!st) st = &st_none;
   using C = Cfg8<BN, M16>;
   constexpr bool AT = LAY == 2, WT = LAY >= 1;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;   // group = wm; waves w and w + 4 share a SIMD
-  const fk_gemm_args& p = ga.p[pi];
+  const ProbEntry q = load_prob(ga, pi);       // the prologue reads nothing else of its problem
   const int kbase = kt_first * (C::BK * 2);   // byte offset of this workgroup's first K-tile in a (K-contiguous) row
 
   // ---- LDS-DMA sources: piece = 8 rows x 128 B, lane -> (row, slot), source chunk = slot ^ swz(row).
   // Wave w requests pieces 2w and 2w + 1 of every half-tile.
   const int lrow = lane >> 3, slot = lane & 7;
   const int prow = lane >> 4, pslot = lane & 15;   // K-major operands: piece = 4 k-rows x 256 B, lane -> (row, 16-byte chunk)
-  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)((const bf16_t*)p.A + (AT ? (int64_t)m0 : fk_row_offset(p.a, m0))), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)((const bf16_t*)p.W + (WT ? (int64_t)n0 : (int64_t)n0 * p.ldw)), 0, 0x7fffffff, 0x00020000);
-  const BufDesc od_a = make_buf_desc((const bf16_t*)p.A + (AT ? (int64_t)m0 : fk_row_offset(p.a, m0)), 0x7fffffffu);   // K-major forms
-  const BufDesc od_w = make_buf_desc((const bf16_t*)p.W + (WT ? (int64_t)n0 : (int64_t)n0 * p.ldw), 0x7fffffffu);
   int a_voff[2][2], w_voff[2][2];   // [half][piece]
+  int64_t a_first = m0;             // element offset of the tile's first row (K-major A: its first column) from A
   {
-    const TileRows arow(p.a, m0);
-    const int ldw2 = (int)p.ldw * 2, lda2 = (int)p.a.ld * 2;
+    const int ldw2 = q.ldw * 2, lda2 = q.lda * 2;
+    int rls[4], aoff[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rls[i] = (i >> 1) * 128 + (wave * 2 + (i & 1)) * 8 + lrow;   // row inside the 256-row tile
+    if constexpr (!AT) a_first = tile_a_rows<4>(ga, pi, q, m0, rls, aoff);
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int rl = h * 128 + (wave * 2 + j) * 8 + lrow;   // row inside the 256-row tile
+        const int rl = rls[h * 2 + j];
         const int sw = (slot ^ C::swz(rl)) << 4;
         // K-major: k-row kl of the K-tile, logical 16-byte chunk of the half's 128 columns behind physical chunk pslot
         const int kl = (wave * 2 + j) * 4 + prow;
         const int ct = (h * 128 + (((((pslot >> 2) ^ prow) << 2) | (pslot & 3)) << 3)) * 2;
-        a_voff[h][j] = AT ? kl * lda2 + ct : arow.off(min(rl, p.M - 1 - m0)) * 2 + sw;
-        w_voff[h][j] = WT ? kl * ldw2 + ct : min(rl, p.N - 1 - n0) * ldw2 + sw;
+        a_voff[h][j] = AT ? kl * lda2 + ct : aoff[h * 2 + j] * 2 + sw;
+        w_voff[h][j] = WT ? kl * ldw2 + ct : min(rl, q.N - 1 - n0) * ldw2 + sw;
       }
   }
+  const bf16_t* const a_src = (const bf16_t*)q.A + a_first;
+  const bf16_t* const w_src = (const bf16_t*)q.W + (WT ? (int64_t)n0 : (int64_t)n0 * q.ldw);
+  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)a_src, 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)w_src, 0, 0x7fffffff, 0x00020000);
+  const BufDesc od_a = make_buf_desc(a_src, 0x7fffffffu);   // K-major forms
+  const BufDesc od_w = make_buf_desc(w_src, 0x7fffffffu);
   // which: 0 = A0, 1 = A1, 2 = W0, 3 = W1; kt is clamped (surplus requests are never read)
-  const int kstep_a = AT ? C::BK * (int)p.a.ld * 2 : C::BK * 2, kstep_w = WT ? C::BK * (int)p.ldw * 2 : C::BK * 2;
+  const int kstep_a = AT ? C::BK * q.lda * 2 : C::BK * 2, kstep_w = WT ? C::BK * q.ldw * 2 : C::BK * 2;
   auto dma_half = [&](int which, int buf, int kt) {
     const int ktc = min(kt, nk - 1);
     char* dst = smem + buf * C::BUF_BYTES + which * C::HALF_BYTES + wave * 2048;
@@ -253,6 +317,32 @@ FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, 
       }
     }
   };
+
+  // ---- prologue: the seven half-tiles read in phases 0 .. 6, in reading order ------------------------------------
+  dma_half(2, 0, 0);   // W0(0)   read in "phase 0" (below)
+  st->mark<1>();
+  dma_half(0, 0, 0);   // A0(0)   P1 of tile 0
+  dma_half(3, 0, 0);   // W1(0)   P2
+  dma_half(1, 0, 0);   // A1(0)   P3
+  dma_half(2, 1, 1);   // W0(1)   P4
+  dma_half(0, 1, 1);   // A0(1)   P1 of tile 1
+  dma_half(3, 1, 1);   // W1(1)   P2 of tile 1
+  // From here on the epilogue's view of the problem: no field of p[pi] is fetched in front of the requests above (its index
+  // is opaque).  The split-K words (ga.sk_mode, ga.sk_ctl, ga.sk_partials) sit at fixed argument offsets: hipcc is free to
+  // fetch them earlier, at worst folded into the entry's first fetch -- no further wait either way.
+  const fk_gemm_args& p = ga.p[behind_requests(pi)];
+  // split-K pairs: "I am on the chip" (rendezvous below).  Behind the prologue's requests, so the round trip of the add hides
+  // behind theirs; only wave 0 waits for it (for all of its requests instead of the first four), and the value stays scalar.
+  unsigned sk_ann = 0;
+  if constexpr (SYM) {
+    if (ga.sk_mode != SK_WHOLE && wave == 0) {
+      unsigned r = 0;
+      if (lane == 0)
+        r = __hip_atomic_fetch_add((__attribute__((address_space(1))) unsigned*)(ga.sk_ctl + 2 * (size_t)sk_slot), 1u, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+      sk_ann = __builtin_amdgcn_readfirstlane(r);
+    }
+  }
 
   // ---- MFMA operand addressing -----------------------------------------------------------------------------------
   // 32 x 32 x 16: lane -> row (lane & 31), k-octet (lane >> 5) of each of the K-tile's 4 k-steps; 16 x 16 x 32: row (lane & 15),
@@ -339,26 +429,7 @@ FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, 
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // ---- prologue: the seven half-tiles read in phases 0 .. 6, in reading order ------------------------------------
-  dma_half(2, 0, 0);   // W0(0)   read in "phase 0" (below)
-  dma_half(0, 0, 0);   // A0(0)   P1 of tile 0
-  dma_half(3, 0, 0);   // W1(0)   P2
-  dma_half(1, 0, 0);   // A1(0)   P3
-  dma_half(2, 1, 1);   // W0(1)   P4
-  dma_half(0, 1, 1);   // A0(1)   P1 of tile 1
-  dma_half(3, 1, 1);   // W1(1)   P2 of tile 1
-  // split-K pairs: "I am on the chip" (rendezvous below).  Behind the prologue's requests, so the round trip of the add hides
-  // behind theirs; only wave 0 waits for it (for all of its requests instead of the first four), and the value stays scalar.
-  unsigned sk_ann = 0;
-  if constexpr (SYM) {
-    if (ga.sk_mode != SK_WHOLE && wave == 0) {
-      unsigned r = 0;
-      if (lane == 0)
-        r = __hip_atomic_fetch_add((__attribute__((address_space(1))) unsigned*)(ga.sk_ctl + 2 * (size_t)sk_slot), 1u, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-      sk_ann = __builtin_amdgcn_readfirstlane(r);
-    }
-  }
+  // ---- (the prologue's requests were issued above) ----------------------------------------------------------------
   wait_vmcnt<10>();    // W0(0), A0(0) (own pieces) landed
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -366,6 +437,7 @@ FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, 
   read_w(0, 0);
   if (wm == 1) __builtin_amdgcn_s_barrier();   // the stagger: group 1 runs one barrier behind group 0
   __builtin_amdgcn_sched_barrier(0);
+  st->mark<2>();
 
   auto tile_body = [&](auto bc, int kt) {
     constexpr int b = decltype(bc)::value;
@@ -378,6 +450,7 @@ FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, 
     tile_body(std::integral_constant<int, 0>{}, kt);
     if (kt + 1 < nk) tile_body(std::integral_constant<int, 1>{}, kt + 1);
   }
+  st->mark<3>();
   if (wm == 0) __builtin_amdgcn_s_barrier();   // balance the stagger
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // surplus (clamped) requests must not land in the C tile
 
@@ -467,7 +540,7 @@ FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, 
 #pragma unroll
       for (int r = 0; r < NH; ++r)
         other[r] = __builtin_amdgcn_raw_buffer_load_b128(rs_p, tid * 16, (keep * NH + r) * (C::NTHREADS * 16), /*sc1*/ 16);
-      store_tile<EPI, BN, C, keep>(acc, p, smem, m0, n0, wm, wn, other);
+      store_tile<EPI, BN, C, keep>(acc, p, smem, m0, n0, wm, wn, other, q.flags);
     };
     if constexpr (SYM) {
       if (role == 2u) {
@@ -516,22 +589,27 @@ FK_DEV void gemm8_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, 
       //  workgroup, outside the K loop; tests/test_kernel_resources.py budgets exactly that for this instantiation)
     }
   }
-  store_tile<EPI, BN, C>(acc, p, smem, m0, n0, wm, wn);
+  store_tile<EPI, BN, C>(acc, p, smem, m0, n0, wm, wn, nullptr, q.flags);
 }
 
 template <int EPI, int BN, bool SPLITK, int LAY = 0, bool M16 = false>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GroupArgs ga) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  EntryStamps st;
+  st.mark<0>();
   int pi, m0, n0;
-  const int t = xcd_chunk_index();
-  const int nk_all = ga.p[0].K / Cfg8<BN>::BK;
+  const Hot x = load_hot(ga);
+  const int t = xcd_chunk_of(x);
+  const int nk_all = x.nk;
   if constexpr (SPLITK) {
-    select_tile<BN>(ga, t >> 1, pi, m0, n0);
-    gemm8_body<EPI, BN, LAY, M16, true>(ga, smem, pi, m0, n0, (t & 1) * (nk_all >> 1), nk_all >> 1, t >> 1, t & 1);
+    select_tile<BN>(x, t >> 1, pi, m0, n0);
+    gemm8_body<EPI, BN, LAY, M16, true>(ga, smem, pi, m0, n0, (t & 1) * (nk_all >> 1), nk_all >> 1, t >> 1, t & 1, &st);
   } else {
-    select_tile<BN>(ga, t, pi, m0, n0);
-    gemm8_body<EPI, BN, LAY, M16>(ga, smem, pi, m0, n0, 0, nk_all, -1);
+    select_tile<BN>(x, t, pi, m0, n0);
+    gemm8_body<EPI, BN, LAY, M16>(ga, smem, pi, m0, n0, 0, nk_all, -1, 0, &st);
   }
+  st.mark<4>();
+  st.flush();
 }
 
 // ---- gemm10: four waves, one per SIMD, 128 x 128 per wave, every instruction of the K loop placed by hand (round 6) ---------
@@ -597,23 +675,26 @@ FK_DEV void gemm10_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0,
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const fk_gemm_args& p = ga.p[pi];
-  const BufDesc od_a = make_buf_desc((const bf16_t*)p.A + fk_row_offset(p.a, m0), 0x7fffffffu);
-  const BufDesc od_w = make_buf_desc((const bf16_t*)p.W + (int64_t)n0 * p.ldw, 0x7fffffffu);
+  const ProbEntry q = load_prob(ga, pi);
   // global side: wave w stages rows [64 w, 64 w + 64) of the A tile and of the W tile as 8 pieces of 8 rows x 128 B each;
   // lane -> (row lane >> 3, 16-byte chunk lane & 7); rows beyond the problem are clamped (their products are never stored)
   const int lrow = lane >> 3, chunk = lane & 7;
   i32x8_t a_voff, w_voff;
+  int64_t a_first;
   {
-    const TileRows arow(p.a, m0);
-    const int ldw2 = (int)p.ldw * 2;
+    const int ldw2 = q.ldw * 2;
+    int rls[8], aoff[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) rls[i] = wave * 64 + i * 8 + lrow;
+    a_first = tile_a_rows<8>(ga, pi, q, m0, rls, aoff);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const int rl = wave * 64 + i * 8 + lrow;
-      a_voff[i] = arow.off(min(rl, p.M - 1 - m0)) * 2 + chunk * 16;
-      w_voff[i] = min(rl, p.N - 1 - n0) * ldw2 + chunk * 16;
+      a_voff[i] = aoff[i] * 2 + chunk * 16;
+      w_voff[i] = min(rls[i], q.N - 1 - n0) * ldw2 + chunk * 16;
     }
   }
+  const BufDesc od_a = make_buf_desc((const bf16_t*)q.A + a_first, 0x7fffffffu);
+  const BufDesc od_w = make_buf_desc((const bf16_t*)q.W + (int64_t)n0 * q.ldw, 0x7fffffffu);
   // LDS side.  Write: piece i of the wave lands at rows 8 ((w & 1) 8 + i) + lrow of half-tile w >> 1 (A) / of W's at + 32 KiB;
   // logical chunk c of row r at physical chunk c ^ ((r >> 1) & 7), and (r >> 1) & 7 = (4 (i & 1) + (lrow >> 1)) & 7.
   // Read: gemm8_kernel's M16 fragments -- row lane & 15 of 16-row block m / n (the immediate), k-octet lane >> 4 of k-step kk.
@@ -711,7 +792,8 @@ FK_DEV void gemm10_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0,
 #include "gemm10_loop_x20.inc"
         G10_OPERANDS_X); }
 #endif
-  store_tile<EPI, 256, C>(acc, p, smem, m0, n0, wm, wn);
+  const fk_gemm_args& p = ga.p[behind_requests(pi)];
+  store_tile<EPI, 256, C>(acc, p, smem, m0, n0, wm, wn, nullptr, q.flags);
 #ifdef FK_G10_EXPERIMENTS
   if constexpr (V > 0) {   // per workgroup, behind C: where it ran, when (wall clock), and wave 0's shader-cycle stamps of kernel entry,
     if (tid == 0) {        // asm statement entry, loop start, loop end (s_memtime inside the statement) and its own last store issued
@@ -728,15 +810,16 @@ FK_DEV void gemm10_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0,
 template <int EPI, int V = 0, bool PERSIST = false>
 __global__ __launch_bounds__(256, 1) void gemm10_kernel(const GroupArgs ga) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nk = ga.p[0].K / Cfg10::BK;
+  const Hot x = load_hot(ga);
+  const int nk = x.nk;
   if constexpr (PERSIST) {
     // one workgroup per CU walks the tile list with stride gridDim: the 32 workgroups of an XCD work on 32 consecutive tiles
     // of the grouped order in every round (what the dispatcher does with a plain grid), without the relaunch gap and with the
     // kernel arguments warm in the scalar cache from the second tile on
-    const int total = ga.tiles_before[FK_MAX_GROUP];
-    for (int t = xcd_chunk_index(); t < total; t += gridDim.x) {
+    const int total = ga.e.cls[0].before[FK_MAX_GROUP];
+    for (int t = xcd_chunk_of(x); t < total; t += (int)x.grid) {
       int pi, m0, n0;
-      select_tile<256>(ga, t, pi, m0, n0);
+      select_tile<256>(x, t, pi, m0, n0);
       gemm10_body<EPI, V>(ga, smem, pi, m0, n0, 0, nk);
       // every wave is done READING the C tile before the next tile's prologue refills the ring: an LDS-only barrier -- a
       // __syncthreads() would also wait for this tile's global stores to drain (all CUs at once: measured 35-50 k cycles)
@@ -744,7 +827,7 @@ __global__ __launch_bounds__(256, 1) void gemm10_kernel(const GroupArgs ga) {
     }
   } else {
     int pi, m0, n0;
-    select_tile<256>(ga, xcd_chunk_index(), pi, m0, n0);
+    select_tile<256>(x, xcd_chunk_of(x), pi, m0, n0);
     gemm10_body<EPI, V>(ga, smem, pi, m0, n0, 0, nk);
   }
 }
@@ -761,9 +844,10 @@ __global__ __launch_bounds__(256, 1) void gemm10_kernel(const GroupArgs ga) {
 template <int EPI, int BN, bool M16 = false>
 __global__ __launch_bounds__(512, 2) void gemm8_streamk_kernel(const GroupArgs ga) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int pos = xcd_chunk_index();
-  const unsigned G = gridDim.x, nk = ga.p[0].K / Cfg8<BN>::BK;
-  const unsigned U = (unsigned)ga.tiles_before[FK_MAX_GROUP] * nk, qU = U / G, rU = U - qU * G;
+  const Hot x = load_hot(ga);
+  const int pos = xcd_chunk_of(x);
+  const unsigned G = x.grid, nk = (unsigned)x.nk;
+  const unsigned U = (unsigned)ga.e.cls[0].before[FK_MAX_GROUP] * nk, qU = U / G, rU = U - qU * G;
   auto cut = [&](unsigned j) __attribute__((always_inline)) {
     unsigned c = qU * j + (rU * j) / G;                      // floor(U j / G) without a 64-bit product
     const unsigned r = c % nk;
@@ -778,27 +862,29 @@ __global__ __launch_bounds__(512, 2) void gemm8_streamk_kernel(const GroupArgs g
     const int k1 = u_end - t * (int)nk, k0 = max(u - t * (int)nk, 0);
     u_end -= k1 - k0;
     int pi, m0, n0;
-    select_tile<BN>(ga, t, pi, m0, n0);
+    select_tile<BN>(x, t, pi, m0, n0);
     const bool part = k0 > 0 || k1 < (int)nk;
     gemm8_body<EPI, BN, 0, M16>(ga, smem, pi, m0, n0, k0, k1 - k0, part ? (k1 < (int)nk ? pos + 1 : pos) : -1);
     __syncthreads();   // every wave is done with the C tile / the ticket word before the next pass refills the ring
   }
 }
 
+// fills the launch's tile class (the entry record's cls[0]) for TM_BM x BN tiles and the grid constants for `grid`
+// workgroups (0: one per tile, split: two per tile); returns the tile count, or -1 when the order's quotients would leave
+// the exact range of their multiply-shift form (>= 2^31 / divisor tiles: the caller falls back)
 template <int BN>
-int count_tiles(GroupArgs& ga, const fk_gemm_args* probs, int n) {
-  int total = 0;
-  for (int i = 0; i < FK_MAX_GROUP; ++i) {
-    ga.tiles_before[i] = total;
-    if (i < n) total += ((probs[i].M + BM - 1) / BM) * ((probs[i].N + BN - 1) / BN);
-  }
-  ga.tiles_before[FK_MAX_GROUP] = total;
+int count_tiles(GroupArgs& ga, const fk_gemm_args* probs, int n, int grid = 0, bool split = false) {
+  int32_t Ms[FK_MAX_GROUP];
+  for (int i = 0; i < n; ++i) Ms[i] = probs[i].M;
+  const int total = tm_fill_class(ga.e.cls[0], Ms, n, (probs[0].N + BN - 1) / BN, 0, ga.e.group_m);
+  if (total >= 0) tm_fill_grid(ga.e, (uint32_t)(grid ? grid : split ? 2 * total : total));
   return total;
 }
 
 template <int EPI, int BN, bool SPLITK, int LAY = 0, bool M16 = false>
 int launch8(GroupArgs& ga, const fk_gemm_args* probs, int n, hipStream_t stream) {
-  const int total = count_tiles<BN>(ga, probs, n);
+  const int total = count_tiles<BN>(ga, probs, n, 0, SPLITK);
+  if (total < 0) return FK_E2BIG_STRIDES;
   auto kern = gemm8_kernel<EPI, BN, SPLITK, LAY, M16>;
   FK_ENSURE_MAX_LDS(kern, Cfg8<BN>::SMEM_BYTES, "fk_gemm_bf16 (256 x 256 tile, 8 waves ping-pong)");
   hipLaunchKernelGGL(kern, dim3(SPLITK ? 2 * total : total), dim3(512), Cfg8<BN>::SMEM_BYTES, stream, ga);
@@ -808,7 +894,7 @@ int launch8(GroupArgs& ga, const fk_gemm_args* probs, int n, hipStream_t stream)
 
 template <int EPI, int BN, bool M16 = false>
 int launch8_streamk(GroupArgs& ga, const fk_gemm_args* probs, int n, int grid, hipStream_t stream) {
-  count_tiles<BN>(ga, probs, n);
+  if (count_tiles<BN>(ga, probs, n, grid) < 0) return FK_E2BIG_STRIDES;
   auto kern = gemm8_streamk_kernel<EPI, BN, M16>;
   FK_ENSURE_MAX_LDS(kern, Cfg8<BN>::SMEM_BYTES, "fk_gemm_bf16 (256 x 256 tile, stream-K ranges)");
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), Cfg8<BN>::SMEM_BYTES, stream, ga);
@@ -821,6 +907,7 @@ int cu_count();
 template <int EPI>
 int launch10(GroupArgs& ga, const fk_gemm_args* probs, int n, hipStream_t stream) {
   const int total = count_tiles<256>(ga, probs, n);
+  if (total < 0) return FK_E2BIG_STRIDES;
 #ifdef FK_G10_EXPERIMENTS
   if constexpr (EPI == FK_EPI_NONE) {   // measurement forms of the loop (gemm10_gen.py EXPERIMENTS): FK_G10_X=<n>
     static const int x = getenv("FK_G10_X") ? atoi(getenv("FK_G10_X")) : 0;
@@ -852,7 +939,9 @@ int launch10(GroupArgs& ga, const fk_gemm_args* probs, int n, hipStream_t stream
     }
     if (kx) {
       if (hipFuncSetAttribute((const void*)kx, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg10::SMEM_BYTES) != hipSuccess) return FK_EINVAL;
-      hipLaunchKernelGGL(kx, dim3(persist ? (total < cu_count() ? total : cu_count()) : total), dim3(256), Cfg10::SMEM_BYTES, stream, ga);
+      const int gx = persist ? (total < cu_count() ? total : cu_count()) : total;
+      tm_fill_grid(ga.e, (uint32_t)gx);
+      hipLaunchKernelGGL(kx, dim3(gx), dim3(256), Cfg10::SMEM_BYTES, stream, ga);
       FK_CHECK_LAUNCH("fk_gemm_bf16 (gemm10 experiment)");
       return FK_OK;
     }
@@ -864,6 +953,7 @@ int launch10(GroupArgs& ga, const fk_gemm_args* probs, int n, hipStream_t stream
   const int G = cu_count();
   if (total >= 4 * G) {
     auto kern = gemm10_kernel<EPI, 0, true>;
+    tm_fill_grid(ga.e, (uint32_t)G);
     FK_ENSURE_MAX_LDS(kern, Cfg10::SMEM_BYTES, "fk_gemm_bf16 (256 x 256 tile, 4 waves, hand-placed loop, one workgroup per CU)");
     hipLaunchKernelGGL(kern, dim3(G), dim3(256), Cfg10::SMEM_BYTES, stream, ga);
     FK_CHECK_LAUNCH("fk_gemm_bf16 (256 x 256 tile, 4 waves, hand-placed loop, one workgroup per CU)");
@@ -907,38 +997,40 @@ struct Cfg9 {
 };
 
 template <int EPI, int BN, bool M16 = false>
-FK_DEV void gemm9_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0) {
+FK_DEV void gemm9_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0, int nk, EntryStamps* st = nullptr) {
+  EntryStamps st_none;
+  if (!st) st = &st_none;
   using C = Cfg9<BN, M16>;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 3, wn = wave >> 2;   // group = wn
-  const fk_gemm_args& p = ga.p[pi];
-  const int nk = p.K / C::BK;
+  const ProbEntry q = load_prob(ga, pi);   // the prologue reads nothing else of its problem
 
   const int lrow = lane >> 3, slot = lane & 7;
-  const __amdgpu_buffer_rsrc_t rs_a =
-      __builtin_amdgcn_make_buffer_rsrc((void*)((const bf16_t*)p.A + fk_row_offset(p.a, m0)), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w =
-      __builtin_amdgcn_make_buffer_rsrc((void*)((const bf16_t*)p.W + (int64_t)n0 * p.ldw), 0, 0x7fffffff, 0x00020000);
   int a_voff[2][2], w_voff[2];   // A: [half][piece]; W: [part j], one piece per wave
+  int64_t a_first;
   {
-    const TileRows arow(p.a, m0);
-    const int ldw2 = (int)p.ldw * 2;
+    const int ldw2 = q.ldw * 2;
+    int rls[4], aoff[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rls[i] = (i >> 1) * 128 + (wave * 2 + (i & 1)) * 8 + lrow;
+    a_first = tile_a_rows<4>(ga, pi, q, m0, rls, aoff);
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int rl = h * 128 + (wave * 2 + j) * 8 + lrow;
-        a_voff[h][j] = arow.off(min(rl, p.M - 1 - m0)) * 2 + ((slot ^ C::swz(rl)) << 4);
-      }
+      for (int j = 0; j < 2; ++j) a_voff[h][j] = aoff[h * 2 + j] * 2 + ((slot ^ C::swz(rls[h * 2 + j])) << 4);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int sr = wave * 8 + lrow;                      // row inside the 64-row part W_j
       const int rl = (sr >> 5) * 64 + j * 32 + (sr & 31);  // row inside the 128-row W tile
-      w_voff[j] = min(rl, p.N - 1 - n0) * ldw2 + ((slot ^ C::swz(sr)) << 4);
+      w_voff[j] = min(rl, q.N - 1 - n0) * ldw2 + ((slot ^ C::swz(sr)) << 4);
     }
   }
+  const __amdgpu_buffer_rsrc_t rs_a =
+      __builtin_amdgcn_make_buffer_rsrc((void*)((const bf16_t*)q.A + a_first), 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w =
+      __builtin_amdgcn_make_buffer_rsrc((void*)((const bf16_t*)q.W + (int64_t)n0 * q.ldw), 0, 0x7fffffff, 0x00020000);
   auto dma_a = [&](int stage, int kt) {   // both halves of the A tile: 4 requests
     const int koff = min(kt, nk - 1) * (C::BK * 2);
     char* dst = smem + stage * C::STAGE_BYTES + wave * 2048;
@@ -951,6 +1043,18 @@ FK_DEV void gemm9_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0) 
     const int koff = min(kt, nk - 1) * (C::BK * 2);
     buffer_lds16(rs_w, smem + stage * C::STAGE_BYTES + 2 * C::A_HALF + j * C::W_PART + wave * 1024, w_voff[j], koff);
   };
+
+  // ---- prologue: everything read in phases 0 .. 4, in reading order (13 requests) --------------------------------
+  dma_w(0, 0, 0);   // W_0(0)   "phase 0"
+  st->mark<1>();
+  dma_a(0, 0);      // A(0)     P1(0)
+  dma_w(1, 0, 0);   // W_1(0)   P2(0)
+  dma_w(0, 1, 1);   // W_0(1)   P2(0)
+  dma_a(1, 1);      // A(1)     P1(1)
+  dma_w(1, 1, 1);   // W_1(1)   P2(1)
+  dma_w(0, 2, 2);   // W_0(2)   P2(1)
+  // From here on the epilogue's view of the problem: nothing of it is fetched in front of the requests above.
+  const fk_gemm_args& p = ga.p[behind_requests(pi)];
 
   constexpr int NKS = M16 ? 2 : 4, ASUB = M16 ? 4 : 2, WSUB = M16 ? 2 : 1;   // as gemm8_body
   constexpr int SUB_BYTES = (M16 ? 16 : 32) * C::ROW_BYTES;
@@ -1009,14 +1113,6 @@ FK_DEV void gemm9_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0) 
   using V10 = std::integral_constant<int, 10>;
   using V8 = std::integral_constant<int, 8>;
 
-  // ---- prologue: everything read in phases 0 .. 4, in reading order (13 requests) --------------------------------
-  dma_w(0, 0, 0);   // W_0(0)   "phase 0"
-  dma_a(0, 0);      // A(0)     P1(0)
-  dma_w(1, 0, 0);   // W_1(0)   P2(0)
-  dma_w(0, 1, 1);   // W_0(1)   P2(0)
-  dma_a(1, 1);      // A(1)     P1(1)
-  dma_w(1, 1, 1);   // W_1(1)   P2(1)
-  dma_w(0, 2, 2);   // W_0(2)   P2(1)
   wait_vmcnt<8>();  // W_0(0), A(0) landed (own pieces)
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -1024,6 +1120,7 @@ FK_DEV void gemm9_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0) 
   read_w(0, 0);
   if (wn == 1) __builtin_amdgcn_s_barrier();   // the stagger
   __builtin_amdgcn_sched_barrier(0);
+  st->mark<2>();
 
   auto tile_body = [&](auto sc, int kt) {
     constexpr int st = decltype(sc)::value, st1 = (st + 1) % 3, st2 = (st + 2) % 3;
@@ -1035,23 +1132,30 @@ FK_DEV void gemm9_body(const GroupArgs& ga, char* smem, int pi, int m0, int n0) 
     if (kt + 1 < nk) tile_body(std::integral_constant<int, 1>{}, kt + 1);
     if (kt + 2 < nk) tile_body(std::integral_constant<int, 2>{}, kt + 2);
   }
+  st->mark<3>();
   if (wn == 0) __builtin_amdgcn_s_barrier();   // balance the stagger
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-  store_tile<EPI, BN, C>(acc, p, smem, m0, n0, wm, wn);
+  store_tile<EPI, BN, C>(acc, p, smem, m0, n0, wm, wn, nullptr, q.flags);
 }
 
 template <int EPI, int BN, bool M16 = false>
 __global__ __launch_bounds__(512, 2) void gemm9_kernel(const GroupArgs ga) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  EntryStamps st;
+  st.mark<0>();
   int pi, m0, n0;
-  select_tile<BN>(ga, xcd_chunk_index(), pi, m0, n0);
-  gemm9_body<EPI, BN, M16>(ga, smem, pi, m0, n0);
+  const Hot x = load_hot(ga);
+  select_tile<BN>(x, xcd_chunk_of(x), pi, m0, n0);
+  gemm9_body<EPI, BN, M16>(ga, smem, pi, m0, n0, x.nk, &st);
+  st.mark<4>();
+  st.flush();
 }
 
 template <int EPI, int BN, bool M16 = false>
 int launch9(GroupArgs& ga, const fk_gemm_args* probs, int n, hipStream_t stream) {
   const int total = count_tiles<BN>(ga, probs, n);
+  if (total < 0) return FK_E2BIG_STRIDES;
   auto kern = gemm9_kernel<EPI, BN, M16>;
   FK_ENSURE_MAX_LDS(kern, Cfg9<BN>::SMEM_BYTES, "fk_gemm_bf16 (256 x 128 tile, 8 waves ping-pong)");
   hipLaunchKernelGGL(kern, dim3(total), dim3(512), Cfg9<BN>::SMEM_BYTES, stream, ga);
@@ -1069,17 +1173,28 @@ int launch9(GroupArgs& ga, const fk_gemm_args* probs, int n, hipStream_t stream)
 template <int EPI, bool M16 = false>
 __global__ __launch_bounds__(512, 2) void gemm_mix_kernel(const GroupArgs ga) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  EntryStamps st;
+  st.mark<0>();
+  // one fetch: the head, BOTH classes and this XCD's three table words; the class is chosen among values
   const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int nbig = ga.xcd_big_cnt[xcd];
+  Hot x;
+  x.h = tm_hot(ga.e, ga.e.cls[0]);
+  TmHot hs = tm_hot(ga.e, ga.e.cls[1]);
+  x.xq = ga.e.xq; x.xr = ga.e.xr; x.grid = ga.e.grid; x.nk = ga.e.nk;
+  const TileEntry::Xcd tab = ga.e.xcd[xcd];
+  int nbig = tab.big_cnt, big0 = tab.big_start, small0 = tab.small_start;
+  asm volatile("" : FK_PIN_HEAD(x), "+s"(nbig), "+s"(big0), "+s"(small0), FK_PIN_CLASS(x.h), FK_PIN_CLASS(hs));
   int pi, m0, n0;
   if (idx < nbig) {
-    tile_of<256>(ga, ga.tiles_before, ga.xcd_big_start[xcd] + idx, ga.big_cols, 0, pi, m0, n0);
-    gemm8_body<EPI, 256, 0, M16>(ga, smem, pi, m0, n0, 0, ga.p[0].K / 64, -1);
+    tm_tile_hot(x.h, 256, big0 + idx, pi, m0, n0);
+    gemm8_body<EPI, 256, 0, M16>(ga, smem, pi, m0, n0, 0, x.nk, -1, 0, &st);
   } else {
-    tile_of<128>(ga, ga.small_before, ga.xcd_small_start[xcd] + idx - nbig, (ga.p[0].N - ga.big_cols * 256 + 127) / 128,
-                 ga.big_cols * 256, pi, m0, n0);
-    gemm9_body<EPI, 128, M16>(ga, smem, pi, m0, n0);
+    hs.n = x.h.n; hs.group_m = x.h.group_m;
+    tm_tile_hot(hs, 128, small0 + idx - nbig, pi, m0, n0);
+    gemm9_body<EPI, 128, M16>(ga, smem, pi, m0, n0, x.nk, &st);
   }
+  st.mark<4>();
+  st.flush();
 }
 
 constexpr int MIX_SMEM = Cfg8<256>::SMEM_BYTES > Cfg9<128>::SMEM_BYTES ? Cfg8<256>::SMEM_BYTES : Cfg9<128>::SMEM_BYTES;
@@ -1087,30 +1202,21 @@ constexpr int MIX_SMEM = Cfg8<256>::SMEM_BYTES > Cfg9<128>::SMEM_BYTES ? Cfg8<25
 template <int EPI, bool M16 = false>
 int launch_mix(GroupArgs& ga, const fk_gemm_args* probs, int n, int big_cols, hipStream_t stream) {
   const int ncols128 = (probs[0].N - big_cols * 256 + 127) / 128;
-  int tb = 0, ts = 0;
-  for (int i = 0; i < FK_MAX_GROUP; ++i) {
-    ga.tiles_before[i] = tb;
-    ga.small_before[i] = ts;
-    if (i < n) {
-      const int nbm = (probs[i].M + BM - 1) / BM;
-      tb += nbm * big_cols;
-      ts += nbm * ncols128;
-    }
-  }
-  ga.tiles_before[FK_MAX_GROUP] = tb;
-  ga.small_before[FK_MAX_GROUP] = ts;
-  ga.big_cols = big_cols;
+  int32_t Ms[FK_MAX_GROUP];
+  for (int i = 0; i < n; ++i) Ms[i] = probs[i].M;
+  const int tb = tm_fill_class(ga.e.cls[0], Ms, n, big_cols, 0, ga.e.group_m);
+  const int ts = tm_fill_class(ga.e.cls[1], Ms, n, ncols128, big_cols * 256, ga.e.group_m);
+  if (tb < 0 || ts < 0) return FK_E2BIG_STRIDES;
   const int W = tb + ts;
   int bs = 0, ss = 0;
   for (int x = 0; x < 8; ++x) {
     const int wx = W / 8 + (x < W % 8 ? 1 : 0), bx = tb / 8 + (x < tb % 8 ? 1 : 0);
     if (wx < bx) return FK_E2BIG_STRIDES;   // cannot happen for the grids the planner proposes (ts >= 8); caller falls back
-    ga.xcd_big_start[x] = bs;
-    ga.xcd_big_cnt[x] = bx;
-    ga.xcd_small_start[x] = ss;
+    ga.e.xcd[x] = {bs, bx, ss, 0};
     bs += bx;
     ss += wx - bx;
   }
+  tm_fill_grid(ga.e, (uint32_t)W);
   auto kern = gemm_mix_kernel<EPI, M16>;
   FK_ENSURE_MAX_LDS(kern, MIX_SMEM, "fk_gemm_bf16 (mixed 256 x 256 / 256 x 128 tiles)");
   hipLaunchKernelGGL(kern, dim3(W), dim3(512), MIX_SMEM, stream, ga);
@@ -1271,9 +1377,14 @@ int fk_gemm2_launch(const fk_gemm_args* probs, int n, int variant_hint, hipStrea
                       : sk_bits == FK_GEMM_PLAN_SPLITK_UNANNOUNCED ? SK_SYM_UNANNOUNCED : SK_MODE_DEFAULT;
   GroupArgs ga;
   ga.sk_mode = sk_mode;
-  ga.n = n;
-  ga.group_m = ctl.group_m ? ctl.group_m : GROUP_M;
-  ga.big_cols = 0;
+  ga.e = TileEntry{};
+  ga.e.n = n;
+  ga.e.nk = probs[0].K / 64;
+  {
+    int32_t Ms[FK_MAX_GROUP];
+    for (int i = 0; i < n; ++i) Ms[i] = probs[i].M;
+    ga.e.group_m = tm_group_m(Ms, n, ctl.group_m ? ctl.group_m : GROUP_M);
+  }
   ga.sk_partials = nullptr;
   ga.sk_ctl = nullptr;
   long nbm_total = 0;
@@ -1299,6 +1410,26 @@ int fk_gemm2_launch(const fk_gemm_args* probs, int n, int variant_hint, hipStrea
     }
   }
   if (!ok32) return FK_E2BIG_STRIDES;   // caller falls back to the 128 x 128 kernel (64-bit addressing)
+  // the per-problem prologue records; rows that lie at m * ld (one batch, a problem inside its first batch, batches
+  // without gaps) are marked flat: no division on the device.  The fused QKV epilogue needs a row's batch and token, so
+  // its C rows are flat only inside the first batch.
+  for (int i = 0; i < FK_MAX_GROUP; ++i) {
+    const fk_gemm_args& q = ga.p[i];
+    ProbEntry& e = ga.pe[i];
+    e.A = q.A;
+    e.W = q.W;
+    e.lda = (int32_t)q.a.ld;
+    e.ldw = (int32_t)q.ldw;
+    e.M = q.M;
+    e.N = q.N;
+    e.K = q.K;
+    e.flags = 0;
+    if (tm_rows_flat(q.a.ld, q.a.rows_per_batch, q.a.batch_stride, q.M)) e.flags |= TM_A_FLAT;
+    if (q.epilogue == FK_EPI_QKV ? (q.c.rows_per_batch > 0 && q.M <= q.c.rows_per_batch)
+                                 : tm_rows_flat(q.c.ld, q.c.rows_per_batch, q.c.batch_stride, q.M)) e.flags |= TM_C_FLAT;
+    if (tm_rows_flat(q.r.ld, q.r.rows_per_batch, q.r.batch_stride, q.M)) e.flags |= TM_R_FLAT;
+    if (q.gate_rows_per_batch <= 0 || q.M <= q.gate_rows_per_batch) e.flags |= TM_G_FLAT;
+  }
 
   // K-major operands (layout 1: W [K, N]; layout 2: A [K, M] too): the 256 x 256 kernel only, whole tiles only
   const int lay = probs[0].layout;
@@ -1389,9 +1520,21 @@ int fk_gemm2_launch(const fk_gemm_args* probs, int n, int variant_hint, hipStrea
     case FK_EPI_QKV: rc = launch_variant<FK_EPI_QKV>(ga, probs, n, plan.variant, plan.big_cols, m16, stream); break;
     default: fk_set_error("fk_gemm_bf16: unknown epilogue %d", probs[0].epilogue); return FK_EUNSUPPORTED;
   }
+  // FK_E2BIG_STRIDES from a launcher: the strides were fine (checked above) but the tile count leaves the exact range of the
+  // order's multiply-shift quotients (tiles x per_group > 2^31: no real grid) -- same remedy, the caller's 128 x 128 kernel;
+  // nothing was launched, so the reported form is taken back
+  if (rc == FK_E2BIG_STRIDES && plan.variant != 384) report_variant(probs, 0);
   if (rc == FK_E2BIG_STRIDES && plan.variant == 384) {   // degenerate XCD split of a mixed grid: plain 256 x 128 grid
     report_variant(probs, 128);
     return fk_gemm2_launch(probs, n, 128, stream);
   }
   return rc;
 }
+
+#ifdef FK_ENTRY_STAMPS
+// diagnostic build only: where the workgroups of the next launches leave their stamps (8 x uint64 per workgroup; NULL: nowhere)
+extern "C" int fk_entry_stamps_set(void* buf) {
+  unsigned long long* p = (unsigned long long*)buf;
+  return hipMemcpyToSymbol(HIP_SYMBOL(fk_entry_stamp_buf), &p, sizeof(p)) == hipSuccess ? 0 : -1;
+}
+#endif
