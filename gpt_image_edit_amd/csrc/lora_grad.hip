@@ -29,6 +29,10 @@
 // scale * (p_0 + p_1 + ... ) in ascending split order, one thread per output element.
 // No atomics: every output element is written once, by a sum whose order (MFMA order inside a step, steps ascending, splits
 // ascending) is fixed by (N, K, r) alone -- two launches give the same bits.  dW, up and down are only read.
+// Accumulate form (fk_lora_grad_acc_bf16, accumulate = 1; gradient accumulation over micro-batches): out = out_old + scale * sum.
+// The add sits where the scaled value is formed -- the final store of an unsplit role, the reduce kernel of a split one -- so the
+// thread that owns an element reads it once and writes it once; partials are never added to, still no atomics, the order still
+// fixed by (N, K, r).  accumulate = 0 never reads the outputs (they may hold NaN bits) and is the code fk_lora_grad_bf16 runs.
 // Views that are not 16-byte aligned (pointer or row stride), and row tails, take the same kernels with element-wise loads.
 // First shapes that cross each boundary: N = 65 second UP strip; K = 33 second UP step; K = 257 second UP chunk (a partial);
 // K = 129 second DOWN strip; N = 65 second DOWN step; N = 129 second DOWN chunk (a partial).
@@ -79,6 +83,7 @@ struct GradArgs {
   int32_t up_blocks;                                 // blocks [0, up_blocks) take role UP
   int32_t splits_up, chunk_up, splits_dn, chunk_dn;
   int32_t vec_dw, vec_up, vec_down;                  // 16-byte loads allowed (pointer % 16 == 0 and row stride % 8 == 0)
+  int32_t accumulate;                                // 1: an unsplit role adds its scaled sum to what its output holds
 };
 
 // elements [k, k + 8) of a row of `len` elements (k % 8 == 0) as an MFMA operand fragment; zeros beyond the row or when !ok
@@ -174,7 +179,11 @@ __global__ __launch_bounds__(LG_THREADS) void lora_grad_kernel(GradArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int64_t nr = n_row + 4 * lg + e;
-        if (nr < N && j < rank) out[nr * rank + j] = final_ ? a.scale * acc[t][e] : acc[t][e];
+        if (nr < N && j < rank) {
+          float v = final_ ? a.scale * acc[t][e] : acc[t][e];
+          if (final_ && a.accumulate) v += out[nr * rank + j];
+          out[nr * rank + j] = v;
+        }
       }
     }
     return;
@@ -220,15 +229,20 @@ __global__ __launch_bounds__(LG_THREADS) void lora_grad_kernel(GradArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int j = 16 * t + 4 * lg + e;
-        if (j < rank && k < K) out[(int64_t)j * K + k] = final_ ? a.scale * acc[t][h][e] : acc[t][h][e];
+        if (j < rank && k < K) {
+          float v = final_ ? a.scale * acc[t][h][e] : acc[t][h][e];
+          if (final_ && a.accumulate) v += out[(int64_t)j * K + k];
+          out[(int64_t)j * K + k] = v;
+        }
       }
     }
 }
 
-// out[i] = scale * (p[0][i] + p[1][i] + ...), splits ascending; elements [0, n_up) are d_up's, the next n_dn are d_down's
+// out[i] = scale * (p[0][i] + p[1][i] + ...) (+ out[i] when accumulate), splits ascending; elements [0, n_up) are d_up's, the
+// next n_dn are d_down's
 __global__ __launch_bounds__(LG_THREADS) void lora_grad_reduce_kernel(const float* p_up, int splits_up, int64_t n_up, float* d_up,
                                                                       const float* p_dn, int splits_dn, int64_t n_dn, float* d_down,
-                                                                      float scale) {
+                                                                      float scale, int accumulate) {
   int64_t i = (int64_t)blockIdx.x * LG_THREADS + threadIdx.x;
   const float* p;
   float* out;
@@ -243,7 +257,9 @@ __global__ __launch_bounds__(LG_THREADS) void lora_grad_reduce_kernel(const floa
   }
   float v = p[i];
   for (int s = 1; s < splits; ++s) v += p[(int64_t)s * n + i];
-  out[i] = scale * v;
+  v *= scale;
+  if (accumulate) v += out[i];
+  out[i] = v;
 }
 
 struct Span { uintptr_t lo, hi; };                     // [lo, hi) in bytes
@@ -264,33 +280,37 @@ extern "C" int64_t fk_lora_grad_ws_floats(int32_t N, int32_t K, int32_t rank) {
   return ws_floats_of(plan_of(N, K), N, K, rank);
 }
 
-extern "C" int fk_lora_grad_bf16(const void* dw, int64_t ld_dw, const void* up, int64_t ld_up, const void* down, int64_t ld_down,
-                                 int32_t N, int32_t K, int32_t rank, float scale, float* d_up, float* d_down, float* ws,
-                                 int64_t ws_floats, fk_stream_t stream) {
-  FK_CHECK_ARG(dw && up && down && d_up && d_down, "fk_lora_grad_bf16: NULL pointer");
-  FK_CHECK_ARG(N >= 1 && K >= 1, "fk_lora_grad_bf16: needs N >= 1 and K >= 1 (N = %d, K = %d)", N, K);
+namespace {
+
+// `fn`: the entry point's name, the prefix of every error message
+int lora_grad_launch(const char* fn, const void* dw, int64_t ld_dw, const void* up, int64_t ld_up, const void* down, int64_t ld_down,
+                     int32_t N, int32_t K, int32_t rank, float scale, float* d_up, float* d_down, int32_t accumulate, float* ws,
+                     int64_t ws_floats, fk_stream_t stream) {
+  FK_CHECK_ARG(dw && up && down && d_up && d_down, "%s: NULL pointer", fn);
+  FK_CHECK_ARG(N >= 1 && K >= 1, "%s: needs N >= 1 and K >= 1 (N = %d, K = %d)", fn, N, K);
   if (rank < 1 || rank > FK_LORA_MAX_RANK) {
-    fk_set_error("fk_lora_grad_bf16: rank %d, supported 1 to %d", rank, FK_LORA_MAX_RANK);
+    fk_set_error("%s: rank %d, supported 1 to %d", fn, rank, FK_LORA_MAX_RANK);
     return FK_EUNSUPPORTED;
   }
-  FK_CHECK_ARG(ld_dw >= K && ld_up >= rank && ld_down >= K, "fk_lora_grad_bf16: a row stride below the row length (ld_dw = %lld, "
-               "ld_down = %lld, K = %d, ld_up = %lld, rank = %d)", (long long)ld_dw, (long long)ld_down, K, (long long)ld_up, rank);
-  FK_CHECK_ARG(scale == scale && scale - scale == 0.0f, "fk_lora_grad_bf16: the scale is not finite");
+  FK_CHECK_ARG(ld_dw >= K && ld_up >= rank && ld_down >= K, "%s: a row stride below the row length (ld_dw = %lld, "
+               "ld_down = %lld, K = %d, ld_up = %lld, rank = %d)", fn, (long long)ld_dw, (long long)ld_down, K, (long long)ld_up, rank);
+  FK_CHECK_ARG(scale == scale && scale - scale == 0.0f, "%s: the scale is not finite", fn);
+  FK_CHECK_ARG(accumulate == 0 || accumulate == 1, "%s: accumulate is %d, it must be 0 (overwrite) or 1 (add)", fn, accumulate);
   const Plan p = plan_of(N, K);
   const int64_t need = ws_floats_of(p, N, K, rank);
-  FK_CHECK_ARG(need == 0 || (ws && ws_floats >= need), "fk_lora_grad_bf16: the workspace holds %lld floats, [%d, %d] at rank %d "
-               "needs %lld (fk_lora_grad_ws_floats)", (long long)(ws ? ws_floats : 0), N, K, rank, (long long)need);
+  FK_CHECK_ARG(need == 0 || (ws && ws_floats >= need), "%s: the workspace holds %lld floats, [%d, %d] at rank %d "
+               "needs %lld (fk_lora_grad_ws_floats)", fn, (long long)(ws ? ws_floats : 0), N, K, rank, (long long)need);
   const Span in[3] = {span_of(dw, ld_dw, N, K, 2), span_of(up, ld_up, N, rank, 2), span_of(down, ld_down, rank, K, 2)};
   const Span o_up = span_of(d_up, rank, N, rank, 4), o_dn = span_of(d_down, K, rank, K, 4);
   const Span o_ws = span_of(ws, need, 1, need, 4);
-  FK_CHECK_ARG(!overlap(o_up, o_dn), "fk_lora_grad_bf16: d_up overlaps d_down");
+  FK_CHECK_ARG(!overlap(o_up, o_dn), "%s: d_up overlaps d_down", fn);
   for (int i = 0; i < 3; ++i)
     FK_CHECK_ARG(!overlap(o_up, in[i]) && !overlap(o_dn, in[i]) && (need == 0 || !overlap(o_ws, in[i])),
-                 "fk_lora_grad_bf16: an output or the workspace overlaps an input");
-  FK_CHECK_ARG(need == 0 || (!overlap(o_ws, o_up) && !overlap(o_ws, o_dn)), "fk_lora_grad_bf16: the workspace overlaps an output");
+                 "%s: an output or the workspace overlaps an input", fn);
+  FK_CHECK_ARG(need == 0 || (!overlap(o_ws, o_up) && !overlap(o_ws, o_dn)), "%s: the workspace overlaps an output", fn);
   const int64_t up_blocks = p.strips_up * p.splits_up, dn_blocks = p.strips_dn * p.splits_dn;
   if (up_blocks + dn_blocks > 0x7fffffffLL) {
-    fk_set_error("fk_lora_grad_bf16: %lld + %lld workgroups exceed one grid", (long long)up_blocks, (long long)dn_blocks);
+    fk_set_error("%s: %lld + %lld workgroups exceed one grid", fn, (long long)up_blocks, (long long)dn_blocks);
     return FK_EUNSUPPORTED;
   }
   GradArgs a;
@@ -307,6 +327,7 @@ extern "C" int fk_lora_grad_bf16(const void* dw, int64_t ld_dw, const void* up, 
   a.vec_dw = (uintptr_t)dw % 16 == 0 && ld_dw % 8 == 0;
   a.vec_up = (uintptr_t)up % 16 == 0 && ld_up % 8 == 0;
   a.vec_down = (uintptr_t)down % 16 == 0 && ld_down % 8 == 0;
+  a.accumulate = accumulate;
   const dim3 grid((unsigned)(up_blocks + dn_blocks)), block(LG_THREADS);
   switch ((rank + 31) / 32) {
     case 1: hipLaunchKernelGGL(lora_grad_kernel<2>, grid, block, 0, (hipStream_t)stream, a); break;
@@ -314,13 +335,29 @@ extern "C" int fk_lora_grad_bf16(const void* dw, int64_t ld_dw, const void* up, 
     case 3: hipLaunchKernelGGL(lora_grad_kernel<6>, grid, block, 0, (hipStream_t)stream, a); break;
     default: hipLaunchKernelGGL(lora_grad_kernel<8>, grid, block, 0, (hipStream_t)stream, a); break;
   }
-  FK_CHECK_LAUNCH("fk_lora_grad_bf16");
+  FK_CHECK_LAUNCH(fn);
   if (need > 0) {
     const int64_t n_up = p.splits_up > 1 ? (int64_t)N * rank : 0, n_dn = p.splits_dn > 1 ? (int64_t)rank * K : 0;
     const int64_t blocks = (n_up + n_dn + LG_THREADS - 1) / LG_THREADS;
     hipLaunchKernelGGL(lora_grad_reduce_kernel, dim3((unsigned)blocks), block, 0, (hipStream_t)stream, part_up, (int)p.splits_up,
-                       n_up, d_up, part_dn, (int)p.splits_dn, n_dn, d_down, scale);
-    FK_CHECK_LAUNCH("fk_lora_grad_bf16 (reduce)");
+                       n_up, d_up, part_dn, (int)p.splits_dn, n_dn, d_down, scale, (int)accumulate);
+    FK_CHECK_LAUNCH(fn);
   }
   return FK_OK;
+}
+
+}  // namespace
+
+extern "C" int fk_lora_grad_bf16(const void* dw, int64_t ld_dw, const void* up, int64_t ld_up, const void* down, int64_t ld_down,
+                                 int32_t N, int32_t K, int32_t rank, float scale, float* d_up, float* d_down, float* ws,
+                                 int64_t ws_floats, fk_stream_t stream) {
+  return lora_grad_launch("fk_lora_grad_bf16", dw, ld_dw, up, ld_up, down, ld_down, N, K, rank, scale, d_up, d_down, 0, ws, ws_floats,
+                          stream);
+}
+
+extern "C" int fk_lora_grad_acc_bf16(const void* dw, int64_t ld_dw, const void* up, int64_t ld_up, const void* down, int64_t ld_down,
+                                     int32_t N, int32_t K, int32_t rank, float scale, float* d_up, float* d_down, int32_t accumulate,
+                                     float* ws, int64_t ws_floats, fk_stream_t stream) {
+  return lora_grad_launch("fk_lora_grad_acc_bf16", dw, ld_dw, up, ld_up, down, ld_down, N, K, rank, scale, d_up, d_down, accumulate, ws,
+                          ws_floats, stream);
 }

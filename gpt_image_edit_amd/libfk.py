@@ -212,6 +212,8 @@ SIGNATURES = {
     "fk_lora_merge_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(LoraTerm), c_i32, c_vp]),
     "fk_lora_grad_ws_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "fk_lora_grad_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "fk_lora_grad_acc_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_vp, c_i64,
+                                      c_vp]),
     "fk_transpose_bf16": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "fk_attention_hd512_bf16": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp]),
     "fk_softmax_rows": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp]),

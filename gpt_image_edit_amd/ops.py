@@ -869,12 +869,16 @@ def lora_grad_ws(N, K, rank, device):
     return torch.empty(libfk.load().fk_lora_grad_ws_floats(N, K, rank), device=device, dtype=torch.float32)
 
 
-def lora_grad(dw, up, down, scale, d_up=None, d_down=None, ws=None):
+def lora_grad(dw, up, down, scale, d_up=None, d_down=None, ws=None, accumulate=False):
     """(d_up [N, r], d_down [r, K]) in fp32: ``scale * dw @ down^T`` and ``scale * up^T @ dw`` for the weight gradient
     ``dw`` bf16 [N, K] of a weight merged as ``base + scale * up @ down`` (fp32 accumulation, fixed summation order: two calls
     give the same bits).  ``dw``, ``up`` [N, r], ``down`` [r, K]: 2-D bf16 views with a contiguous last dimension; the
-    outputs contiguous fp32.  ``ws``: :func:`lora_grad_ws` (allocated per call when None -- the hot path owns one)."""
+    outputs contiguous fp32 (views at any 4-byte offset of a larger buffer will do).  ``ws``: :func:`lora_grad_ws` (allocated per
+    call when None -- the hot path owns one).  ``accumulate=True`` (``fk_lora_grad_acc_bf16``): the projection is ADDED to what
+    ``d_up`` / ``d_down`` hold -- a further micro-batch -- each element read once and written once, the order still fixed."""
     ins = [dw, up, down]
+    if accumulate and (d_up is None or d_down is None):
+        raise ValueError("lora_grad(accumulate=True) adds to d_up / d_down: pass both")
     _need_cuda(*ins)
     for t in ins:
         if t.dim() != 2 or t.stride(-1) != 1 or t.dtype != BF16:
@@ -897,6 +901,12 @@ def lora_grad(dw, up, down, scale, d_up=None, d_down=None, ws=None):
             raise ValueError(f"lora_grad writes contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
     if ws.dtype != torch.float32 or not ws.is_contiguous():
         raise ValueError("ws must be a contiguous fp32 workspace")
+    if accumulate:
+        libfk.check(libfk.load().fk_lora_grad_acc_bf16(_ptr(dw), dw.stride(0), _ptr(up), up.stride(0), _ptr(down), down.stride(0), N, K,
+                                                       r, float(scale), _ptr(d_up), _ptr(d_down), int(accumulate),
+                                                       _ptr(ws) if ws.numel() else None, ws.numel(), _stream()),
+                    "fk_lora_grad_acc_bf16")
+        return d_up, d_down
     libfk.check(libfk.load().fk_lora_grad_bf16(_ptr(dw), dw.stride(0), _ptr(up), up.stride(0), _ptr(down), down.stride(0), N, K, r,
                                                float(scale), _ptr(d_up), _ptr(d_down), _ptr(ws) if ws.numel() else None,
                                                ws.numel(), _stream()), "fk_lora_grad_bf16")

@@ -26,7 +26,9 @@ the loss only and the attention runs unmasked, as before.
 With ``lora=adapter_name`` the step trains a LoRA adapter's factors instead of the weights (``lora.py``, "Training"): the same
 forward and backward on the merged weights, each target weight's ``dW`` projected onto ``up`` / ``down`` as its block emits it
 (``fk_lora_grad_bf16``), AdamW on fp32 masters of the factors, then one re-merge per touched weight from its saved base.  The
-optimiser state is 12 bytes per ADAPTER parameter and only one block's ``dW`` is alive at a time.
+optimiser state is 12 bytes per ADAPTER parameter and only one block's ``dW`` is alive at a time.  With ``data_parallel=True`` as well
+the factors live in a ``zero.ShardedAdamW``: every ``dW`` is projected straight into the optimiser's fp32 gradient views
+(``fk_lora_grad_acc_bf16``, which can add to what is there), so the adapter has micro-batch accumulation and the data-parallel exchange.
 
 With ``optimizer="prodigy"`` the optimiser pass is Prodigy instead of AdamW (the reference's ``optimizer: 'prodigy'``,
 ``train_denoiser.py:603-624``; ``csrc/prodigy.hip``): ``fk_sumsq``, ``fk_prodigy_begin``, ``fk_prodigy_moments`` over the sorted names,
@@ -45,7 +47,7 @@ BF16 = torch.bfloat16
 class DenoiserTrainStep:
     def __init__(self, model, lr=None, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, trainable=None,
                  sharded=False, group=None, store_activations="auto", projector=None, keep_grads=True, bucket_numel=None,
-                 lora=None, optimizer="adamw", prodigy=None):
+                 lora=None, optimizer="adamw", prodigy=None, data_parallel=False):
         """sharded=True: the optimiser state lives in ``zero.ShardedAdamW`` (ZeRO-2: one flat bf16 parameter buffer the
         model's trainable tensors become views of, fp32 gradients reduce-scattered over the data-parallel ranks, this
         rank's slice of master + moments updated, parameters all-gathered); works unchanged with one process.
@@ -56,6 +58,12 @@ class DenoiserTrainStep:
         weights, with only the adapter's target weights in the wgrad set; each block's ``dW`` is projected onto the factors as it is
         emitted (``fk_lora_grad_bf16``) and dropped.  The trainable parameters are ``<module>.lora_A.weight`` (down) and
         ``<module>.lora_B.weight`` (up); other active adapters stay merged and frozen.  Not with ``sharded=True``.
+        data_parallel=True (with ``lora=``; ``group=`` / ``bucket_numel=`` as for ``sharded``): the factors (and any ``projector=``
+        parameters) become views of the flat bf16 buffer of a ``zero.ShardedAdamW`` in ``backward_order``; every ``dW`` is projected
+        STRAIGHT into the optimiser's fp32 gradient views (``fk_lora_grad_acc_bf16``: overwritten by the first micro-batch, added
+        to by later ones on one rank; staged and reduce-scattered with more ranks), so a second ``forward_backward`` before
+        ``optimizer_step`` is a further micro-batch and the step uses the mean over micro-batches and ranks.  All ranks must start
+        from the same factors (checked once, collectively).  Works unchanged with one process.
         optimizer="adamw" | "prodigy" (the reference's ``optimizer`` key, train_denoiser.py:595-624): Prodigy estimates its step
         size ``d`` on the fly (``csrc/prodigy.hip``; two more fp32 state tensors, ``s`` and the initial point ``p0``);
         ``prodigy=dict(beta3=, d0=, d_coef=, growth_rate=, use_bias_correction=, safeguard_warmup=, decouple=)`` overrides its
@@ -65,10 +73,14 @@ class DenoiserTrainStep:
         self.model = model
         self.projector = projector
         self.lora = lora
+        self.data_parallel = bool(data_parallel)
+        if data_parallel and lora is None:
+            raise ValueError("DenoiserTrainStep: data_parallel=True is the adapter's gradient accumulation / data-parallel mode and "
+                             "needs lora=; the full-weight step has both with sharded=True")
         if lora is not None:
             if sharded:
-                raise ValueError("DenoiserTrainStep: lora= with sharded=True is not built (no ZeRO / data-parallel exchange of "
-                                 "adapter gradients)")
+                raise ValueError("DenoiserTrainStep: lora= with sharded=True is not built (sharded=True lays out the full weights); "
+                                 "data_parallel=True gives an adapter gradient accumulation and the data-parallel exchange")
             if trainable is not None:
                 raise ValueError("DenoiserTrainStep: lora= trains the adapter's factors; trainable= selects full weights")
             if lora not in model._lora_adapters or lora not in model._lora_active:
@@ -87,6 +99,8 @@ class DenoiserTrainStep:
         self.opt = None
         self.keep_grads = keep_grads
         self._sunk = {}     # name -> (data_ptr, version) of the gradients already handed to the sharded optimiser
+        if data_parallel:
+            self._init_lora_dp(group, bucket_numel)
         if sharded:
             from .zero import DEFAULT_BUCKET, ShardedAdamW, backward_order
             names = sorted(self.trainable_names())
@@ -99,6 +113,26 @@ class DenoiserTrainStep:
             for k in names:
                 self._param(k).data = self.opt.params[k]     # the forward now reads views of the flat buffer
             model._packed = None
+
+    def _init_lora_dp(self, group, bucket_numel):
+        """``lora=`` with ``data_parallel=True``: the factors move into a ``ShardedAdamW``'s flat buffer (``e.up`` / ``e.down`` become
+        views of it, so the merge and ``lora_state_dict`` read the trained values with no copy), then ONE all-reduce verifies that
+        every rank starts from the same factors -- all ranks raise together or none does."""
+        from .zero import DEFAULT_BUCKET, ShardedAdamW, backward_order
+        names = sorted(self.trainable_names())
+        self.opt = ShardedAdamW({k: self._param(k).data for k in names}, lr=self.lr, betas=self.betas, eps=self.eps,
+                                weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm, group=group,
+                                order=backward_order(names), bucket_numel=bucket_numel or DEFAULT_BUCKET,
+                                **({} if self.optimizer == "adamw" else dict(optimizer=self.optimizer, prodigy=self.prodigy)))
+        for k in names:
+            if k.startswith(self.PROJ):
+                self._param(k).data = self.opt.params[k]
+                continue
+            for sfx, slot in ((self.LORA_A, "down"), (self.LORA_B, "up")):
+                if k.endswith(sfx):
+                    setattr(self._lora_entries[k[:-len(sfx)] + ".weight"], slot, self.opt.params[k])
+        self.opt.check_ranks_agree(f"DenoiserTrainStep(lora={self.lora!r}, data_parallel=True): create or load the adapter "
+                                   "identically on every rank, e.g. the same add_lora_adapter(seed=)")
 
     PROJ = "denoise_projector."
 
@@ -132,6 +166,20 @@ class DenoiserTrainStep:
             dev = self.model.device
             need = max(ops.lora_grad_ws(e.up.shape[0], e.down.shape[1], e.rank, dev).numel() for e in self._lora_entries.values())
             self._lora_ws = torch.empty(need, device=dev, dtype=torch.float32)
+
+        def dp_sink(block_grads):
+            # the two targets are the optimiser's own fp32 views: no gradient buffer of this step's, no copy
+            for pname, dw in block_grads.items():
+                e = self._lora_entries.get(pname)
+                if e is None:
+                    continue
+                mod = pname[:-len(".weight")]
+                (d_up, acc), (d_down, _) = self.opt.grad_target(mod + self.LORA_B), self.opt.grad_target(mod + self.LORA_A)
+                ops.lora_grad(dw, e.up, e.down, scales[pname], d_up=d_up, d_down=d_down, ws=self._lora_ws, accumulate=acc)
+                self.opt.written([mod + self.LORA_B, mod + self.LORA_A])
+                out[mod + self.LORA_B], out[mod + self.LORA_A] = d_up, d_down
+        if self.data_parallel:
+            return dp_sink
 
         def sink(block_grads):
             for pname, dw in block_grads.items():
@@ -250,14 +298,15 @@ class DenoiserTrainStep:
             missing = sorted(k for k in self.trainable_names() if not k.startswith(self.PROJ) and k not in lora_grads)
             if missing:
                 raise RuntimeError("the backward emitted no weight gradient for " + ", ".join(missing[:4]))
-            grads = lora_grads
+            # data_parallel: the live running sums on one rank (valid until optimizer_step); staged gradients are not kept
+            grads = lora_grads if self.opt is None or self.opt.direct else {}
         else:
             grads, d_enc = self.bw.backward(dsample, sink=sink, keep=self.keep_grads or self.opt is None)
         if n_proj:
             pg = {self.PROJ + k: g for k, g in self.projector.backward(d_enc[:, :n_proj]).items()}
             if sink is not None:
                 sink(pg)
-            if self.keep_grads or self.opt is None:
+            if (self.keep_grads and not self.data_parallel) or self.opt is None:
                 grads.update(pg)
         return loss, grads, d_enc
 
@@ -270,6 +319,8 @@ class DenoiserTrainStep:
             # without a gradient this step -- e.g. the projector on a batch that came with ready prompt_embeds -- count as 0
             rest = {}
             for k, g in grads.items():
+                if self.data_parallel and not k.startswith(self.PROJ):
+                    continue                  # a factor's gradient is already where the optimiser reads it
                 stamp = self._sunk.get(k)
                 if stamp is None:
                     rest[k] = g
@@ -283,6 +334,7 @@ class DenoiserTrainStep:
             self._sunk = {}
             norm = self.opt.step()
             self.step_count = self.opt.step_count
+            self._lora_remerge()              # data_parallel: every rank holds the same factors after the all-gather
             self.bw.refresh()
             return norm * norm
         sumsq = ops.sumsq([grads[k].contiguous() for k in names])
@@ -354,11 +406,19 @@ class DenoiserTrainStep:
             self.opt.zero_grad()
         self._sunk = {}
 
+    KINDS = dict(per_tensor="sharded=False, lora=None (kind 'per_tensor')", lora="lora= without data_parallel (kind 'lora')",
+                 sharded="sharded=True, lora=None (kind 'sharded')", lora_dp="lora= with data_parallel=True (kind 'lora_dp')")
+
+    def _kind(self):
+        if self.data_parallel:
+            return "lora_dp"
+        return "sharded" if self.opt is not None else "lora" if self.lora is not None else "per_tensor"
+
     def state_dict(self):
         """Optimiser state for ``accelerator.save_state``-style checkpoints (train_denoiser.py:1229): the ZeRO-2 shard of
         this rank (``zero.ShardedAdamW.state_dict``) or, unsharded, the per-tensor fp32 masters and moments."""
         if self.opt is not None:
-            return dict(kind="sharded", opt=self.opt.state_dict())
+            return dict(kind=self._kind(), opt=self.opt.state_dict())
         sd = dict(kind="lora" if self.lora is not None else "per_tensor", step=self.step_count,
                   state={k: tuple(t.detach().cpu().clone() for t in st) for k, st in self.state.items()})
         if self.optimizer == "prodigy":      # an AdamW state keeps exactly the keys it had
@@ -371,10 +431,10 @@ class DenoiserTrainStep:
     def load_state_dict(self, sd):
         """Resume (train_denoiser.py:349-367, 769): restores the state and rewrites the model's trainable bf16 parameters from
         the fp32 masters, so the next step continues bit for bit."""
-        if (sd.get("kind") == "sharded") != (self.opt is not None):
-            raise ValueError("optimiser state was saved with another `sharded` setting")
-        if (sd.get("kind") == "lora") != (self.lora is not None):
-            raise ValueError("optimiser state was saved with another `lora` setting")
+        kind = sd.get("kind", "per_tensor")
+        if kind != self._kind():
+            raise ValueError(f"optimiser state was saved with {self.KINDS.get(kind, repr(kind))}, this step runs with "
+                             f"{self.KINDS[self._kind()]}")
         saved_opt = (sd["opt"] if self.opt is not None else sd).get("optimizer", "adamw")
         if saved_opt != self.optimizer:
             raise ValueError(f"optimiser state was saved by optimizer={saved_opt!r}, this step runs optimizer={self.optimizer!r}")

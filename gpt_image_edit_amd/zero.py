@@ -16,6 +16,9 @@ This module is that exchange written for one process per GPU over ``torch.distri
     bucket's fp32 staging buffer; the moment a bucket is complete its ``reduce_scatter_tensor(SUM)`` is issued
     asynchronously, so it runs under the backward of the earlier blocks.  Two staging buffers alternate; a rank keeps
     only ITS chunk of every reduced bucket (gradient memory: 2 buckets + total / world, not the whole set).
+  * ``grad_target(name)`` / ``written(names)`` are the same intake for a kernel that writes a gradient IN PLACE (the LoRA
+    projection of ``DenoiserTrainStep(lora=, data_parallel=True)``): the fp32 view to write, whether the kernel must add to it
+    (one rank, no staging, a later micro-batch -- the case in which ``accumulate`` adds) and the report that starts the reduction.
   * ``step()``: wait for the outstanding reductions; ``fk_sumsq`` of the local chunks + one scalar all-reduce = the global
     norm (``accelerator.clip_grad_norm_``, ``train_denoiser.py:1171-1177``); ``fk_adamw_step_scaled`` per bucket chunk
     -- the 1 / world of the gradient MEAN is folded into the clipping coefficient, no pass divides the sums -- writing
@@ -221,6 +224,24 @@ class ShardedAdamW:
         out["k"], out["skipped"] = int(out["k"]), bool(out["skipped"])
         return out
 
+    def check_ranks_agree(self, what=""):
+        """Collective, a no-op on one rank: verify that every rank holds the same flat bf16 parameters (a rank-dependent seed is
+        the easy mistake) with ONE all-reduce of a checksum -- the fp64 sum and sum of squares, as MAX of (x, -x) = (max, -min).
+        Every rank sees the same reduced values and so takes the same decision: all raise ``ValueError`` or none does, and no
+        rank is left behind in a later collective.  A NaN checksum raises too."""
+        if self.world == 1:
+            return
+        flat = self.flat_param.double()
+        mine = torch.stack([flat.sum(), flat.pow(2).sum()])
+        both = torch.cat([mine, -mine])
+        if self._host_staged:                             # gloo cannot exchange device tensors
+            both = both.cpu()
+        dist.all_reduce(both, op=dist.ReduceOp.MAX, group=self.group)
+        hi, lo = both[:2].tolist(), (-both[2:]).tolist()
+        if not (hi[0] == lo[0] and hi[1] == lo[1]):
+            raise ValueError(f"the ranks start from different parameters (checksums over the ranks: sum in [{lo[0]!r}, {hi[0]!r}], "
+                             f"sum of squares in [{lo[1]!r}, {hi[1]!r}])" + (": " + what if what else ""))
+
     # ---- gradient intake ---------------------------------------------------------------------------------------------
     def _begin(self):
         self._micro = 0            # micro-batches whose gradients are already part of grad_slice
@@ -308,6 +329,36 @@ class ShardedAdamW:
             self._seen[b].add(n)
             if len(self._seen[b]) == len(L.buckets[b]["names"]):
                 self._reduce(b)
+
+    def grad_target(self, name):
+        """(fp32 view, accumulate) for a kernel that WRITES the gradient of ``name`` in place instead of handing a finished tensor
+        to ``accumulate()`` (the LoRA projection, ``train_step.DenoiserTrainStep(lora=, data_parallel=True)``).  ``accumulate`` is
+        True in the one case in which ``accumulate()`` adds: one rank, no staging, a later micro-batch -- the view then holds the
+        running sum and the kernel must add to it.  Otherwise the kernel overwrites the view: this rank's chunk on the first
+        micro-batch of one rank, else the zeroed staging buffer, whose reduce-then-add path is the one ``accumulate()`` takes.
+        The view is a contiguous slice at whatever offset the layout gives the tensor (4-byte aligned, no more).  Report the
+        write with ``written([name])``: until then nothing is marked."""
+        self._writable(name)
+        return self.grad_view(name), bool(self.direct and self._micro)
+
+    def written(self, names):
+        """The gradients of ``names`` have been written (enqueued on the current stream) into their ``grad_target`` views: mark
+        them seen and start the reduction of every bucket they complete, exactly as ``accumulate()`` does after its copies."""
+        L = self.layout
+        for n in sorted(names, key=lambda n: L.offsets[n][0]):
+            b = self._writable(n)
+            self._seen[b].add(n)
+            if len(self._seen[b]) == len(L.buckets[b]["names"]):
+                self._reduce(b)
+
+    def _writable(self, name):
+        b = self.layout.bucket_of[name]
+        if self._launched[b]:
+            raise RuntimeError(f"gradient of {name} arrived after its bucket was reduced: a second backward pass before step() must "
+                               "be announced with begin_micro_batch() (gradient accumulation)")
+        if name in self._seen[b]:
+            raise RuntimeError(f"gradient of {name} arrived twice in one pass")
+        return b
 
     def _reduce(self, b):
         bk = self.layout.buckets[b]

@@ -867,6 +867,16 @@ int64_t fk_lora_grad_ws_floats(int32_t N, int32_t K, int32_t rank);
 int fk_lora_grad_bf16(const void* dw, int64_t ld_dw, const void* up, int64_t ld_up, const void* down, int64_t ld_down,
                       int32_t N, int32_t K, int32_t rank, float scale, float* d_up, float* d_down, float* ws,
                       int64_t ws_floats, fk_stream_t stream);
+/* The same projection with a choice of what happens to the outputs (gradient accumulation over micro-batches; train_step.py:
+ * DenoiserTrainStep(lora=..., data_parallel=True)).  accumulate = 0: overwrite -- exactly fk_lora_grad_bf16, the outputs are never
+ * read (they may hold NaN bits).  accumulate = 1: d_up[n, j] = d_up_old[n, j] + scale * sum_k ..., likewise d_down; the thread
+ * that owns an element reads it once and writes it once, where the scaled value is formed (the final store of an unsplit role, the
+ * reduction of a split one; partials are never added to).  Still no atomics and an order fixed by (N, K, rank): two identical call
+ * sequences give the same bits.  The outputs need only 4-byte alignment (views anywhere inside a flat fp32 buffer).  Any other
+ * value of accumulate returns FK_EINVAL and writes nothing. */
+int fk_lora_grad_acc_bf16(const void* dw, int64_t ld_dw, const void* up, int64_t ld_up, const void* down, int64_t ld_down,
+                          int32_t N, int32_t K, int32_t rank, float scale, float* d_up, float* d_down, int32_t accumulate,
+                          float* ws, int64_t ws_floats, fk_stream_t stream);
 
 const char* fk_last_error(void);
 /* Build identification: "fk <version> gfx950". */

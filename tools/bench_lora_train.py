@@ -1,6 +1,7 @@
 """Timing of LoRA training on one MI355X (development aid; bench.py is the contract benchmark).
 
     python tools/bench_lora_train.py [--ranks 16,64,128] [--steps 3] [--warmup 2] [--out profiles/lora_train.json]
+    python tools/bench_lora_train.py --data_parallel [--micro_batches 2] [--ranks 16] [--out profiles/lora_train_dp.json]
 
 Full-size model (19 + 38 blocks, synthetic weights) at the cfg 5 shape (1024^2, batch 1: 512 text + 4096 target + 4096 condition
 tokens), ready ``prompt_embeds`` (no projector on either side):
@@ -11,6 +12,13 @@ tokens), ready ``prompt_embeds`` (no projector on either side):
 3. per rank, the summed time of the ``fk_lora_grad_bf16`` launches of one step (one per target weight, on the q / k / v row blocks
    of a [3D, D] gradient as the step issues them) beside the wgrad GEMMs they follow (``backward.wgrad`` at the step's token
    count), both on random operands, each list timed as one bracket of events.
+
+With ``--data_parallel`` (world 1; ``--micro_batches N`` backward passes per step, default 1) the record is the flat mode beside
+the per-tensor one, to ``profiles/lora_train_dp.json``: per rank, ms per step and peak memory of ``DenoiserTrainStep(model, lora=...)``
+and of ``DenoiserTrainStep(model, lora=..., data_parallel=True)`` on the same batches (with N > 1 the per-tensor step runs the same N
+backward passes, each overwriting the last: the same work, not the same mathematics), and the summed time of one step's
+projection launches in overwrite form (``fk_lora_grad_bf16``) and in accumulate form (``fk_lora_grad_acc_bf16``, accumulate = 1).
+The full stage-2 step is left out of this record.
 
 Every phase builds its own model and frees it; peak memory is reset in between.  No threshold is asserted anywhere.
 """
@@ -40,21 +48,25 @@ def batch_of(device):
                 pooled=torch.randn(B, 768, generator=g, device=device).to(BF)), S_txt + 2 * (h // 2) * (w // 2)
 
 
-def timed_steps(ts, batch, steps, warmup):
+def timed_steps(ts, batch, steps, warmup, micro_batches=1):
+    def one():
+        for _ in range(micro_batches - 1):
+            ts.forward_backward(**batch)
+        return ts.step(**batch)
     for _ in range(warmup):
-        out = ts.step(**batch)
+        out = one()
     torch.cuda.synchronize()
     ms = []
     for _ in range(steps):
         t0 = time.perf_counter()
-        out = ts.step(**batch)
+        out = one()
         torch.cuda.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3)
     assert torch.isfinite(out["loss"]).all()
     return ms
 
 
-def phase(build, steps, warmup, device):
+def phase(build, steps, warmup, device, micro_batches=1):
     from gpt_image_edit_amd import flux_spec
     from gpt_image_edit_amd.transformer import HipFluxTransformer2DModel
     gc.collect()
@@ -63,7 +75,7 @@ def phase(build, steps, warmup, device):
     model = HipFluxTransformer2DModel(dict(flux_spec.FLUX_KONTEXT_CONFIG), device=device, init="synthetic", seed=0)
     ts = build(model)
     batch, _ = batch_of(device)
-    ms = timed_steps(ts, batch, steps, warmup)
+    ms = timed_steps(ts, batch, steps, warmup, micro_batches)
     n_train = sum(ts._param(k).numel() for k in ts.trainable_names())
     res = dict(ms_per_step_median=statistics.median(ms), ms_per_step=ms, trainable_params=n_train,
                peak_memory_gb=torch.cuda.max_memory_allocated(device) / 1e9)
@@ -85,7 +97,7 @@ def bracket_ms(fn, reps):
     return out
 
 
-def kernels(rank, S, device, reps, D=3072, n_double=19, n_single=38):
+def kernels(rank, S, device, reps, D=3072, n_double=19, n_single=38, accumulate_arm=False):
     """One step's projection launches beside the wgrad GEMMs in front of them, on random operands."""
     from gpt_image_edit_amd import backward, ops
     g = torch.Generator(device=device).manual_seed(rank)
@@ -108,14 +120,20 @@ def kernels(rank, S, device, reps, D=3072, n_double=19, n_single=38):
         for _ in range(n_double):
             backward.wgrad(buf, dy1, x, out=dw1)
 
-    def projections():
+    def projections(accumulate=False):
         for _ in range(n_double + n_single):
             for k in range(3):
-                ops.lora_grad(dw3[k * D:(k + 1) * D], up, down, 1.0, d_up=d_up, d_down=d_down, ws=ws)
+                ops.lora_grad(dw3[k * D:(k + 1) * D], up, down, 1.0, d_up=d_up, d_down=d_down, ws=ws, accumulate=accumulate)
         for _ in range(n_double):
-            ops.lora_grad(dw1, up, down, 1.0, d_up=d_up, d_down=d_down, ws=ws)
-    w, p = bracket_ms(wgrads, reps), bracket_ms(projections, reps)
+            ops.lora_grad(dw1, up, down, 1.0, d_up=d_up, d_down=d_down, ws=ws, accumulate=accumulate)
     n = 3 * (n_double + n_single) + n_double
+    if accumulate_arm:
+        d_up.zero_(), d_down.zero_()
+        p, a = bracket_ms(projections, reps), bracket_ms(lambda: projections(True), reps)
+        return dict(launches=n, overwrite_ms_median=statistics.median(p), accumulate_ms_median=statistics.median(a),
+                    accumulate_over_overwrite=statistics.median(a) / statistics.median(p), overwrite_ms=p, accumulate_ms=a,
+                    note="both brackets include the host loop (one ctypes call per launch)")
+    w, p = bracket_ms(wgrads, reps), bracket_ms(projections, reps)
     return dict(launches=n, wgrad_ms_median=statistics.median(w), lora_grad_ms_median=statistics.median(p),
                 lora_grad_us_per_launch=1e3 * statistics.median(p) / n,
                 lora_grad_gb_per_s=n * 4 * D * D / 1e9 / (statistics.median(p) / 1e3),       # dW read twice: 4 B per element
@@ -130,14 +148,37 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skip_full", action="store_true", help="leave out the full stage-2 step (48 GB of optimiser state)")
-    ap.add_argument("--out", default="profiles/lora_train.json")
+    ap.add_argument("--data_parallel", action="store_true", help="record the flat data_parallel=True step beside the per-tensor one")
+    ap.add_argument("--micro_batches", type=int, default=1, help="backward passes per step (with --data_parallel)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = "profiles/lora_train_dp.json" if args.data_parallel else "profiles/lora_train.json"
+    if args.micro_batches != 1 and not args.data_parallel:
+        raise SystemExit("--micro_batches belongs to --data_parallel")
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU: a timing from anything else says nothing")
     from gpt_image_edit_amd.train_step import DenoiserTrainStep
     dev = "cuda"
     _, S = batch_of(dev)
     res = dict(device=torch.cuda.get_device_name(0), shape="cfg5 1024x1024 bs1", seq_len=S, steps=args.steps, warmup=args.warmup, ranks=[])
+    if args.data_parallel:
+        res.update(world=1, micro_batches=args.micro_batches)
+        for rank in [int(r) for r in args.ranks.split(",")]:
+            def build(m, dp, rank=rank):
+                m.add_lora_adapter("bench", rank=rank)
+                return DenoiserTrainStep(m, lora="bench", data_parallel=dp)
+            entry = dict(rank=rank,
+                         lora_step=phase(lambda m: build(m, False), args.steps, args.warmup, dev, args.micro_batches),
+                         lora_dp_step=phase(lambda m: build(m, True), args.steps, args.warmup, dev, args.micro_batches),
+                         kernels=kernels(rank, S, dev, args.reps, accumulate_arm=True))
+            res["ranks"].append(entry)
+            print(json.dumps({"rank": rank, **{a: {k: v for k, v in entry[a].items() if k != "ms_per_step"} for a in ("lora_step", "lora_dp_step")},
+                              "kernels": {k: v for k, v in entry["kernels"].items() if not k.endswith("_ms")}}), flush=True)
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if not args.skip_full:
         res["full_step"] = phase(lambda m: DenoiserTrainStep(m), args.steps, args.warmup, dev)
         print(json.dumps({"full_step": {k: v for k, v in res["full_step"].items() if k != "ms_per_step"}}), flush=True)
