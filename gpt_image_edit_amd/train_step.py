@@ -6,7 +6,8 @@ configuration (continuous timesteps, unit loss weights, guidance 1.0, AdamW, glo
 checkpoint per block and backward (``backward.FluxBackward``), flow-matching loss fused with its gradient
 (``fk_flow_loss_bf16``), squared gradient norm (``fk_sumsq``) and AdamW with the clipping coefficient folded in and the
 bf16 parameter copy written in the same pass (``fk_adamw_step``).  The step's scalars (which parameters train, sigma
-sampling, shift) are ``training.py``; the data-parallel exchange is ``zero.py``.  No torch arithmetic touches an
+sampling, shift) are ``training.py``; the optimiser pass and the unsharded state are ``optim.py``; the data-parallel exchange
+is ``zero.py``.  No torch arithmetic touches an
 activation, gradient or parameter.
 
 With ``projector=`` the ``denoise_projector`` trains along (it is in the reference's trainable set,
@@ -39,7 +40,8 @@ import torch
 
 from . import helpers, ops
 from .backward import FluxBackward
-from .zero import PRODIGY_SLOTS, resolve_optimizer
+from .optim import PerTensorState
+from .zero import DEFAULT_BUCKET, ShardedAdamW, backward_order
 
 BF16 = torch.bfloat16
 
@@ -69,7 +71,9 @@ class DenoiserTrainStep:
         ``prodigy=dict(beta3=, d0=, d_coef=, growth_rate=, use_bias_correction=, safeguard_warmup=, decouple=)`` overrides its
         defaults (the reference config's: the three flags True).  ``lr=None`` is 1e-6 for AdamW and 1.0 for Prodigy; Prodigy
         with ``lr <= 0.1`` is refused as the reference refuses it (:609-612)."""
-        self.optimizer, lr, self.prodigy = resolve_optimizer(optimizer, lr, prodigy)
+        # the unsharded optimiser (its refusals come before the model is touched); unused once `opt` below is set
+        self.local = PerTensorState(self._param, optimizer, lr, betas, eps, weight_decay, max_grad_norm, prodigy)
+        self.optimizer, self.lr, self.prodigy = self.local.optimizer, self.local.hp["lr"], self.local.prodigy
         self.model = model
         self.projector = projector
         self.lora = lora
@@ -88,59 +92,61 @@ class DenoiserTrainStep:
                                  "load_lora_adapter / set_adapters before the train step is built)")
             model.set_lora_scale(1.0)          # the scale of the projection is the one the weights were merged with
             self._lora_entries = model._lora_adapters[lora]
-            self._lora_grads = {}              # parameter name -> (d_up, d_down): persistent fp32 gradient buffers
             self._lora_ws = None
         self.bw = FluxBackward(model, trainable, store_activations=store_activations, lora=lora)
-        self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
-        self.step_count = 0
-        self.state = {}     # name -> (fp32 master, exp_avg, exp_avg_sq); Prodigy: (master, m, v, s, p0)
-        self.pstate = None  # Prodigy: the fp64 scalar buffer on the device (include/fk.h FK_PRODIGY_*), created at the first step
-        self._pws = None
-        self.opt = None
+        self.betas, self.eps, self.weight_decay, self.max_grad_norm = betas, eps, weight_decay, max_grad_norm
+        self.opt = None     # the zero.ShardedAdamW of sharded=True / data_parallel=True
         self.keep_grads = keep_grads
         self._sunk = {}     # name -> (data_ptr, version) of the gradients already handed to the sharded optimiser
-        if data_parallel:
-            self._init_lora_dp(group, bucket_numel)
+        if sharded or data_parallel:
+            self.opt = self._flat_optimizer(group, bucket_numel)
         if sharded:
-            from .zero import DEFAULT_BUCKET, ShardedAdamW, backward_order
-            names = sorted(self.trainable_names())
-            # buckets in the order the backward pass finishes the gradients: a bucket's reduce-scatter is issued the moment
-            # its last block is done and runs under the backward of the earlier blocks (zero2.json: overlap_comm)
-            self.opt = ShardedAdamW({k: self._param(k).data for k in names}, lr=lr, betas=betas, eps=eps,
-                                    weight_decay=weight_decay, max_grad_norm=max_grad_norm, group=group,
-                                    order=backward_order(names), bucket_numel=bucket_numel or DEFAULT_BUCKET,
-                                    **({} if self.optimizer == "adamw" else dict(optimizer=self.optimizer, prodigy=self.prodigy)))
-            for k in names:
-                self._param(k).data = self.opt.params[k]     # the forward now reads views of the flat buffer
             model._packed = None
+        if data_parallel:        # ONE all-reduce: all ranks raise together or none does
+            self.opt.check_ranks_agree(f"DenoiserTrainStep(lora={self.lora!r}, data_parallel=True): create or load the adapter "
+                                       "identically on every rank, e.g. the same add_lora_adapter(seed=)")
 
-    def _init_lora_dp(self, group, bucket_numel):
-        """``lora=`` with ``data_parallel=True``: the factors move into a ``ShardedAdamW``'s flat buffer (``e.up`` / ``e.down`` become
-        views of it, so the merge and ``lora_state_dict`` read the trained values with no copy), then ONE all-reduce verifies that
-        every rank starts from the same factors -- all ranks raise together or none does."""
-        from .zero import DEFAULT_BUCKET, ShardedAdamW, backward_order
+    # the optimiser's own state, under the names it had when it was kept here
+    state = property(lambda self: self.local.state)              # name -> (fp32 master, exp_avg, exp_avg_sq) (+ s, p0: Prodigy)
+    pstate = property(lambda self: self.local.pstate)
+    _optim = property(lambda self: self.opt or self.local)       # the optimiser in use: both have the same calls
+    step_count = property(lambda self: self._optim.step_count)
+
+    def _flat_optimizer(self, group, bucket_numel):
+        """The ``ShardedAdamW`` of ``sharded=True`` and ``data_parallel=True``: every trainable tensor (with ``lora=``: ``e.up`` /
+        ``e.down``, so the merge and ``lora_state_dict`` read the trained values with no copy) becomes a view of its flat bf16 buffer.
+        Buckets in the order the backward pass finishes the gradients: a bucket's reduce-scatter is issued the moment its last block
+        is done and runs under the backward of the earlier blocks (zero2.json: overlap_comm)."""
         names = sorted(self.trainable_names())
-        self.opt = ShardedAdamW({k: self._param(k).data for k in names}, lr=self.lr, betas=self.betas, eps=self.eps,
-                                weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm, group=group,
-                                order=backward_order(names), bucket_numel=bucket_numel or DEFAULT_BUCKET,
-                                **({} if self.optimizer == "adamw" else dict(optimizer=self.optimizer, prodigy=self.prodigy)))
-        for k in names:
-            if k.startswith(self.PROJ):
-                self._param(k).data = self.opt.params[k]
-                continue
-            for sfx, slot in ((self.LORA_A, "down"), (self.LORA_B, "up")):
-                if k.endswith(sfx):
-                    setattr(self._lora_entries[k[:-len(sfx)] + ".weight"], slot, self.opt.params[k])
-        self.opt.check_ranks_agree(f"DenoiserTrainStep(lora={self.lora!r}, data_parallel=True): create or load the adapter "
-                                   "identically on every rank, e.g. the same add_lora_adapter(seed=)")
+        opt = ShardedAdamW({k: self._param(k).data for k in names}, lr=self.lr, betas=self.betas, eps=self.eps,
+                           weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm, group=group,
+                           order=backward_order(names), bucket_numel=bucket_numel or DEFAULT_BUCKET,
+                           **({} if self.optimizer == "adamw" else dict(optimizer=self.optimizer, prodigy=self.prodigy)))
+        for k in names:          # the forward now reads views of the flat buffer
+            if self.lora is not None and not k.startswith(self.PROJ):
+                setattr(*self._factor(k), opt.params[k])
+            else:
+                self._param(k).data = opt.params[k]
+        return opt
 
     PROJ = "denoise_projector."
 
     LORA_A, LORA_B = ".lora_A.weight", ".lora_B.weight"
 
+    def _factor(self, name):
+        """(adapter entry, "up" | "down") of the factor ``name``."""
+        for sfx, slot in ((self.LORA_A, "down"), (self.LORA_B, "up")):
+            if name.endswith(sfx):
+                return self._lora_entries[name[:-len(sfx)] + ".weight"], slot
+        raise KeyError(f"{name} is no factor of adapter {self.lora!r}")
+
+    def _factor_names(self, pname):
+        """(name of up, name of down) for the target weight ``pname``: the inverse of ``_factor``."""
+        return pname[:-len(".weight")] + self.LORA_B, pname[:-len(".weight")] + self.LORA_A
+
     def trainable_names(self):
         if self.lora is not None:
-            names = {k[:-len(".weight")] + sfx for k in self._lora_entries for sfx in (self.LORA_A, self.LORA_B)}
+            names = {n for k in self._lora_entries for n in self._factor_names(k)}
         else:
             names = set(self.bw.trainable)
         if self.projector is not None:
@@ -151,60 +157,32 @@ class DenoiserTrainStep:
         if name.startswith(self.PROJ):
             return self.projector.p(name[len(self.PROJ):])
         if self.lora is not None:
-            for sfx, slot in ((self.LORA_A, "down"), (self.LORA_B, "up")):
-                if name.endswith(sfx):
-                    return getattr(self._lora_entries[name[:-len(sfx)] + ".weight"], slot)
-            raise KeyError(f"{name} is no factor of adapter {self.lora!r}")
+            return getattr(*self._factor(name))
         return self.model.p(name)
 
     def _lora_sink(self, out):
-        """The sink of ``FluxBackward.backward`` under ``lora=``: every emitted ``dW`` of a target weight is projected onto
-        its two factors (one ``fk_lora_grad_bf16`` call) into the persistent fp32 buffers; ``out`` collects them by name."""
+        """The sink of ``FluxBackward.backward`` under ``lora=``: every emitted ``dW`` of a target weight is projected onto its two
+        factors (one ``fk_lora_grad_bf16`` / ``fk_lora_grad_acc_bf16`` call) into the optimiser's two fp32 targets -- persistent buffers
+        of ``PerTensorState``, the gradient views of ``ShardedAdamW`` (no buffer of this step's, no copy); ``out`` collects them by name."""
         scales = {p: next(s for a, s, _ in ts if a == self.lora) for p, ts in self.model._lora_wanted().items()
                   if any(a == self.lora for a, _, _ in ts)}
         if self._lora_ws is None:
             dev = self.model.device
             need = max(ops.lora_grad_ws(e.up.shape[0], e.down.shape[1], e.rank, dev).numel() for e in self._lora_entries.values())
             self._lora_ws = torch.empty(need, device=dev, dtype=torch.float32)
-
-        def dp_sink(block_grads):
-            # the two targets are the optimiser's own fp32 views: no gradient buffer of this step's, no copy
-            for pname, dw in block_grads.items():
-                e = self._lora_entries.get(pname)
-                if e is None:
-                    continue
-                mod = pname[:-len(".weight")]
-                (d_up, acc), (d_down, _) = self.opt.grad_target(mod + self.LORA_B), self.opt.grad_target(mod + self.LORA_A)
-                ops.lora_grad(dw, e.up, e.down, scales[pname], d_up=d_up, d_down=d_down, ws=self._lora_ws, accumulate=acc)
-                self.opt.written([mod + self.LORA_B, mod + self.LORA_A])
-                out[mod + self.LORA_B], out[mod + self.LORA_A] = d_up, d_down
-        if self.data_parallel:
-            return dp_sink
+        optim = self._optim
 
         def sink(block_grads):
             for pname, dw in block_grads.items():
                 e = self._lora_entries.get(pname)
                 if e is None:                  # the rest of a q / k / v group, a bias: not this adapter's
                     continue
-                bufs = self._lora_grads.get(pname)
-                if bufs is None:
-                    bufs = self._lora_grads[pname] = (torch.empty(e.up.shape, device=dw.device, dtype=torch.float32),
-                                                      torch.empty(e.down.shape, device=dw.device, dtype=torch.float32))
-                ops.lora_grad(dw, e.up, e.down, scales[pname], d_up=bufs[0], d_down=bufs[1], ws=self._lora_ws)
-                mod = pname[:-len(".weight")]
-                out[mod + self.LORA_B], out[mod + self.LORA_A] = bufs
+                up, down = self._factor_names(pname)
+                (d_up, acc), (d_down, _) = optim.grad_target(up), optim.grad_target(down)
+                ops.lora_grad(dw, e.up, e.down, scales[pname], d_up=d_up, d_down=d_down, ws=self._lora_ws, accumulate=acc)
+                optim.written([up, down])
+                out[up], out[down] = d_up, d_down
         return sink
-
-    def _state(self, name):
-        st = self.state.get(name)
-        if st is None:
-            p = self._param(name)
-            st = (p.detach().float().contiguous(), torch.zeros(p.shape, device=p.device, dtype=torch.float32),
-                  torch.zeros(p.shape, device=p.device, dtype=torch.float32))
-            if self.optimizer == "prodigy":     # + s and the point the distance estimate is measured from
-                st = st + (torch.zeros(p.shape, device=p.device, dtype=torch.float32), st[0].clone())
-            self.state[name] = st
-        return st
 
     @torch.no_grad()
     def prepare_inputs(self, model_input, cond_latents, noise, sigmas, prompt_embeds, pooled, guidance_scale=1.0):
@@ -312,79 +290,41 @@ class DenoiserTrainStep:
 
     @torch.no_grad()
     def optimizer_step(self, grads):
-        """Global-norm clipping + AdamW on fp32 masters; the bf16 parameters of the model are rewritten in the same pass."""
-        names = sorted(grads)
-        if self.opt is not None:
-            # whatever forward_backward has not already handed to the buckets (gradients from another source); tensors
-            # without a gradient this step -- e.g. the projector on a batch that came with ready prompt_embeds -- count as 0
-            rest = {}
-            for k, g in grads.items():
-                if self.data_parallel and not k.startswith(self.PROJ):
-                    continue                  # a factor's gradient is already where the optimiser reads it
-                stamp = self._sunk.get(k)
-                if stamp is None:
-                    rest[k] = g
-                elif stamp != (g.data_ptr(), g._version):
-                    raise RuntimeError(f"optimizer_step: the gradient passed for {k} is not the one forward_backward already "
-                                       "handed to the sharded optimiser (it was replaced or modified in place afterwards) and "
-                                       "would be ignored: with sharded=True accumulate by calling forward_backward again, and "
-                                       "scale through lr / max_grad_norm, not on the returned tensors")
+        """Global-norm clipping + the optimiser pass on fp32 masters (``optim.optimizer_pass``); the bf16 parameters of the model
+        are rewritten in the same pass.  Returns the squared gradient norm."""
+        # whatever forward_backward has not already handed to the flat optimiser's buckets (gradients from another source;
+        # without one: all of them); tensors without a gradient this step -- e.g. the projector on a batch that came with ready
+        # prompt_embeds -- count as 0 there
+        rest = {}
+        for k, g in grads.items():
+            if self.data_parallel and not k.startswith(self.PROJ):
+                continue                  # a factor's gradient is already where the optimiser reads it
+            stamp = self._sunk.get(k)
+            if stamp is None:
+                rest[k] = g
+            elif stamp != (g.data_ptr(), g._version):
+                raise RuntimeError(f"optimizer_step: the gradient passed for {k} is not the one forward_backward already "
+                                   "handed to the sharded optimiser (it was replaced or modified in place afterwards) and "
+                                   "would be ignored: with sharded=True accumulate by calling forward_backward again, and "
+                                   "scale through lr / max_grad_norm, not on the returned tensors")
+        self._sunk = {}
+        if self.opt is None:
+            sumsq = self.local.step(rest)
+        else:
             if rest:
                 self.opt.accumulate(rest)
-            self._sunk = {}
             norm = self.opt.step()
-            self.step_count = self.opt.step_count
-            self._lora_remerge()              # data_parallel: every rank holds the same factors after the all-gather
-            self.bw.refresh()
-            return norm * norm
-        sumsq = ops.sumsq([grads[k].contiguous() for k in names])
-        self.step_count += 1
-        if self.optimizer == "prodigy":
-            self._prodigy_step(names, grads, sumsq)
-            self._lora_remerge()
-            self.bw.refresh()
-            return sumsq
-        for k in names:
-            master, m1, m2 = self._state(k)
-            ops.adamw_step(master, grads[k].contiguous(), m1, m2, self.step_count, self.lr, self.betas, self.eps,
-                           self.weight_decay, grad_sumsq=sumsq, max_grad_norm=self.max_grad_norm, param_bf16=self._param(k).data)
-        self._lora_remerge()
+            sumsq = norm * norm
+        self._lora_remerge()              # data_parallel: every rank holds the same factors after the all-gather
         self.bw.refresh()
         return sumsq
-
-    def _prodigy_step(self, names, grads, sumsq):
-        """begin, moments over the sorted names (their two sums accumulate on the device in that order), update_d, apply over the
-        same names.  Nothing is read back: ``d``, the step count of the bias correction and the zero-gradient rule are device-side."""
-        hp = self.prodigy
-        dev = grads[names[0]].device
-        if self.pstate is None:
-            self.pstate = ops.prodigy_init_state(hp["d0"], dev)
-        if self._pws is None:
-            self._pws = ops.prodigy_ws(dev)
-        ops.prodigy_begin(self.pstate, self.lr, self.betas, hp["beta3"], hp["use_bias_correction"])
-        for k in names:
-            master, m, v, s, p0 = self._state(k)
-            ops.prodigy_moments(master, p0, grads[k].contiguous(), m, v, s, self.pstate, betas=self.betas, beta3=hp["beta3"],
-                                weight_decay=self.weight_decay, d0=hp["d0"], decouple=hp["decouple"],
-                                safeguard_warmup=hp["safeguard_warmup"], grad_sumsq=sumsq, max_grad_norm=self.max_grad_norm,
-                                ws=self._pws)
-        ops.prodigy_update_d(self.pstate, hp["d0"], hp["d_coef"], hp["growth_rate"])
-        for k in names:
-            master, m, v, _, _ = self._state(k)
-            ops.prodigy_apply(master, m, v, self.pstate, eps=self.eps, weight_decay=self.weight_decay, decouple=hp["decouple"],
-                              param_bf16=self._param(k).data)
 
     def prodigy_state(self):
         """The Prodigy scalars (``d``, ``dlr``, ``k``, ...; ``ops.prodigy_state``) as python numbers -- this synchronises; log
         ``d * lr`` from it as the reference does (train_denoiser.py:1364-1373)."""
         if self.optimizer != "prodigy":
             raise RuntimeError("prodigy_state(): the optimiser is " + self.optimizer)
-        if self.opt is not None:
-            return self.opt.prodigy_state()
-        if self.pstate is None:
-            d0 = float(self.prodigy["d0"])
-            return dict(zip(PRODIGY_SLOTS, [d0, d0] + [0.0] * 4 + [0, False, 0.0, 0.0]))
-        return ops.prodigy_state(self.pstate)
+        return self._optim.prodigy_state()
 
     def _lora_remerge(self):
         """The factors changed: re-merge exactly the weights the trained adapter touches, one launch each, from their bases.  The
@@ -419,13 +359,7 @@ class DenoiserTrainStep:
         this rank (``zero.ShardedAdamW.state_dict``) or, unsharded, the per-tensor fp32 masters and moments."""
         if self.opt is not None:
             return dict(kind=self._kind(), opt=self.opt.state_dict())
-        sd = dict(kind="lora" if self.lora is not None else "per_tensor", step=self.step_count,
-                  state={k: tuple(t.detach().cpu().clone() for t in st) for k, st in self.state.items()})
-        if self.optimizer == "prodigy":      # an AdamW state keeps exactly the keys it had
-            sd.update(optimizer="prodigy", hp=dict(self.prodigy, lr=self.lr, betas=tuple(self.betas), eps=self.eps,
-                                                   weight_decay=self.weight_decay),
-                      scalars=None if self.pstate is None else self.pstate.detach().cpu().clone())
-        return sd
+        return dict(kind=self._kind(), **self.local.state_dict())
 
     @torch.no_grad()
     def load_state_dict(self, sd):
@@ -435,24 +369,12 @@ class DenoiserTrainStep:
         if kind != self._kind():
             raise ValueError(f"optimiser state was saved with {self.KINDS.get(kind, repr(kind))}, this step runs with "
                              f"{self.KINDS[self._kind()]}")
-        saved_opt = (sd["opt"] if self.opt is not None else sd).get("optimizer", "adamw")
+        inner = sd["opt"] if self.opt is not None else sd
+        saved_opt = inner.get("optimizer", "adamw")
         if saved_opt != self.optimizer:
             raise ValueError(f"optimiser state was saved by optimizer={saved_opt!r}, this step runs optimizer={self.optimizer!r}")
         self._sunk = {}
-        if self.opt is not None:
-            self.opt.load_state_dict(sd["opt"])
-            self.step_count = self.opt.step_count
-        else:
-            self.step_count = int(sd["step"])
-            self.state = {}
-            for k, st in sd["state"].items():
-                p = self._param(k)
-                if len(st) != (5 if self.optimizer == "prodigy" else 3):
-                    raise ValueError(f"{k}: {len(st)} state tensors do not fit optimizer={self.optimizer!r}")
-                self.state[k] = tuple(t.to(p.device) for t in st)
-                p.data.copy_(self.state[k][0])
-            if self.optimizer == "prodigy":
-                self.pstate = None if sd["scalars"] is None else sd["scalars"].to(self.model.device)
+        self._optim.load_state_dict(inner)
         self._lora_remerge()
         self.bw.refresh()
         self.model._packed = None

@@ -36,40 +36,12 @@ Unmeasured on hardware so far: no multi-GPU node was available to the builder (D
 import torch
 import torch.distributed as dist
 
+from .optim import PRODIGY_DEFAULTS, PRODIGY_SLOTS, optimizer_pass, resolve_optimizer  # noqa: F401  (re-exported)
+
 __all__ = ["FlatLayout", "ShardedAdamW", "backward_order", "resolve_optimizer"]
 
 ALIGN = 64                      # elements: every chunk starts on a 256-byte (fp32) boundary
 DEFAULT_BUCKET = 540_000_000    # zero2.json: reduce_bucket_size 5.4e8
-
-
-PRODIGY_SLOTS = ("d", "d_max", "d_numerator", "d_denom", "d_hat", "dlr", "k", "skipped", "sum_dot", "sum_abs")   # include/fk.h
-PRODIGY_DEFAULTS = dict(beta3=None, d0=1e-6, d_coef=1.0, growth_rate=float("inf"), use_bias_correction=True,
-                        safeguard_warmup=True, decouple=True)     # the reference config's (configuration_denoise.py:49-55)
-
-
-def resolve_optimizer(optimizer, lr, prodigy):
-    """(optimizer, lr, Prodigy hyper-parameters or None) after the defaults and refusals of the training seam
-    (train_denoiser.py:595-624): ``lr=None`` is 1e-6 for AdamW and 1.0 for Prodigy, Prodigy wants ``lr`` around 1."""
-    if optimizer not in ("adamw", "prodigy"):
-        raise ValueError(f"optimizer must be 'adamw' or 'prodigy', got {optimizer!r}")
-    if optimizer == "adamw":
-        if prodigy is not None:
-            raise ValueError("prodigy= holds Prodigy's hyper-parameters; the optimiser is 'adamw'")
-        return optimizer, (1e-6 if lr is None else lr), None
-    lr = 1.0 if lr is None else lr
-    if lr <= 0.1:
-        raise ValueError(f"optimizer='prodigy' estimates the step size itself and wants lr around 1.0; lr = {lr} (<= 0.1) would "
-                         "scale that estimate down")
-    hp = dict(PRODIGY_DEFAULTS)
-    unknown = sorted(set(prodigy or {}) - set(hp))
-    if unknown:
-        raise ValueError("prodigy=: unknown keys " + ", ".join(unknown) + "; known: " + ", ".join(sorted(hp)))
-    hp.update(prodigy or {})
-    if not hp["d0"] > 0 or not hp["d_coef"] > 0 or not hp["growth_rate"] > 1.0:
-        raise ValueError("prodigy=: d0 and d_coef must be positive and growth_rate above 1")
-    if hp["beta3"] is not None and not 0.0 <= hp["beta3"] < 1.0:
-        raise ValueError("prodigy=: beta3 must lie in [0, 1)")
-    return optimizer, lr, hp
 
 
 def backward_order(names):
@@ -234,9 +206,7 @@ class ShardedAdamW:
         flat = self.flat_param.double()
         mine = torch.stack([flat.sum(), flat.pow(2).sum()])
         both = torch.cat([mine, -mine])
-        if self._host_staged:                             # gloo cannot exchange device tensors
-            both = both.cpu()
-        dist.all_reduce(both, op=dist.ReduceOp.MAX, group=self.group)
+        self._all_reduce(both, "MAX")
         hi, lo = both[:2].tolist(), (-both[2:]).tolist()
         if not (hi[0] == lo[0] and hi[1] == lo[1]):
             raise ValueError(f"the ranks start from different parameters (checksums over the ranks: sum in [{lo[0]!r}, {hi[0]!r}], "
@@ -273,8 +243,7 @@ class ShardedAdamW:
         if handle is not None:
             handle.wait()
         if tmp is not None:
-            bk = self.layout.buckets[b]
-            self.grad_slice[bk["state_offset"]: bk["state_offset"] + bk["chunk"]].add_(tmp[: bk["chunk"]])
+            self._chunk(self.grad_slice, b).add_(tmp[: self.layout.buckets[b]["chunk"]])
 
     def _flush(self):
         for b in range(len(self.layout.buckets)):        # buckets with tensors that received no gradient this pass (zeros)
@@ -287,8 +256,7 @@ class ShardedAdamW:
     def _stage_for(self, b):
         """Staging buffer of bucket b (waits for the reduction of the bucket that used it before)."""
         if self.direct:
-            bk = self.layout.buckets[b]
-            return self.grad_slice[bk["state_offset"]: bk["state_offset"] + bk["chunk"]]
+            return self._chunk(self.grad_slice, b)
         slot = b % len(self.staging)
         owner = self._stage_owner[slot]
         if owner != b:
@@ -314,21 +282,14 @@ class ShardedAdamW:
         """Take a block's gradients (dict name -> bf16 / fp32 tensor; a cast, no arithmetic) and start the reduction of
         every bucket they complete."""
         L = self.layout
+        adding = bool(self.direct and self._micro)            # accumulating pass on one rank: straight into the chunk
         for n in sorted((n for n in grads if n in L.offsets), key=lambda n: L.offsets[n][0]):
-            b = L.bucket_of[n]
-            if self._launched[b]:
-                raise RuntimeError(f"gradient of {n} arrived after its bucket was reduced: a second backward pass before "
-                                   "step() must be announced with begin_micro_batch() (gradient accumulation), and within a "
-                                   "pass a tensor's gradient may arrive only once per bucket flush")
-            if self.direct and self._micro:                   # accumulating pass on one rank: straight into the chunk
-                if n in self._seen[b]:
-                    raise RuntimeError(f"gradient of {n} arrived twice in one accumulating pass")
+            b = self._writable(n, tensor=True)
+            if adding:
                 self.grad_view(n).add_(grads[n])
             else:
                 self.grad_view(n).copy_(grads[n])
-            self._seen[b].add(n)
-            if len(self._seen[b]) == len(L.buckets[b]["names"]):
-                self._reduce(b)
+            self._mark_seen(b, n)
 
     def grad_target(self, name):
         """(fp32 view, accumulate) for a kernel that WRITES the gradient of ``name`` in place instead of handing a finished tensor
@@ -344,26 +305,30 @@ class ShardedAdamW:
     def written(self, names):
         """The gradients of ``names`` have been written (enqueued on the current stream) into their ``grad_target`` views: mark
         them seen and start the reduction of every bucket they complete, exactly as ``accumulate()`` does after its copies."""
-        L = self.layout
-        for n in sorted(names, key=lambda n: L.offsets[n][0]):
-            b = self._writable(n)
-            self._seen[b].add(n)
-            if len(self._seen[b]) == len(L.buckets[b]["names"]):
-                self._reduce(b)
+        for n in sorted(names, key=lambda n: self.layout.offsets[n][0]):
+            self._mark_seen(self._writable(n), n)
 
-    def _writable(self, name):
+    def _writable(self, name, tensor=False):
+        """The arrival check; returns the bucket.  ``tensor``: a finished tensor handed to ``accumulate()``, which a pass that
+        overwrites may hand in again before the bucket is reduced; a kernel's in-place write may come once per pass."""
         b = self.layout.bucket_of[name]
         if self._launched[b]:
             raise RuntimeError(f"gradient of {name} arrived after its bucket was reduced: a second backward pass before step() must "
-                               "be announced with begin_micro_batch() (gradient accumulation)")
-        if name in self._seen[b]:
-            raise RuntimeError(f"gradient of {name} arrived twice in one pass")
+                               "be announced with begin_micro_batch() (gradient accumulation)"
+                               + (", and within a pass a tensor's gradient may arrive only once per bucket flush" if tensor else ""))
+        if name in self._seen[b] and (not tensor or (self.direct and self._micro)):
+            raise RuntimeError(f"gradient of {name} arrived twice in one " + ("accumulating pass" if tensor else "pass"))
         return b
+
+    def _mark_seen(self, b, name):
+        self._seen[b].add(name)
+        if len(self._seen[b]) == len(self.layout.buckets[b]["names"]):
+            self._reduce(b)
 
     def _reduce(self, b):
         bk = self.layout.buckets[b]
         stage = self._stage_for(b)[: bk["size"]]
-        dst = self.grad_slice[bk["state_offset"]: bk["state_offset"] + bk["chunk"]]
+        dst = self._chunk(self.grad_slice, b)
         if self.world > 1:
             tmp = None
             if self._micro:                                   # accumulating pass: reduce into a temporary, add on completion
@@ -404,6 +369,26 @@ class ShardedAdamW:
         dist.all_gather_into_tensor(h_out, mine.cpu(), group=self.group)
         out.copy_(h_out)
         return _Done()
+
+    def _all_reduce(self, t, op):
+        """In-place all-reduce of ``t`` with ``dist.ReduceOp.<op>``; nothing to do on one rank."""
+        if self.world == 1:
+            return
+        h = t.cpu() if self._host_staged else t
+        dist.all_reduce(h, op=getattr(dist.ReduceOp, op), group=self.group)
+        if h is not t:
+            t.copy_(h)
+
+    def _chunk(self, t, b):
+        """This rank's chunk of bucket b in one of the fp32 state tensors."""
+        bk = self.layout.buckets[b]
+        return t[bk["state_offset"]: bk["state_offset"] + bk["chunk"]]
+
+    def _gather(self, works, b):
+        """Start the all-gather of bucket b, IN PLACE: the send buffer is the rank's chunk of the bucket being gathered."""
+        if self.world > 1:
+            L = self.layout
+            works.append(self._all_gather(L.bucket_view(self.flat_param, b), L.chunk_of(self.flat_param, b, self.rank)))
 
     # ---- compatibility: whole-gradient views (tests, small models) ------------------------------------------------------
     @property
@@ -481,13 +466,10 @@ class ShardedAdamW:
                 raise ValueError("scalars: not a Prodigy state buffer")
             self.prodigy = dict(sd["prodigy"])
             self.pstate.copy_(sd["scalars"])
-        L = self.layout
         works = []
-        for b, bk in enumerate(L.buckets):
-            mine = L.chunk_of(self.flat_param, b, self.rank)
-            mine.copy_(self.master[bk["state_offset"]: bk["state_offset"] + bk["chunk"]])      # fp32 -> bf16, round to nearest even
-            if self.world > 1:
-                works.append(self._all_gather(L.bucket_view(self.flat_param, b), mine))
+        for b in range(len(self.layout.buckets)):
+            self.layout.chunk_of(self.flat_param, b, self.rank).copy_(self._chunk(self.master, b))   # fp32 -> bf16, round to nearest even
+            self._gather(works, b)
         for w in works:
             w.wait()
 
@@ -519,64 +501,23 @@ class ShardedAdamW:
         L = self.layout
         self._flush()
         sumsq = self.k.sumsq(self.grad_slice)            # fp64 [1] over the SUMS; padding elements are zero
-        if self.world > 1:
-            if self._host_staged:
-                h = sumsq.cpu()
-                dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
-                sumsq.copy_(h)
-            else:
-                dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self.group)
+        self._all_reduce(sumsq, "SUM")
         scale = 1.0 / self.world                          # mean over the data-parallel ranks, like DDP / DeepSpeed
         if self.average_micro_batches:
             scale /= self._micro + 1                      # ... and over the accumulated micro-batches (accelerate)
         self.last_grad_norm = sumsq.sqrt() * scale
         self.step_count += 1
+        # one segment per bucket: this rank's chunk (padding elements have a zero gradient, zero ``s`` and ``p0 == p``: they add
+        # nothing to Prodigy's sums).  The 1 / world of the MEAN rides in `scale`; each bucket's all-gather starts at its write
+
+        def segments():
+            state = (self.master, self.grad_slice, self.exp_avg, self.exp_avg_sq, self.s, self.p0)      # s, p0: None for AdamW
+            for b in range(len(L.buckets)):
+                yield (*(t if t is None else self._chunk(t, b) for t in state), L.chunk_of(self.flat_param, b, self.rank))
         works = []
-        if self.optimizer == "prodigy":
-            self._prodigy_moments_and_d(sumsq, scale)
-        for b, bk in enumerate(L.buckets):
-            so, ch = bk["state_offset"], bk["chunk"]
-            mine = L.chunk_of(self.flat_param, b, self.rank)
-            if self.optimizer == "prodigy":
-                self.k.prodigy_apply(self.master[so:so + ch], self.exp_avg[so:so + ch], self.exp_avg_sq[so:so + ch], self.pstate,
-                                     eps=self.hp["eps"], weight_decay=self.hp["weight_decay"], decouple=self.prodigy["decouple"],
-                                     param_bf16=mine)
-                if self.world > 1:
-                    works.append(self._all_gather(L.bucket_view(self.flat_param, b), mine))
-                continue
-            self.k.adamw_step(self.master[so:so + ch], self.grad_slice[so:so + ch], self.exp_avg[so:so + ch],
-                              self.exp_avg_sq[so:so + ch], self.step_count,
-                              grad_sumsq=sumsq if self.max_grad_norm is not None else None,
-                              max_grad_norm=self.max_grad_norm if self.max_grad_norm is not None else 0.0,
-                              param_bf16=mine, grad_scale=scale, **self.hp)
-            if self.world > 1:   # in place: `mine` IS the rank's chunk of the bucket being gathered
-                works.append(self._all_gather(L.bucket_view(self.flat_param, b), mine))
+        optimizer_pass(self.k, segments, self.step_count, self.hp, self.prodigy, self.pstate, self._pws, sumsq, self.max_grad_norm,
+                       scale, reduce_sums=lambda sums: self._all_reduce(sums, "SUM"), after_write=lambda b: self._gather(works, b))
         for w in works:
             w.wait()
         self._begin()
         return self.last_grad_norm
-
-    def _prodigy_moments_and_d(self, sumsq, scale):
-        """The first pass of a Prodigy step and the scalar update between the passes: the two running sums of this rank's chunks
-        (padding elements have a zero gradient, zero ``s`` and ``p0 == p``: they add nothing) are summed over the ranks as ONE
-        2-double all-reduce, so every rank computes the same ``d``."""
-        hp, pr = self.hp, self.prodigy
-        self.k.prodigy_begin(self.pstate, hp["lr"], hp["betas"], pr["beta3"], pr["use_bias_correction"])
-        for bk in self.layout.buckets:
-            so, ch = bk["state_offset"], bk["chunk"]
-            self.k.prodigy_moments(self.master[so:so + ch], self.p0[so:so + ch], self.grad_slice[so:so + ch],
-                                   self.exp_avg[so:so + ch], self.exp_avg_sq[so:so + ch], self.s[so:so + ch], self.pstate,
-                                   betas=hp["betas"], beta3=pr["beta3"], weight_decay=hp["weight_decay"], d0=pr["d0"],
-                                   decouple=pr["decouple"], safeguard_warmup=pr["safeguard_warmup"],
-                                   grad_sumsq=sumsq if self.max_grad_norm is not None else None,
-                                   max_grad_norm=self.max_grad_norm if self.max_grad_norm is not None else 0.0,
-                                   grad_scale=scale, ws=self._pws)
-        if self.world > 1:
-            sums = self.pstate[PRODIGY_SLOTS.index("sum_dot"): PRODIGY_SLOTS.index("sum_abs") + 1]
-            if self._host_staged:
-                h = sums.cpu()
-                dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
-                sums.copy_(h)
-            else:
-                dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
-        self.k.prodigy_update_d(self.pstate, pr["d0"], pr["d_coef"], pr["growth_rate"])

@@ -5,9 +5,9 @@
 The cfg 5 trainable set (``training.trainable_names`` over the full-size denoiser's shapes: 4.04 B parameters) as bf16 tensors with
 random bf16 gradients -- no model, no forward or backward.  Four phases, each with its own tensors, freed before the next:
 
-  per-tensor   ``DenoiserTrainStep.optimizer_step`` (``fk_sumsq`` + ``fk_adamw_step`` per tensor | ``fk_sumsq``, ``fk_prodigy_begin``,
-               ``fk_prodigy_moments`` per tensor, ``fk_prodigy_update_d``, ``fk_prodigy_apply`` per tensor) on a step object whose
-               model is a bare holder of those parameters (the method touches nothing else of a model);
+  per-tensor   ``optim.PerTensorState.step``, the optimiser of ``DenoiserTrainStep.optimizer_step`` (``fk_sumsq`` + ``fk_adamw_step`` per
+               tensor | ``fk_sumsq``, ``fk_prodigy_begin``, ``fk_prodigy_moments`` per tensor, ``fk_prodigy_update_d``, ``fk_prodigy_apply``
+               per tensor) around the bare parameters;
   sharded      ``zero.ShardedAdamW(...).step()`` at world 1; the cast of the gradients into its fp32 chunks (``accumulate``) is
                outside the bracket, as it runs during the backward pass.
 
@@ -21,7 +21,6 @@ import json
 import os
 import statistics
 import sys
-from types import SimpleNamespace
 
 import torch
 
@@ -60,17 +59,10 @@ def bracket(fn, before, steps, warmup):
 
 
 def per_tensor(optimizer, params, grads):
-    """A ``DenoiserTrainStep`` around bare parameters: ``optimizer_step`` reads ``_param``, the hyper-parameters and the state only."""
-    from gpt_image_edit_amd.train_step import DenoiserTrainStep
-    from gpt_image_edit_amd.zero import resolve_optimizer
-    ts = DenoiserTrainStep.__new__(DenoiserTrainStep)
-    ts.model = SimpleNamespace(p=lambda name: params[name], device=next(iter(params.values())).device)
-    ts.projector = ts.lora = ts.opt = ts.pstate = ts._pws = None
-    ts.optimizer, ts.lr, ts.prodigy = resolve_optimizer(optimizer, None, None)
-    ts.betas, ts.eps, ts.weight_decay, ts.max_grad_norm = (0.9, 0.99), 1e-8, 0.01, 1.0
-    ts.state, ts._sunk, ts.step_count = {}, {}, 0
-    ts.bw = SimpleNamespace(refresh=lambda: None, trainable=set(params))
-    return (lambda: ts.optimizer_step(grads)), (lambda: None), ts
+    """The unsharded optimiser of ``DenoiserTrainStep`` around bare parameters."""
+    from gpt_image_edit_amd.optim import PerTensorState
+    st = PerTensorState(params.__getitem__, optimizer, weight_decay=0.01)
+    return (lambda: st.step(grads)), (lambda: None), st
 
 
 def sharded(optimizer, params, grads):
