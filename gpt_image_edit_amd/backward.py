@@ -87,13 +87,44 @@ def wgrad(buf, dy, x, out=None):
 class FluxBackward:
     """Training forward / backward around a ``HipFluxTransformer2DModel`` (which keeps owning the parameters)."""
 
-    def __init__(self, model, trainable=None, store_activations="auto", activation_budget_bytes=96 << 30, lora=None):
+    # Side targets (``side=``): the linears whose adapter gradient the factored LoRA backward takes from the linear's own
+    # backward operands (dY, X) through ``side_sink`` instead of a weight gradient -- leaf -> (dY, X).  The per-launch route calls
+    # the sink where the wgrad GEMM would have run; the block entry points (csrc/blocks_bwd.hip, which skip a wgrad whose output
+    # pointer is null) call it after the block, on buffers that still hold the operands then:
+    #   double block   attn.to_q / to_k / to_v              column block k of dqkv, image rows | n1, image rows
+    #                  attn.add_q_proj / add_k_proj / add_v_proj   the same on the text rows
+    #                  attn.to_out.0 / attn.to_add_out      dy as its SECOND use leaves it (the gate_res_bwd of the attention
+    #                                                       projection), image / text rows | the kept attention output o
+    #                  ff.net.0.proj / ff_context.net.0.proj   dff after gelu_bwd (nothing writes it afterwards) | n2
+    #   single block   attn.to_q / to_k / to_v              column block k of dqkv | n1
+    #                  proj_mlp                             dff after gelu_bwd | n1
+    # NOT side targets -- they stay in the wgrad set and are projected from dW as before: ff.net.2 / ff_context.net.2 (their dy
+    # is overwritten by the attention projection's, their X is the shared GELU scratch), the single blocks' proj_out (its X is
+    # the shared ``cat`` scratch; it stays projected rather than rebuilt a second time), and the AdaLN linears (batch-reduced).
+    SIDE_LEAVES = {"transformer_blocks": ("attn.to_q", "attn.to_k", "attn.to_v", "attn.add_q_proj", "attn.add_k_proj",
+                                          "attn.add_v_proj", "attn.to_out.0", "attn.to_add_out", "ff.net.0.proj",
+                                          "ff_context.net.0.proj"),
+                   "single_transformer_blocks": ("attn.to_q", "attn.to_k", "attn.to_v", "proj_mlp")}
+    QKV_GROUPS = (("attn.to_q", "attn.to_k", "attn.to_v"), ("attn.add_q_proj", "attn.add_k_proj", "attn.add_v_proj"))
+
+    @classmethod
+    def side_routable(cls, name):
+        """Can the weight ``name`` be a side target (the table above)?"""
+        kind, _, rest = name.partition(".")
+        idx, _, leaf = rest.partition(".")
+        return idx.isdigit() and leaf.endswith(".weight") and leaf[:-len(".weight")] in cls.SIDE_LEAVES.get(kind, ())
+
+    def __init__(self, model, trainable=None, store_activations="auto", activation_budget_bytes=96 << 30, lora=None, side=None):
         """store_activations: True = keep every block's intermediates from the forward (no recomputation: 37 GB at
         1024^2, bs 1 -- sized for 288 GB of HBM, where the reference's 80 GB GPUs force checkpointing); False = one
         checkpoint per block + recomputation in the backward; "auto" = store when it fits ``activation_budget_bytes``.
         lora: the name of a loaded adapter that is being trained (``train_step.DenoiserTrainStep(lora=...)``) -- permits a model
         with adapters merged into its weights; ``trainable`` then defaults to the WEIGHTS that adapter touches, so only their
-        wgrad GEMMs run and ``backward`` emits the gradient w.r.t. the merged weight.  Without it such a model is refused."""
+        wgrad GEMMs run and ``backward`` emits the gradient w.r.t. the merged weight.  Without it such a model is refused.
+        side: a set (or mapping) of trainable weight names that are SIDE targets (``SIDE_LEAVES``): their wgrad GEMM and ``dW``
+        are skipped and ``backward(side_sink=)`` is called with the two operand views instead.  Names the table does not route
+        stay in the wgrad set.  A q / k / v group is a side group as a whole (its one fused wgrad GEMM runs or does not).  With
+        ``side=None`` nothing changes."""
         from . import training
         self.store_activations, self.activation_budget = store_activations, activation_budget_bytes
         self.m = model
@@ -111,11 +142,70 @@ class FluxBackward:
         if lora is None and getattr(model, "lora_loaded", None) is not None and model.lora_loaded():
             raise RuntimeError("FluxBackward: the model has LoRA adapters merged into its weights; a full-weight step would train "
                                "the merged weights -- unload_lora() first, or train the adapter (DenoiserTrainStep(lora=...))")
+        self._rewritten = set(self.trainable)     # what an optimiser step rewrites: refresh() re-packs all of it
+        self.side = self._take_side(side, None if lora is None else set(model._lora_adapters[lora]))
+        self._side_sink = None
         if not model._train_packs:     # from now on the model fuses nothing an optimiser rewrites (transformer.pack_weights)
             model._train_packs, model._packed = True, None
         self._wT = {}          # name -> (W^T (bf16 [in, out]) for the data gradients, stamp of its source)
         self._buf = {}
         self._saved = None
+
+    def _take_side(self, side, targets):
+        """The side targets among ``side`` (the routable ones), taken out of the wgrad set ``self.trainable``.  ``targets``: the
+        weights whose gradient somebody reads (None: every trainable one) -- with ``lora=`` the q / k / v members that only
+        complete a group are not, and leave the wgrad set together with the group's side members."""
+        if not side:
+            return set()
+        side = set(side)
+        unknown = sorted(side - self.trainable)
+        if unknown:
+            raise ValueError("FluxBackward(side=): not in the trainable set: " + ", ".join(unknown[:4]))
+        side = {k for k in side if self.side_routable(k)}
+        rest = self.trainable - side
+        for k in sorted(side):
+            stem, leaf = k[:-len(".weight")].rsplit(".attn.", 1) if ".attn." in k else (k, "")
+            for group in self.QKV_GROUPS:
+                if "attn." + leaf in group:
+                    others = {f"{stem}.{g}.weight" for g in group} & rest
+                    needed = sorted(o for o in others if targets is None or o in targets)
+                    if needed:
+                        raise ValueError(f"FluxBackward(side=): {k} is a side target but {needed[0]} of the same q / k / v group "
+                                         "needs the fused weight gradient: a group is side or projected as a whole")
+                    rest -= others
+        self.trainable = rest
+        return side
+
+    def _side_emit(self, views, names):
+        """Hand the side targets among ``names`` to the side sink with their (dY, X) views."""
+        for name in names:
+            if name in self.side:
+                dy, x = views[name]
+                self._side_sink(name, dy, x)
+
+    def _double_side_views(self, i, sv, dy, dff, dqkv):
+        """name -> (dY view, X view) of double block ``i``'s side targets (``SIDE_LEAVES``), on the backward's buffers."""
+        D, S_txt = self.m.inner_dim, sv.S_txt
+        p = f"transformer_blocks.{i}."
+        bb = self._block_bufs(sv, i, True)
+        o, n1, n2 = sv.o_ckpt[i], bb.n, bb.n2
+        img, txt = slice(S_txt, None), slice(0, S_txt)
+        v = {p + "attn.to_out.0.weight": (dy[:, img], o[:, img]), p + "attn.to_add_out.weight": (dy[:, txt], o[:, txt]),
+             p + "ff.net.0.proj.weight": (dff[:, img], n2[:, img]), p + "ff_context.net.0.proj.weight": (dff[:, txt], n2[:, txt])}
+        for group, sl in zip(self.QKV_GROUPS, (img, txt)):
+            for k, leaf in enumerate(group):
+                v[p + leaf + ".weight"] = (dqkv[:, sl, k * D:(k + 1) * D], n1[:, sl])
+        return v
+
+    def _single_side_views(self, j, sv, dff, dqkv):
+        """The same for single block ``j``."""
+        D = self.m.inner_dim
+        p = f"single_transformer_blocks.{j}."
+        n1 = self._block_bufs(sv, len(sv.pk.double) + j, False).n
+        v = {p + "proj_mlp.weight": (dff, n1)}
+        for k, leaf in enumerate(self.QKV_GROUPS[0]):
+            v[p + leaf + ".weight"] = (dqkv[:, :, k * D:(k + 1) * D], n1)
+        return v
 
     # ---- transposed weights ------------------------------------------------------------------------------------------
     @staticmethod
@@ -168,9 +258,9 @@ class FluxBackward:
         which torch's version counters do not see): invalidate the transposes of the trainable weights and the model's
         fused copies.  Updates made by torch itself (a stock optimiser, an all-gather) are caught by the stamps."""
         for k, (t, _) in list(self._wT.items()):
-            if k in self.trainable or k.startswith("packed:"):
+            if k in self._rewritten or k.startswith("packed:"):
                 self._wT[k] = (t, None)
-        self.m.repack(self.trainable)
+        self.m.repack(self._rewritten)
 
     # ---- buffers ---------------------------------------------------------------------------------------------------
     def _b(self, name, shape, dtype=BF16, zero=False):
@@ -321,15 +411,20 @@ class FluxBackward:
 
     # ---- backward ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def backward(self, dsample, sink=None, keep=True):
+    def backward(self, dsample, sink=None, keep=True, side_sink=None):
         """dsample: gradient of the loss w.r.t. the forward's output [B, S_img, 64] (bf16).
         Returns (grads: dict name -> tensor, d_encoder_hidden_states [B, S_txt, joint_dim] bf16).
         ``sink``: called with every block's trainable gradients as soon as that block's backward has been enqueued
         (``zero.ShardedAdamW.accumulate``: the bucket's reduce-scatter then overlaps the earlier blocks' backward);
-        ``keep=False`` drops them from the returned dict afterwards (they live on in the sink)."""
+        ``keep=False`` drops them from the returned dict afterwards (they live on in the sink).
+        ``side_sink(pname, dy_view, x_view)``: called once per side target (``FluxBackward(side=)``) with the [B, R, N] / [B, R, K]
+        operand views of its linear, valid only during the call's enqueue order (the next block overwrites them)."""
         sv = self._saved
         if sv is None:
             raise RuntimeError("FluxBackward.backward() needs the forward() of the same step first")
+        if self.side and side_sink is None:
+            raise RuntimeError("FluxBackward.backward(): this backward has side targets (side=) and needs side_sink=")
+        self._side_sink = side_sink
         self.__dict__["_mod_ready"] = None
         m, P, ws, pk = self.m, self.m.p, sv.ws, sv.pk
         D, S_txt, B, S = m.inner_dim, sv.S_txt, sv.B, sv.S
@@ -374,6 +469,7 @@ class FluxBackward:
             emit(bg)
         d_enc = ops.gemm(g[:, :S_txt], **self.dW("context_embedder.weight"))
         self._saved = None
+        self._side_sink = None
         return grads, d_enc
 
     def _double_backward(self, i, sv, g, grads):
@@ -408,6 +504,8 @@ class FluxBackward:
             if p + f"{ff}.net.0.proj.weight" in T:
                 grads[p + f"{ff}.net.0.proj.weight"] = self._wgrad(dff[:, sl], n2[:, sl])
                 grads[p + f"{ff}.net.0.proj.bias"] = ops.colsum(dff[:, sl])
+        side = self._double_side_views(i, sv, dy, dff, self._b("dqkv", (B, S, 3 * D))) if self.side else {}
+        self._side_emit(side, (p + "ff.net.0.proj.weight", p + "ff_context.net.0.proj.weight"))
         ops.gemm_grouped([dict(a=dff[:, img], out=dn[:, img], **self.dW(p + "ff.net.0.proj.weight")),
                           dict(a=dff[:, txt], out=dn[:, txt], **self.dW(p + "ff_context.net.0.proj.weight"))])
         ops.ln_modulate_bwd(x1[:, img], dn[:, img], ch(mi, 4), g[:, img], dm_i[:, 3 * D:5 * D], dx_in=g[:, img])
@@ -425,6 +523,7 @@ class FluxBackward:
         if p + "attn.to_add_out.weight" in self.trainable:
             grads[p + "attn.to_add_out.weight"] = self._wgrad(dy[:, txt], o[:, txt])
             grads[p + "attn.to_add_out.bias"] = ops.colsum(dy[:, txt])
+        self._side_emit(side, (p + "attn.to_out.0.weight", p + "attn.to_add_out.weight"))
         # -- joint attention
         dqkv = self._b("dqkv", (B, S, 3 * D))
         dq, dk = self._b("dq", (B, H, S, 128)), self._b("dk", (B, H, S, 128))
@@ -449,6 +548,7 @@ class FluxBackward:
             for k, nm in enumerate(("add_q_proj", "add_k_proj", "add_v_proj")):
                 grads[p + f"attn.{nm}.weight"] = dwqkv[k * D:(k + 1) * D]
                 grads[p + f"attn.{nm}.bias"] = dbqkv[k * D:(k + 1) * D]
+        self._side_emit(side, [p + leaf + ".weight" for group in self.QKV_GROUPS for leaf in group])
         ops.ln_modulate_bwd(x0[:, img], dn[:, img], ch(mi, 1), g[:, img], dm_i[:, 0:2 * D], dx_in=g[:, img])
         ops.ln_modulate_bwd(x0[:, txt], dn[:, txt], ch(mt, 1), g[:, txt], dm_t[:, 0:2 * D], dx_in=g[:, txt])
         if p + "norm1.linear.weight" in self.trainable:
@@ -557,6 +657,9 @@ class FluxBackward:
             grads[p + "proj_out.weight"], grads[p + "proj_out.bias"] = out["dw_out"], out["db_out"]
         if "dw_mod" in out:
             grads[p + "norm.linear.weight"], grads[p + "norm.linear.bias"] = out["dw_mod"], out["db_mod"][:, 0]
+        if self.side:      # after the block: dqkv, dff and n1 still hold this block's operands (SIDE_LEAVES)
+            side = self._single_side_views(j, sv, cb.bufs["dff"], cb.bufs["dqkv"])
+            self._side_emit(side, [p + leaf + ".weight" for leaf in self.QKV_GROUPS[0]] + [p + "proj_mlp.weight"])
 
     # struct field stem of fk_double_block_grads -> (parameter stem, weight shape as a function of D)
     _DOUBLE_PAIRS = {
@@ -610,6 +713,10 @@ class FluxBackward:
             grads[p + "norm1.linear.weight"], grads[p + "norm1.linear.bias"] = out["dw_mod_img"], out["db_mod_img"][:, 0]
         if "dw_mod_txt" in out:
             grads[p + "norm1_context.linear.weight"], grads[p + "norm1_context.linear.bias"] = out["dw_mod_txt"], out["db_mod_txt"][:, 0]
+        if self.side:      # after the block, in the per-launch route's order: dff, the second dy, dqkv still hold the operands
+            side = self._double_side_views(i, sv, cb.bufs["dy"], cb.bufs["dff"], cb.bufs["dqkv"])
+            self._side_emit(side, [p + "ff.net.0.proj.weight", p + "ff_context.net.0.proj.weight", p + "attn.to_out.0.weight",
+                                   p + "attn.to_add_out.weight"] + [p + leaf + ".weight" for group in self.QKV_GROUPS for leaf in group])
 
     def _single_backward(self, j, sv, g, grads):
         m, P, ws, pk = self.m, self.m.p, sv.ws, sv.pk
@@ -648,6 +755,9 @@ class FluxBackward:
         if p + "proj_mlp.weight" in self.trainable:
             grads[p + "proj_mlp.weight"] = self._wgrad(dff, n1)
             grads[p + "proj_mlp.bias"] = ops.colsum(dff)
+        if self.side:
+            side = self._single_side_views(j, sv, dff, dqkv)
+            self._side_emit(side, [p + leaf + ".weight" for leaf in self.QKV_GROUPS[0]] + [p + "proj_mlp.weight"])
         if p + "proj_out.weight" in self.trainable:
             if sv.store:   # cat is shared scratch: rebuild [attn | gelu(mlp)] of this block
                 ws.cat[:, :, :D].copy_(o)

@@ -913,6 +913,69 @@ def lora_grad(dw, up, down, scale, d_up=None, d_down=None, ws=None, accumulate=F
     return d_up, d_down
 
 
+# ---- factored LoRA gradient (include/fk.h: fk_lora_side_grad_bf16) -------------------------------------------------------
+def _side_view(t, what):
+    """(B, R, cols, row stride, batch stride) of a 2-D [R, cols] or 3-D [B, R, cols] bf16 view with a contiguous last dimension."""
+    if t.dim() not in (2, 3) or t.stride(-1) != 1 or t.dtype != BF16:
+        raise ValueError(f"lora_side_grad takes {what} as a 2-D or 3-D bf16 view with a contiguous last dimension, got "
+                         f"{tuple(t.shape)} {t.dtype} strides {t.stride()}")
+    if t.dim() == 2:
+        return 1, t.shape[0], t.shape[1], t.stride(0), 0
+    return t.shape[0], t.shape[1], t.shape[2], t.stride(1), t.stride(0)
+
+
+def lora_side_grad_ws_floats(B, R, N, K, rank):
+    """fp32 elements of :func:`lora_side_grad`'s workspace."""
+    return libfk.load().fk_lora_side_grad_ws_floats(B, R, N, K, rank)
+
+
+def lora_side_grad_ws(B, R, N, K, rank, device):
+    """The workspace of :func:`lora_side_grad` for ``B * R`` rows of a linear [N, K] at ``rank`` (fp32 elements: the split-bf16
+    intermediates and the partials of the split reduction): one per stream of ordered launches."""
+    return torch.empty(lora_side_grad_ws_floats(B, R, N, K, rank), device=device, dtype=torch.float32)
+
+
+def lora_side_grad(x, dy, up, down, scale, d_up=None, d_down=None, ws=None, accumulate=False):
+    """(d_up [N, r], d_down [r, K]) in fp32 for a linear ``y = x W^T`` whose weight was merged as ``base + scale * up @ down``:
+    ``scale * dy^T (x down^T)`` and ``scale * (dy up)^T x``, from the linear's own backward operands ``x`` [B, R, K] and ``dy``
+    [B, R, N] -- the weight gradient ``dy^T x`` is never formed (fp32 accumulation, split-bf16 intermediates, fixed summation order:
+    two calls give the same bits).  ``x`` / ``dy``: bf16 views with a contiguous last dimension and any row and batch stride (2-D
+    means B = 1); ``up`` [N, r], ``down`` [r, K]: 2-D bf16 views with a contiguous last dimension; the outputs contiguous fp32
+    (views at any 4-byte offset of a larger buffer will do).  ``ws``: :func:`lora_side_grad_ws` (allocated per call when None --
+    the hot path owns one).  ``accumulate=True``: the result is ADDED to what ``d_up`` / ``d_down`` hold."""
+    if accumulate and (d_up is None or d_down is None):
+        raise ValueError("lora_side_grad(accumulate=True) adds to d_up / d_down: pass both")
+    _need_cuda(x, dy, up, down)
+    B, R, K, ld_x, bs_x = _side_view(x, "x")
+    B2, R2, N, ld_dy, bs_dy = _side_view(dy, "dy")
+    if (B, R) != (B2, R2):
+        raise ValueError(f"x {tuple(x.shape)} and dy {tuple(dy.shape)} do not have the same rows")
+    for t in (up, down):
+        if t.dim() != 2 or t.stride(-1) != 1 or t.dtype != BF16:
+            raise ValueError(f"lora_side_grad takes up / down as 2-D bf16 views with a contiguous last dimension, got "
+                             f"{tuple(t.shape)} {t.dtype} strides {t.stride()}")
+    r = up.shape[1]
+    if up.shape[0] != N or down.shape[1] != K or down.shape[0] != r:
+        raise ValueError(f"up {tuple(up.shape)} / down {tuple(down.shape)} do not fit the linear [{N}, {K}]")
+    if d_up is None:
+        d_up = torch.empty(N, r, device=x.device, dtype=torch.float32)
+    if d_down is None:
+        d_down = torch.empty(r, K, device=x.device, dtype=torch.float32)
+    if ws is None:
+        ws = lora_side_grad_ws(B, R, N, K, r, x.device)
+    _need_cuda(d_up, d_down, ws)
+    for t, shape in ((d_up, (N, r)), (d_down, (r, K))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"lora_side_grad writes contiguous fp32 {shape}, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+    if ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError("ws must be a contiguous fp32 workspace")
+    libfk.check(libfk.load().fk_lora_side_grad_bf16(_ptr(x), ld_x, bs_x, _ptr(dy), ld_dy, bs_dy, B, R, N, K, _ptr(up), up.stride(0),
+                                                    _ptr(down), down.stride(0), r, float(scale), _ptr(d_up), _ptr(d_down),
+                                                    int(accumulate), _ptr(ws) if ws.numel() else None, ws.numel(), _stream()),
+                "fk_lora_side_grad_bf16")
+    return d_up, d_down
+
+
 def transpose(src, dst):
     """dst[b, c, r] = src[b, r, c] for 3-D views with contiguous last dims."""
     _need_cuda(src, dst)

@@ -30,6 +30,9 @@ forward and backward on the merged weights, each target weight's ``dW`` projecte
 optimiser state is 12 bytes per ADAPTER parameter and only one block's ``dW`` is alive at a time.  With ``data_parallel=True`` as well
 the factors live in a ``zero.ShardedAdamW``: every ``dW`` is projected straight into the optimiser's fp32 gradient views
 (``fk_lora_grad_acc_bf16``, which can add to what is there), so the adapter has micro-batch accumulation and the data-parallel exchange.
+With ``lora_backward="factored"`` the adapter gradient of every linear whose backward operands survive (``FluxBackward.SIDE_LEAVES``)
+is taken from those operands, ``d_up = s dY^T (X down^T)``, ``d_down = s (dY up)^T X`` (``fk_lora_side_grad_bf16``): its wgrad GEMM and
+its ``dW`` do not exist, and the gradient does not pass through ``dW``'s bf16 rounding.  The other targets stay projected.
 
 With ``optimizer="prodigy"`` the optimiser pass is Prodigy instead of AdamW (the reference's ``optimizer: 'prodigy'``,
 ``train_denoiser.py:603-624``; ``csrc/prodigy.hip``): ``fk_sumsq``, ``fk_prodigy_begin``, ``fk_prodigy_moments`` over the sorted names,
@@ -49,7 +52,7 @@ BF16 = torch.bfloat16
 class DenoiserTrainStep:
     def __init__(self, model, lr=None, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, trainable=None,
                  sharded=False, group=None, store_activations="auto", projector=None, keep_grads=True, bucket_numel=None,
-                 lora=None, optimizer="adamw", prodigy=None, data_parallel=False):
+                 lora=None, optimizer="adamw", prodigy=None, data_parallel=False, lora_backward="projected"):
         """sharded=True: the optimiser state lives in ``zero.ShardedAdamW`` (ZeRO-2: one flat bf16 parameter buffer the
         model's trainable tensors become views of, fp32 gradients reduce-scattered over the data-parallel ranks, this
         rank's slice of master + moments updated, parameters all-gathered); works unchanged with one process.
@@ -70,7 +73,18 @@ class DenoiserTrainStep:
         size ``d`` on the fly (``csrc/prodigy.hip``; two more fp32 state tensors, ``s`` and the initial point ``p0``);
         ``prodigy=dict(beta3=, d0=, d_coef=, growth_rate=, use_bias_correction=, safeguard_warmup=, decouple=)`` overrides its
         defaults (the reference config's: the three flags True).  ``lr=None`` is 1e-6 for AdamW and 1.0 for Prodigy; Prodigy
-        with ``lr <= 0.1`` is refused as the reference refuses it (:609-612)."""
+        with ``lr <= 0.1`` is refused as the reference refuses it (:609-612).
+        lora_backward="projected" | "factored" (with ``lora=``): "projected" is the step above, launch for launch.  "factored": every
+        target of the adapter that ``FluxBackward.side_routable`` leaves the wgrad set; the backward hands its two operand views to a
+        side sink that asks the optimiser for the same two fp32 targets as the projection does (``grad_target``, then ``written``)
+        and makes one ``ops.lora_side_grad`` call -- so ``data_parallel=True``, ``optimizer="prodigy"``, ``projector=``, frozen
+        second adapters, ``discard()`` and save / resume work as before.  The optimiser state is the same in both modes and
+        ``state_dict()`` does not record the mode: a state saved in one loads in the other."""
+        if lora_backward not in ("projected", "factored"):
+            raise ValueError(f"DenoiserTrainStep: lora_backward={lora_backward!r}, it is \"projected\" or \"factored\"")
+        if lora_backward == "factored" and lora is None:
+            raise ValueError("DenoiserTrainStep: lora_backward=\"factored\" is the adapter's backward and needs lora=")
+        self.lora_backward = lora_backward
         # the unsharded optimiser (its refusals come before the model is touched); unused once `opt` below is set
         self.local = PerTensorState(self._param, optimizer, lr, betas, eps, weight_decay, max_grad_norm, prodigy)
         self.optimizer, self.lr, self.prodigy = self.local.optimizer, self.local.hp["lr"], self.local.prodigy
@@ -93,7 +107,11 @@ class DenoiserTrainStep:
             model.set_lora_scale(1.0)          # the scale of the projection is the one the weights were merged with
             self._lora_entries = model._lora_adapters[lora]
             self._lora_ws = None
-        self.bw = FluxBackward(model, trainable, store_activations=store_activations, lora=lora)
+            self._side_ws = None
+        side = None
+        if lora_backward == "factored":
+            side = {k for k in self._lora_entries if FluxBackward.side_routable(k)}
+        self.bw = FluxBackward(model, trainable, store_activations=store_activations, lora=lora, side=side)
         self.betas, self.eps, self.weight_decay, self.max_grad_norm = betas, eps, weight_decay, max_grad_norm
         self.opt = None     # the zero.ShardedAdamW of sharded=True / data_parallel=True
         self.keep_grads = keep_grads
@@ -164,8 +182,7 @@ class DenoiserTrainStep:
         """The sink of ``FluxBackward.backward`` under ``lora=``: every emitted ``dW`` of a target weight is projected onto its two
         factors (one ``fk_lora_grad_bf16`` / ``fk_lora_grad_acc_bf16`` call) into the optimiser's two fp32 targets -- persistent buffers
         of ``PerTensorState``, the gradient views of ``ShardedAdamW`` (no buffer of this step's, no copy); ``out`` collects them by name."""
-        scales = {p: next(s for a, s, _ in ts if a == self.lora) for p, ts in self.model._lora_wanted().items()
-                  if any(a == self.lora for a, _, _ in ts)}
+        scales = self._lora_scales()
         if self._lora_ws is None:
             dev = self.model.device
             need = max(ops.lora_grad_ws(e.up.shape[0], e.down.shape[1], e.rank, dev).numel() for e in self._lora_entries.values())
@@ -183,6 +200,33 @@ class DenoiserTrainStep:
                 optim.written([up, down])
                 out[up], out[down] = d_up, d_down
         return sink
+
+    def _lora_scales(self):
+        """target weight -> the scale the trained adapter was merged with."""
+        return {p: next(s for a, s, _ in ts if a == self.lora) for p, ts in self.model._lora_wanted().items()
+                if any(a == self.lora for a, _, _ in ts)}
+
+    def _lora_side_sink(self, out):
+        """The side sink of ``FluxBackward.backward`` under ``lora_backward="factored"``: the two operand views of a side target's
+        linear go through one ``fk_lora_side_grad_bf16`` call into the optimiser's two fp32 targets, by the protocol of
+        ``_lora_sink`` (``grad_target``, then ``written``).  One workspace, grown to the largest (rows, target) seen."""
+        scales = self._lora_scales()
+        optim = self._optim
+
+        def side_sink(pname, dy, x):
+            e = self._lora_entries[pname]
+            B, R = (1, dy.shape[0]) if dy.dim() == 2 else dy.shape[:2]
+            need = ops.lora_side_grad_ws_floats(B, R, e.up.shape[0], e.down.shape[1], e.rank)
+            if self._side_ws is None or self._side_ws.numel() < need:
+                big = max(ops.lora_side_grad_ws_floats(B, R, f.up.shape[0], f.down.shape[1], f.rank)
+                          for k, f in self._lora_entries.items() if k in self.bw.side)
+                self._side_ws = torch.empty(max(big, need), device=self.model.device, dtype=torch.float32)
+            up, down = self._factor_names(pname)
+            (d_up, acc), (d_down, _) = optim.grad_target(up), optim.grad_target(down)
+            ops.lora_side_grad(x, dy, e.up, e.down, scales[pname], d_up=d_up, d_down=d_down, ws=self._side_ws, accumulate=acc)
+            optim.written([up, down])
+            out[up], out[down] = d_up, d_down
+        return side_sink
 
     @torch.no_grad()
     def prepare_inputs(self, model_input, cond_latents, noise, sigmas, prompt_embeds, pooled, guidance_scale=1.0):
@@ -272,7 +316,8 @@ class DenoiserTrainStep:
                     self._sunk[k] = (g.data_ptr(), g._version)
         if self.lora is not None:
             lora_grads = {}
-            _, d_enc = self.bw.backward(dsample, sink=self._lora_sink(lora_grads), keep=False)
+            side_sink = self._lora_side_sink(lora_grads) if self.bw.side else None
+            _, d_enc = self.bw.backward(dsample, sink=self._lora_sink(lora_grads), keep=False, side_sink=side_sink)
             missing = sorted(k for k in self.trainable_names() if not k.startswith(self.PROJ) and k not in lora_grads)
             if missing:
                 raise RuntimeError("the backward emitted no weight gradient for " + ", ".join(missing[:4]))

@@ -878,6 +878,26 @@ int fk_lora_grad_acc_bf16(const void* dw, int64_t ld_dw, const void* up, int64_t
                           int32_t N, int32_t K, int32_t rank, float scale, float* d_up, float* d_down, int32_t accumulate,
                           float* ws, int64_t ws_floats, fk_stream_t stream);
 
+/* ---- Factored LoRA gradient (train_step.py: DenoiserTrainStep(lora=..., lora_backward="factored")): the same two gradients from
+ * the linear's own backward operands, without the weight gradient dw = dy^T x:
+ *   d_up[n, j] = scale * sum_m dy[m, n] * T[m, j],  T = x down^T      d_down[j, k] = scale * sum_m U[m, j] * x[m, k],  U = dy up
+ * x [B, R, K] and dy [B, R, N]: bf16 views, last dimension contiguous, a row stride ld_* and a batch stride bs_* (>= 0) each, in
+ * elements (the image rows of a joint [B, S, *] buffer, a column block of a wider one; M = B * R is any value >= 1).  up [N, rank],
+ * down [rank, K]: bf16, rows contiguous.  d_up [N, rank], d_down [rank, K]: fp32, contiguous, 4-byte aligned.  All products on the
+ * bf16 MFMA with fp32 accumulation; T and U pass through the workspace as split-bf16 pairs hi = bf16(t), lo = bf16(t - hi)
+ * (|t - hi - lo| <= 2^-18 |t|), both multiplied into one accumulator; scale multiplies the finished sum once.  No atomics, the order
+ * fixed by (B, R, N, K, rank) alone (csrc/lora_side_grad.hip states it): two launches give the same bits.  accumulate = 0: overwrite,
+ * the outputs are never read (they may hold NaN bits); accumulate = 1: the scaled sum is added to the old value, each element read
+ * once and written once by its owner; any other value is FK_EINVAL.  ws: fk_lora_side_grad_ws_floats(B, R, N, K, rank) floats
+ * (0 for unsupported arguments), 4-byte aligned, one per stream of ordered launches.  Inputs are never written; outputs and
+ * workspace overlap nothing.  Supported: 1 <= rank <= FK_LORA_MAX_RANK, ld_* >= the row length, a finite scale; anything else
+ * returns FK_EINVAL / FK_EUNSUPPORTED and writes nothing. ---- */
+int64_t fk_lora_side_grad_ws_floats(int64_t B, int64_t R, int64_t N, int64_t K, int64_t rank);
+int fk_lora_side_grad_bf16(const void* x, int64_t ld_x, int64_t bs_x, const void* dy, int64_t ld_dy, int64_t bs_dy, int64_t B,
+                           int64_t R, int64_t N, int64_t K, const void* up, int64_t ld_up, const void* down, int64_t ld_down,
+                           int64_t rank, float scale, float* d_up, float* d_down, int accumulate, float* ws, int64_t ws_floats,
+                           fk_stream_t stream);
+
 const char* fk_last_error(void);
 /* Build identification: "fk <version> gfx950". */
 const char* fk_version(void);

@@ -2,6 +2,7 @@
 
     python tools/bench_lora_train.py [--ranks 16,64,128] [--steps 3] [--warmup 2] [--out profiles/lora_train.json]
     python tools/bench_lora_train.py --data_parallel [--micro_batches 2] [--ranks 16] [--out profiles/lora_train_dp.json]
+    python tools/bench_lora_train.py --lora_backward factored [--ranks 16,128] [--out profiles/lora_train_factored.json]
 
 Full-size model (19 + 38 blocks, synthetic weights) at the cfg 5 shape (1024^2, batch 1: 512 text + 4096 target + 4096 condition
 tokens), ready ``prompt_embeds`` (no projector on either side):
@@ -19,6 +20,12 @@ and of ``DenoiserTrainStep(model, lora=..., data_parallel=True)`` on the same ba
 backward passes, each overwriting the last: the same work, not the same mathematics), and the summed time of one step's
 projection launches in overwrite form (``fk_lora_grad_bf16``) and in accumulate form (``fk_lora_grad_acc_bf16``, accumulate = 1).
 The full stage-2 step is left out of this record.
+
+With ``--lora_backward factored`` the record is the factored backward beside the projected one (the step as it was before the
+keyword), to ``profiles/lora_train_factored.json``: per rank, two models in ONE process, both warmed, then timed steps taken in turn
+(projected, factored, projected, ...) so that clock and temperature drift hit both alike; and the summed time of one step's side
+launches (``fk_lora_side_grad_bf16``: three kernels per call, on the q / k / v column blocks of a [S, 3D] gradient as the step
+issues them) beside the wgrad GEMMs plus projection launches they replace.  Whichever is faster is recorded as measured.
 
 Every phase builds its own model and frees it; peak memory is reset in between.  No threshold is asserted anywhere.
 """
@@ -81,6 +88,79 @@ def phase(build, steps, warmup, device, micro_batches=1):
                peak_memory_gb=torch.cuda.max_memory_allocated(device) / 1e9)
     del ts, model, batch
     return res
+
+
+def paired_steps(builds, steps, warmup, device):
+    """ms per step of several steps objects, each on a model of its own, timed in turn within one process."""
+    from gpt_image_edit_amd import flux_spec
+    from gpt_image_edit_amd.transformer import HipFluxTransformer2DModel
+    gc.collect()
+    torch.cuda.empty_cache()
+    batch, _ = batch_of(device)
+    arms = {}
+    for name, build in builds.items():
+        model = HipFluxTransformer2DModel(dict(flux_spec.FLUX_KONTEXT_CONFIG), device=device, init="synthetic", seed=0)
+        arms[name] = build(model)
+    for ts in arms.values():
+        for _ in range(warmup):
+            ts.step(**batch)
+    torch.cuda.synchronize()
+    ms = {name: [] for name in arms}
+    loss = {}
+    for _ in range(steps):
+        for name, ts in arms.items():
+            t0 = time.perf_counter()
+            out = ts.step(**batch)
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+            loss[name] = float(out["loss"])
+    res = {name: dict(ms_per_step_median=statistics.median(v), ms_per_step_min=min(v), ms_per_step=v, last_loss=loss[name],
+                      wgrad_set=len(arms[name].bw.trainable), side_targets=len(arms[name].bw.side)) for name, v in ms.items()}
+    del arms, batch
+    return res
+
+
+def side_kernels(rank, S, device, reps, D=3072, n_double=19, n_single=38):
+    """One step's side launches on the default targets beside the wgrad GEMMs + projections they replace, on random operands."""
+    from gpt_image_edit_amd import backward, ops
+    g = torch.Generator(device=device).manual_seed(rank)
+    rnd = lambda *shape, s=1.0: (s * torch.randn(*shape, generator=g, device=device)).to(BF)  # noqa: E731
+    dy3, dy1, x = rnd(1, S, 3 * D, s=0.02), rnd(1, S, D, s=0.02), rnd(1, S, D)
+    bufs = {}
+
+    def buf(name, shape, zero=False):
+        if name not in bufs:
+            bufs[name] = (torch.zeros if zero else torch.empty)(shape, device=device, dtype=BF)
+        return bufs[name]
+    dw3, dw1 = torch.empty(3 * D, D, device=device, dtype=BF), torch.empty(D, D, device=device, dtype=BF)
+    up, down = rnd(D, rank, s=0.02), rnd(rank, D, s=0.02)
+    d_up, d_down = torch.empty(D, rank, device=device), torch.empty(rank, D, device=device)
+    ws, sws = ops.lora_grad_ws(D, D, rank, device), ops.lora_side_grad_ws(1, S, D, D, rank, device)
+
+    def replaced():
+        for _ in range(n_double + n_single):
+            backward.wgrad(buf, dy3, x, out=dw3)
+            for k in range(3):
+                ops.lora_grad(dw3[k * D:(k + 1) * D], up, down, 1.0, d_up=d_up, d_down=d_down, ws=ws)
+        for _ in range(n_double):
+            backward.wgrad(buf, dy1, x, out=dw1)
+            ops.lora_grad(dw1, up, down, 1.0, d_up=d_up, d_down=d_down, ws=ws)
+
+    def side():
+        for _ in range(n_double + n_single):
+            for k in range(3):
+                ops.lora_side_grad(x, dy3[:, :, k * D:(k + 1) * D], up, down, 1.0, d_up=d_up, d_down=d_down, ws=sws)
+        for _ in range(n_double):
+            ops.lora_side_grad(x, dy1, up, down, 1.0, d_up=d_up, d_down=d_down, ws=sws)
+    n = 3 * (n_double + n_single) + n_double
+    r, f = [], []
+    for _ in range(reps):                      # in turn, one repetition each
+        r += bracket_ms(replaced, 1)
+        f += bracket_ms(side, 1)
+    return dict(targets=n, rows=S, replaced_ms_median=statistics.median(r), side_ms_median=statistics.median(f),
+                side_us_per_target=1e3 * statistics.median(f) / n, side_over_replaced=statistics.median(f) / statistics.median(r),
+                side_gb_per_s=n * 2 * 2 * 2 * S * D / 1e9 / (statistics.median(f) / 1e3),   # X and dY read twice each, 2 B per element
+                replaced_ms=r, side_ms=f, note="both brackets include the host loop (one ctypes call per launch group)")
 
 
 def bracket_ms(fn, reps):
@@ -150,10 +230,15 @@ def main():
     ap.add_argument("--skip_full", action="store_true", help="leave out the full stage-2 step (48 GB of optimiser state)")
     ap.add_argument("--data_parallel", action="store_true", help="record the flat data_parallel=True step beside the per-tensor one")
     ap.add_argument("--micro_batches", type=int, default=1, help="backward passes per step (with --data_parallel)")
+    ap.add_argument("--lora_backward", default="projected", choices=["projected", "factored"],
+                    help="factored: record the factored backward beside the projected one")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.lora_backward == "factored" and args.data_parallel:
+        raise SystemExit("--lora_backward factored is a record of its own")
     if args.out is None:
-        args.out = "profiles/lora_train_dp.json" if args.data_parallel else "profiles/lora_train.json"
+        args.out = ("profiles/lora_train_dp.json" if args.data_parallel else "profiles/lora_train_factored.json"
+                    if args.lora_backward == "factored" else "profiles/lora_train.json")
     if args.micro_batches != 1 and not args.data_parallel:
         raise SystemExit("--micro_batches belongs to --data_parallel")
     if not torch.cuda.is_available():
@@ -162,6 +247,21 @@ def main():
     dev = "cuda"
     _, S = batch_of(dev)
     res = dict(device=torch.cuda.get_device_name(0), shape="cfg5 1024x1024 bs1", seq_len=S, steps=args.steps, warmup=args.warmup, ranks=[])
+    if args.lora_backward == "factored":
+        for rank in [int(r) for r in args.ranks.split(",")]:
+            def build(m, mode, rank=rank):
+                m.add_lora_adapter("bench", rank=rank)
+                return DenoiserTrainStep(m, lora="bench", lora_backward=mode)
+            entry = dict(rank=rank, kernels=side_kernels(rank, S, dev, args.reps),
+                         **paired_steps({mode: (lambda m, mode=mode: build(m, mode)) for mode in ("projected", "factored")},
+                                        args.steps, args.warmup, dev))
+            res["ranks"].append(entry)
+            print(json.dumps({"rank": rank, **{a: {k: v for k, v in entry[a].items() if k != "ms_per_step"} for a in ("projected", "factored")},
+                              "kernels": {k: v for k, v in entry["kernels"].items() if not k.endswith("_ms")}}), flush=True)
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if args.data_parallel:
         res.update(world=1, micro_batches=args.micro_batches)
         for rank in [int(r) for r in args.ranks.split(",")]:
