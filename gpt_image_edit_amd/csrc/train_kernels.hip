@@ -41,12 +41,17 @@ FK_DEV int64_t latent_index(int64_t tok, int C, int h, int w) {
 __global__ __launch_bounds__(256) void flow_mix_pack_kernel(const float* x, const float* noise, const float* sigma,
                                                             bf16_t* tokens, int64_t tok_bs, int C, int h, int w,
                                                             int64_t n_per_batch, int64_t total) {
+  // Plain operators under contract(off): to hipcc __fmul_rn / __fadd_rn are the same operators, compiled in a header where its
+  // default -ffp-contract=fast-honor-pragmas holds, and the mix became one fma -- the bf16 token of a few elements in a million then
+  // differs from the reference's separately rounded fp32 expression (tests/test_hip_train_kernels.py::test_noisy_tokens, 557 056 elements)
+#pragma clang fp contract(off)
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int64_t b = i / n_per_batch, r = i - b * n_per_batch;
     const int64_t src = latent_index(i, C, h, w);
     const float sg = sigma[b];
-    const float v = __fadd_rn(__fmul_rn(1.0f - sg, x[src]), __fmul_rn(sg, noise[src]));
-    tokens[b * tok_bs + r] = f2bf(v);
+    const float a = (1.0f - sg) * x[src];
+    const float c = sg * noise[src];
+    tokens[b * tok_bs + r] = f2bf(a + c);
   }
 }
 
@@ -108,22 +113,28 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* master, bf16_t* param
                                                     float* m, float* v, const double* grad_sumsq, float max_norm,
                                                     float grad_scale, float decay, float b1, float b2, float eps,
                                                     float step_size, float bc2_sqrt, int64_t n) {
+  // One rounding per operation, as torch's single-tensor AdamW, which needs plain operators under contract(off): to hipcc the _rn
+  // intrinsics are the same operators compiled in a header, where its default -ffp-contract=fast-honor-pragmas holds (three of the
+  // products below were fused into their sums), and __fsqrt_rn is its native 1-ulp square root.  sqrtf and / are correctly rounded
+  // in this build (tests/test_hip_train_kernels.py::test_adamw holds the result to a float32 emulation bit for bit).
+#pragma clang fp contract(off)
   // grad_scale: the stored gradients are grad_scale^-1 times the gradient to apply (sums over the data-parallel ranks:
   // grad_scale = 1 / world) -- folded into the clipping coefficient, so no separate pass divides them
   float coef = grad_scale;
   if (grad_sumsq) {
-    const float total = __fmul_rn((float)sqrt(grad_sumsq[0]), grad_scale);
-    coef = __fmul_rn(fminf(max_norm / (total + 1e-6f), 1.0f), grad_scale);
+    const float total = (float)sqrt(grad_sumsq[0]) * grad_scale;
+    coef = fminf(max_norm / (total + 1e-6f), 1.0f) * grad_scale;
   }
+  const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     float g = g_is_bf16 ? bf2f(((const bf16_t*)grad)[i]) : ((const float*)grad)[i];
-    g = __fmul_rn(g, coef);
-    float p = __fmul_rn(master[i], decay);
+    g = g * coef;
+    float p = master[i] * decay;
     const float mi = m[i], vi = v[i];
-    const float mn = __fadd_rn(mi, __fmul_rn(1.0f - b1, __fsub_rn(g, mi)));            // lerp_
-    const float vn = __fadd_rn(__fmul_rn(vi, b2), __fmul_rn(__fmul_rn(1.0f - b2, g), g));   // mul_ + addcmul_
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(vn), bc2_sqrt), eps);
-    p = __fadd_rn(p, __fmul_rn(-step_size, __fdiv_rn(mn, denom)));                        // addcdiv_
+    const float mn = mi + omb1 * (g - mi);             // lerp_
+    const float vn = vi * b2 + (omb2 * g) * g;         // mul_ + addcmul_
+    const float denom = sqrtf(vn) / bc2_sqrt + eps;
+    p = p + (-step_size) * (mn / denom);               // addcdiv_
     master[i] = p; m[i] = mn; v[i] = vn;
     if (param_bf16) param_bf16[i] = f2bf(p);
   }

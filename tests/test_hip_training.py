@@ -125,8 +125,10 @@ def test_adamw_with_clipping_matches_torch(ops):
             torch.testing.assert_close(master[i].cpu(), p.detach(), rtol=3e-6, atol=3e-8)
             assert torch.equal(bf[i].cpu(), master[i].cpu().to(BF))
     # bf16 gradients (what a bf16 backward hands over) and no clipping
+    # within the derived bound of the float64 step on the state reached above (test_hip_train_kernels.check_bf16_gradient_step)
+    from test_hip_train_kernels import check_bf16_gradient_step
     g16 = [torch.randn(s).to(BF) for s in shapes]
     before = [t.clone() for t in master]
     for i in range(len(shapes)):
-        ops.adamw_step(master[i], g16[i].cuda(), m[i], v[i], 4, lr=1e-3, betas=(0.9, 0.99), weight_decay=0.0)
+        check_bf16_gradient_step(ops, master[i], g16[i].cuda(), m[i], v[i], 4, lr=1e-3, betas=(0.9, 0.99), weight_decay=0.0)
     assert all(not torch.equal(a, b) for a, b in zip(before, master))
