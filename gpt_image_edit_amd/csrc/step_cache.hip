@@ -1,8 +1,9 @@
 // Step cache (residual caching across denoise steps, pipeline.py / step_cache.py): the measure and the two residual passes.
-// Three HBM-bound kernels over bf16 [B, R, D] views with contiguous rows, a row stride and a batch stride of their own
-// (fk_rows) -- the caller hands over the image part of a joint [B, S_txt + S_img, D] buffer as it is.
+// Four HBM-bound kernels over bf16 [B, R, D] views with contiguous rows, a row stride and a batch stride of their own
+// (fk_rows) -- the caller hands over the image part of a joint [B, S_txt + S_img, D] buffer as it is.  The fourth is the
+// first-block measure (fk_residual_absdiff_sums_bf16): the residual pass and the sums in one, with the bits of the two.
 //
-// One decomposition for all three: a work item is chunk c (elements [8c, 8c + 8) of the row, cut at D) of row m, item
+// One decomposition for all of them: a work item is chunk c (elements [8c, 8c + 8) of the row, cut at D) of row m, item
 // i = m * cpr + c with cpr = ceil(D / 8); thread g of the grid takes items g, g + T, g + 2T, ... (T = blocks * 256, at most
 // SC_MAX_BLOCKS blocks).  A full chunk of a view whose rows are 16-byte aligned is one 16-byte load / store; a cut chunk, or
 // any chunk of an unaligned view, goes element by element.  Nothing outside [0, D) of a row is read or written.
@@ -67,6 +68,64 @@ __global__ __launch_bounds__(SC_THREADS) void absdiff_partials_kernel(const bf16
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       td[e] = fabsf(fa[e] - fb[e]);
+      tb[e] = fabsf(fb[e]);
+    }
+    accd += tree8(td);
+    accb += tree8(tb);
+  }
+  sd[t] = accd;
+  sb[t] = accb;
+  block_tree(sd, sb, t);
+  if (t == 0) {
+    ws[2 * (int64_t)blockIdx.x] = sd[0];
+    ws[2 * (int64_t)blockIdx.x + 1] = sb[0];
+  }
+}
+
+// The first-block measure as one pass: r = bf16(float(h1) - float(h0)) (residual_kernel<., -1>'s value), optionally stored, then
+// the terms |float(r) - float(ref)| and |float(ref)| through absdiff_partials_kernel's decomposition and order -- hence the
+// bits of residual_save followed by absdiff_sums.  ALIGNED speaks for every view of the launch, r_out included.
+template <bool ALIGNED, bool STORE>
+__global__ __launch_bounds__(SC_THREADS) void residual_absdiff_partials_kernel(const bf16_t* h1, fk_rows r1, const bf16_t* h0,
+                                                                               fk_rows r0, const bf16_t* ref, fk_rows rf,
+                                                                               bf16_t* r_out, fk_rows rr, int64_t nitems,
+                                                                               int cpr, int D, float* ws) {
+  __shared__ float sd[SC_THREADS], sb[SC_THREADS];
+  const int t = threadIdx.x;
+  float accd = 0.0f, accb = 0.0f;
+  for (int64_t i = (int64_t)blockIdx.x * SC_THREADS + t; i < nitems; i += (int64_t)gridDim.x * SC_THREADS) {
+    const int64_t m = i / cpr;
+    const int c = (int)(i - m * cpr);
+    const bf16_t* xr = h1 + fk_row_offset(r1, m);
+    const bf16_t* yr = h0 + fk_row_offset(r0, m);
+    float fr[8], fb[8], td[8], tb[8];
+    load_chunk<ALIGNED>(ref + fk_row_offset(rf, m), c, D, fb);
+    if (ALIGNED && c * 8 + 8 <= D) {
+      const u32x4_t xw = *(const u32x4_t*)(xr + c * 8), yw = *(const u32x4_t*)(yr + c * 8);
+      u32x4_t ow;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        ow[e] = pack_bf2(bf_lo(xw[e]) - bf_lo(yw[e]), bf_hi(xw[e]) - bf_hi(yw[e]));
+        fr[2 * e] = bf_lo(ow[e]);
+        fr[2 * e + 1] = bf_hi(ow[e]);
+      }
+      if (STORE) *(u32x4_t*)(r_out + fk_row_offset(rr, m) + c * 8) = ow;
+    } else {
+      bf16_t* orow = STORE ? r_out + fk_row_offset(rr, m) : nullptr;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int j = c * 8 + e;
+        fr[e] = 0.0f;
+        if (j < D) {
+          const bf16_t rv = f2bf(bf2f(xr[j]) - bf2f(yr[j]));
+          fr[e] = bf2f(rv);
+          if (STORE) orow[j] = rv;
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      td[e] = fabsf(fr[e] - fb[e]);
       tb[e] = fabsf(fb[e]);
     }
     accd += tree8(td);
@@ -217,6 +276,46 @@ extern "C" int fk_absdiff_sums_bf16(const void* a, fk_rows ra, const void* b, fk
   FK_CHECK_LAUNCH("fk_absdiff_sums_bf16");
   hipLaunchKernelGGL(absdiff_final_kernel, dim3(1), dim3(SC_THREADS), 0, st, (const float*)ws, nblk, out);
   FK_CHECK_LAUNCH("fk_absdiff_sums_bf16 (final)");
+  return FK_OK;
+}
+
+extern "C" int fk_residual_absdiff_sums_bf16(const void* h1, fk_rows r1, const void* h0, fk_rows r0, const void* ref, fk_rows rf,
+                                             void* r_out, fk_rows rr, int64_t M, int32_t D, int32_t is_bf16, float* out,
+                                             float* ws, int64_t ws_floats, fk_stream_t stream) {
+  const char* name = "fk_residual_absdiff_sums_bf16";
+  FK_CHECK_ARG(h1 && h0 && ref && out && ws, "%s: NULL pointer", name);
+  FK_CHECK_ARG(M >= 1 && D >= 1, "%s: needs M >= 1 rows of D >= 1 elements (M = %lld, D = %d)", name, (long long)M, D);
+  if (!is_bf16) {
+    fk_set_error("%s: bf16 views only", name);
+    return FK_EUNSUPPORTED;
+  }
+  FK_CHECK_ARG(rows_ok(r1, D) && rows_ok(r0, D) && rows_ok(rf, D) && (!r_out || rows_ok(rr, D)),
+               "%s: a row stride below D = %d (or a negative batch stride)", name, D);
+  if (r_out) {
+    FK_CHECK_ARG(rows_disjoint(rr, D), "%s: r_out's rows overlap", name);
+    const Span so = span_of(r_out, rr, M, D);
+    FK_CHECK_ARG(!overlap(so, span_of(h1, r1, M, D)) && !overlap(so, span_of(h0, r0, M, D)) && !overlap(so, span_of(ref, rf, M, D)),
+                 "%s: r_out overlaps an input", name);
+  }
+  const int cpr = (D + 7) / 8;
+  const int64_t nitems = M * cpr;
+  const int nblk = grid_of(nitems);
+  FK_CHECK_ARG(ws_floats >= 2 * (int64_t)nblk, "%s: the workspace holds %lld floats, %d blocks need %d", name,
+               (long long)ws_floats, nblk, 2 * nblk);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool al = aligned16(h1, r1) && aligned16(h0, r0) && aligned16(ref, rf) && (!r_out || aligned16(r_out, rr));
+  const dim3 grid(nblk), block(SC_THREADS);
+#define FK_SC_LAUNCH(AL, ST)                                                                                              \
+  hipLaunchKernelGGL((residual_absdiff_partials_kernel<AL, ST>), grid, block, 0, st, (const bf16_t*)h1, r1, (const bf16_t*)h0, \
+                     r0, (const bf16_t*)ref, rf, (bf16_t*)r_out, rr, nitems, cpr, (int)D, ws)
+  if (al && r_out) FK_SC_LAUNCH(true, true);
+  else if (al) FK_SC_LAUNCH(true, false);
+  else if (r_out) FK_SC_LAUNCH(false, true);
+  else FK_SC_LAUNCH(false, false);
+#undef FK_SC_LAUNCH
+  FK_CHECK_LAUNCH(name);
+  hipLaunchKernelGGL(absdiff_final_kernel, dim3(1), dim3(SC_THREADS), 0, st, (const float*)ws, nblk, out);
+  FK_CHECK_LAUNCH("fk_residual_absdiff_sums_bf16 (final)");
   return FK_OK;
 }
 

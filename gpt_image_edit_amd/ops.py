@@ -783,7 +783,7 @@ def pack_inpaint_mask(mask, h_lat, w_lat):
     return m.reshape(m.shape[0], (h_lat // 2) * (w_lat // 2), 4).to(BF16).contiguous()
 
 
-# ---- step cache (include/fk.h: fk_absdiff_sums_bf16, fk_residual_save_bf16, fk_residual_apply_bf16) -------------------
+# ---- step cache (include/fk.h: fk_absdiff_sums_bf16, fk_residual_absdiff_sums_bf16, fk_residual_save_bf16, fk_residual_apply_bf16)
 def _step_cache_views(what, *ts):
     """(M, D, is_bf16, [Rows]) of [B, R, D] (or [M, D]) views of one shape and dtype with contiguous rows.  The dtype travels
     with the call: the library refuses anything but bf16 (FK_EUNSUPPORTED)."""
@@ -816,6 +816,27 @@ def absdiff_sums(a, b, out=None, ws=None):
         raise ValueError("out must be fp32 [2], ws a contiguous fp32 workspace")
     libfk.check(libfk.load().fk_absdiff_sums_bf16(_ptr(a), ra, _ptr(b), rb, M, D, eb, _ptr(out), _ptr(ws), ws.numel(), _stream()),
                 "fk_absdiff_sums_bf16")
+    return out
+
+
+def residual_absdiff_sums(h1, h0, ref, r_out=None, out=None, ws=None):
+    """The first-block measure in one pass: ``r = bf16(float(h1) - float(h0))`` (:func:`residual_save`'s value, written to
+    ``r_out`` when given) and fp32 [2] ``(sum |r - ref|, sum |ref|)`` in :func:`absdiff_sums`' order -- the bits of
+    ``residual_save(h1, h0, r)`` followed by ``absdiff_sums(r, ref)``.  bf16 [B, R, D] views with contiguous rows; ``r_out`` may
+    overlap no input."""
+    views = (h1, h0, ref) if r_out is None else (h1, h0, ref, r_out)
+    M, D, eb, rows = _step_cache_views("residual_absdiff_sums", *views)
+    if out is None:
+        out = torch.empty(2, device=h1.device, dtype=torch.float32)
+    if ws is None:
+        ws = absdiff_ws(h1.device)
+    _need_cuda(out, ws)
+    if out.dtype != torch.float32 or out.numel() < 2 or not out.is_contiguous() or ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError("out must be fp32 [2], ws a contiguous fp32 workspace")
+    rr = rows[3] if r_out is not None else Rows(0, 0, 0)
+    libfk.check(libfk.load().fk_residual_absdiff_sums_bf16(_ptr(h1), rows[0], _ptr(h0), rows[1], _ptr(ref), rows[2], _ptr(r_out), rr,
+                                                           M, D, eb, _ptr(out), _ptr(ws), ws.numel(), _stream()),
+                "fk_residual_absdiff_sums_bf16")
     return out
 
 

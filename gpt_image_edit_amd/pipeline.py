@@ -312,7 +312,8 @@ class FluxKontextPipeline:
         ``step_cache`` (a ``step_cache.StepCache``): skip the MMDiT blocks on the steps its rule or schedule says, adding the
         residual kept at the last computed step instead (one decision per step for the whole model batch).  A schedule is
         sync-free and graph-capturable; the adaptive rule reads 8 bytes back per step and therefore runs the eager loop.
-        ``None`` is today's call, launch for launch.
+        ``StepCache(..., measure="first_block")`` runs block 0 at every step, measures what it added to the image stream and
+        skips only the blocks behind it.  ``None`` is today's call, launch for launch.
 
         ``joint_attention_kwargs["scale"]`` (default 1.0): the call scale of the loaded LoRA adapters (``load_lora_weights``)."""
         device = self.device
@@ -525,8 +526,9 @@ class FluxKontextPipeline:
         if not hasattr(tr, "step_cache_begin"):
             raise ValueError("`step_cache` needs a transformer with the two-phase forward (HipFluxTransformer2DModel)")
         st = L.cache_state if L.cache_state is not None else self._cache_state
-        if st is None or st.measure != L.step_cache.adaptive:
-            st = tr.step_cache_state(measure=L.step_cache.adaptive)
+        sc = L.step_cache
+        if st is None or st.measure != sc.adaptive or st.mode != sc.measure:
+            st = tr.step_cache_state(measure=sc.adaptive, mode=sc.measure)
         if L.cache_state is None:
             self._cache_state = st
         st.steps, st.block_passes, st.have_residual, st.f = 0, 0, False, None
@@ -550,8 +552,8 @@ class FluxKontextPipeline:
                # masked edits: the preserved picture, the noise and the mask are inputs (a new mask of the same shape replays);
                # their presence, the mask's batch form and the keep region's noise levels are frozen into the graph
                L.inpaint, None if L.mask is None else tuple(L.mask.shape), tuple(L.sigma_next),
-               # step cache: which steps run the blocks is frozen into the graph
-               None if L.step_cache is None else L.step_cache.schedule)
+               # step cache: which steps run the blocks, and which blocks a skipped step still runs, is frozen into the graph
+               None if L.step_cache is None else (L.step_cache.schedule, L.step_cache.measure))
         cur = torch.cuda.current_stream()
         if self._loop_graph is None or self._loop_graph[0] != key:
             self._loop_graph = None
@@ -561,7 +563,7 @@ class FluxKontextPipeline:
                 setattr(G, n, None if t is None else t.clone())
             G.model_tokens = torch.empty_like(L.model_tokens) if L.do_true_cfg else G.tokens
             if L.step_cache is not None:    # the cache state (h0, the residual) belongs to the graph's own buffers
-                G.cache_state = self.transformer.step_cache_state(measure=False)
+                G.cache_state = self.transformer.step_cache_state(measure=False, mode=L.step_cache.measure)
             side = torch.cuda.Stream(device=L.tokens.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):       # eager warm-up off the capture: kernel attributes, workspaces, RoPE cache

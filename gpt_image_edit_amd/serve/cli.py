@@ -111,11 +111,12 @@ def inpaint_kwargs(args):
 
 
 def step_cache_kwargs(args):
-    """``--step_cache_threshold`` / ``--step_cache_schedule`` / ``--step_cache_coefficients`` as the pipeline's ``step_cache``
+    """``--step_cache_threshold`` / ``--step_cache_schedule`` / ``--step_cache_coefficients`` / ``--step_cache_measure`` as the
+    pipeline's ``step_cache``
     (nothing when neither mode is given: every step runs the blocks).  A fresh ``StepCache`` per call."""
     from ..step_cache import from_args
     sc = from_args(getattr(args, "step_cache_threshold", None), getattr(args, "step_cache_schedule", None),
-                   getattr(args, "step_cache_coefficients", None))
+                   getattr(args, "step_cache_coefficients", None), getattr(args, "step_cache_measure", None))
     return {} if sc is None else {"step_cache": sc}
 
 
@@ -135,6 +136,10 @@ def add_step_cache_arguments(parser):
                              "goes through the graph route")
     parser.add_argument("--step_cache_coefficients", type=str, default=None, metavar="a0,a1,...",
                         help="with --step_cache_threshold: rescaling polynomial of the measure, lowest order first (default 0,1)")
+    parser.add_argument("--step_cache_measure", choices=("input", "first_block"), default=None,
+                        help="what the step cache measures and skips (default input): input -- the first block's modulated "
+                             "input, every block skipped; first_block -- block 0 runs at every step, the change of what it adds "
+                             "to the image stream is compared with F directly and the blocks behind it are skipped")
 
 
 def generate_image(pipe, prompt_embeds, pooled_prompt_embeds, history_image_paths, new_h, new_w, args, fused_pixels=True):

@@ -16,14 +16,27 @@ Two modes, exactly one of which must be chosen:
                 when ``strength < 1``).  Must contain 0, be strictly increasing and lie inside the step count.  Nothing is
                 measured and nothing is read back: the loop stays sync-free and graph-capturable.
 
+``measure="first_block"`` (the first-block cache of ParaAttention / diffusers' ``FirstBlockCacheConfig``) changes what
+is measured and what is skipped.  Block 0 runs at EVERY step; ``r1`` is what it added to the image stream.  Adaptive:
+``rel = sum|r1 - ref| / sum|ref|`` against the ``r1`` of the last computed step (``ops.residual_absdiff_sums``), and the step
+computes iff ``rel >= threshold`` -- nothing is accumulated (``ref`` stays put, so drift adds up by itself) and there is no
+polynomial (``coefficients`` other than the default is a ``ValueError``).  A skipped step adds the residual of blocks 1 .. end
+kept at the last computed step to block 0's output.  ``schedule=`` names the same steps with nothing measured.
+
 After a call ``computed_steps`` lists the computed step indices, ``block_passes`` counts the passes through the blocks the
 transformer made and, in adaptive mode, ``rel_l1`` holds the per-step floats (steps 1 .. n-1); ``StepCache(schedule=sc.computed_steps)`` replays an adaptive run's decisions.
 """
 import math
 
 
+MEASURES = ("input", "first_block")
+
+
 class StepCache:
-    def __init__(self, threshold=None, schedule=None, coefficients=(0.0, 1.0)):
+    def __init__(self, threshold=None, schedule=None, coefficients=(0.0, 1.0), measure="input"):
+        if measure not in MEASURES:
+            raise ValueError(f"`measure` must be one of {MEASURES}, got {measure!r}")
+        self.measure = measure
         if (threshold is None) == (schedule is None):
             raise ValueError("StepCache takes exactly one of `threshold` (adaptive) and `schedule` (fixed)")
         self.threshold = None
@@ -45,11 +58,17 @@ class StepCache:
         self.coefficients = tuple(float(c) for c in coefficients)
         if not self.coefficients:
             raise ValueError("`coefficients` must hold at least one value (lowest order first)")
+        if self.first_block and self.coefficients != (0.0, 1.0):
+            raise ValueError('`coefficients` belongs to measure="input": the first-block measure is a plain relative change')
         self.begin(0)
 
     @property
     def adaptive(self):
         return self.threshold is not None
+
+    @property
+    def first_block(self):
+        return self.measure == "first_block"
 
     # ---- pure pieces -------------------------------------------------------------------------------------------------
     @staticmethod
@@ -72,6 +91,8 @@ class StepCache:
         with); the first and the last step compute whatever the measure says."""
         if i == 0:
             return True, 0.0
+        if self.first_block:         # no accumulation: the reference residual stays where it is, so drift adds up by itself
+            return i == n - 1 or math.isnan(rel) or rel >= self.threshold, 0.0
         acc = acc + self.polyval(self.coefficients, rel)
         if math.isnan(acc):          # inf - inf through a polynomial with a negative coefficient: never skip on a NaN
             acc = math.inf
@@ -123,13 +144,15 @@ def parse_float_list(text):
     return [float(p) for p in str(text).split(",") if p.strip() != ""]
 
 
-def from_args(threshold=None, schedule=None, coefficients=None):
-    """The command line's three options -> a StepCache, or None when neither mode is asked for."""
+def from_args(threshold=None, schedule=None, coefficients=None, measure=None):
+    """The command line's four options -> a StepCache, or None when neither mode is asked for."""
     if threshold is None and schedule is None:
         if coefficients is not None:
             raise ValueError("--step_cache_coefficients needs --step_cache_threshold")
         return None
     kw = {}
+    if measure is not None:
+        kw["measure"] = measure
     if coefficients is not None:
         kw["coefficients"] = parse_float_list(coefficients)
     return StepCache(threshold=threshold, schedule=None if schedule is None else parse_int_list(schedule), **kw)

@@ -535,15 +535,27 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
             mod = ws.mod
         return mod
 
-    def _infer_blocks(self, f, mod, key_mask=None):
-        """The 19 + 38 blocks on the workspace's residual stream, on whichever route applies."""
+    @staticmethod
+    def _block_ranges(pk, blocks):
+        """``blocks`` = (lo, hi) over the block sequence (the double blocks, then the single ones; None: all of them) -> the
+        ranges of double and of single block indices it covers."""
+        nd, ns = len(pk.double), len(pk.single)
+        lo, hi = (0, nd + ns) if blocks is None else blocks
+        if not 0 <= lo <= hi <= nd + ns:
+            raise ValueError(f"block range {blocks} outside the model's {nd} + {ns} blocks")
+        return range(min(lo, nd), min(hi, nd)), range(max(lo - nd, 0), max(hi - nd, 0))
+
+    def _infer_blocks(self, f, mod, key_mask=None, blocks=None):
+        """The 19 + 38 blocks on the workspace's residual stream, on whichever route applies.  ``blocks`` = (lo, hi): only that
+        part of the block sequence (blocks talk to one another through the residual stream alone, so a range followed by the
+        rest is the whole loop, launch for launch)."""
         D = self.inner_dim
         pk, ws, B, S_txt, S_img, cos, sin, cs = f.pk, f.ws, f.B, f.S_txt, f.S_img, f.cos, f.sin, f.cs
         s = ws.s
         block_api = BLOCK_API if (FUSE_QKV and not MLP_FIRST and not (OVERLAP_MLP and (OVERLAP_MLP != "auto" or self._overlap_pays(B, ws.S)))
                                   and S_txt > 0) else 0
         if key_mask is not None:   # masked attention: per-launch bf16 route, no block-level entry point, no side stream
-            self._blocks_by_kernel_calls(ws, pk, mod, cos, sin, cs, B, S_txt, key_mask)
+            self._blocks_by_kernel_calls(ws, pk, mod, cos, sin, cs, B, S_txt, key_mask, blocks=blocks)
         elif pk.format == "mxfp8":
             if ws.mxq is None:
                 # quantized activations: one launch's operand, at most B * S rows of K = 5D -- and in front of it, in the fused
@@ -554,15 +566,15 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
             if S_txt == 0:
                 raise ValueError("the mxfp8 weight format needs a text stream (S_txt > 0)")
             if BLOCK_API:
-                self._blocks_by_c_entry(ws, pk, mod, cs, B, S_txt, S_img, BLOCK_API)
+                self._blocks_by_c_entry(ws, pk, mod, cs, B, S_txt, S_img, BLOCK_API, blocks=blocks)
             elif MX_FUSED_QUANT:
-                self._blocks_by_kernel_calls_mx_fused(ws, pk, mod, cs, B, S_txt)
+                self._blocks_by_kernel_calls_mx_fused(ws, pk, mod, cs, B, S_txt, blocks=blocks)
             else:
-                self._blocks_by_kernel_calls_mx(ws, pk, mod, cs, S_txt)
+                self._blocks_by_kernel_calls_mx(ws, pk, mod, cs, S_txt, blocks=blocks)
         elif block_api:
-            self._blocks_by_c_entry(ws, pk, mod, cs, B, S_txt, S_img, block_api)
+            self._blocks_by_c_entry(ws, pk, mod, cs, B, S_txt, S_img, block_api, blocks=blocks)
         else:
-            self._blocks_by_kernel_calls(ws, pk, mod, cos, sin, cs, B, S_txt)
+            self._blocks_by_kernel_calls(ws, pk, mod, cos, sin, cs, B, S_txt, blocks=blocks)
 
     def _infer_head(self, f, mod):
         """Output head: AdaLayerNormContinuous (scale first, then shift) + proj_out on the image stream."""
@@ -574,10 +586,16 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
         return ops.gemm(f.n_img, self.p("proj_out.weight"), self.p("proj_out.bias"))
 
     # ---- step cache: one forward in two phases (pipeline._denoise; step_cache.py holds the decision) ------------------------
-    def step_cache_state(self, measure):
+    def step_cache_state(self, measure, mode="input"):
         """State of one cached denoise loop.  ``measure``: adaptive mode -- every ``step_cache_begin`` also writes the first
-        block's modulated image input and launches the distance to the previous step's into ``state.sums`` (fp32 [2])."""
-        return SimpleNamespace(measure=bool(measure), key=None, f=None, mod=None, key_mask=None, block_passes=0, steps=0,
+        block's modulated image input and launches the distance to the previous step's into ``state.sums`` (fp32 [2]).
+        ``mode`` (``StepCache.measure``): ``"first_block"`` runs block 0 at every step and caches what blocks 1 .. end add
+        (:meth:`_first_block_begin`); there ``measure`` compares what block 0 added with the last computed step's."""
+        if mode not in ("input", "first_block"):
+            raise ValueError(f"unknown step-cache mode {mode!r}")
+        if mode == "first_block" and len(self.packed().double) + len(self.packed().single) < 2:
+            raise ValueError("the first-block step cache needs a model of at least two blocks: behind block 0 there is nothing to skip")
+        return SimpleNamespace(measure=bool(measure), mode=mode, key=None, f=None, mod=None, key_mask=None, block_passes=0, steps=0,
                                have_residual=False, h0=None, r=None, cur=None, prev=None, sums=None, absdiff_ws=None)
 
     @torch.no_grad()
@@ -593,6 +611,8 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
         if joint_attention_kwargs and joint_attention_kwargs.get("attention_mask") is not None:
             state.key_mask = self._joint_key_mask(joint_attention_kwargs["attention_mask"], hidden_states, encoder_hidden_states)
         f = self._infer_frame(hidden_states, encoder_hidden_states, pooled_projections, img_ids, txt_ids)
+        if state.mode == "first_block":
+            return self._first_block_begin(state, f, timestep, guidance, pooled_projections)
         D, dev = self.inner_dim, f.ws.s.device
         key = (f.B, f.S_img, D, dev, state.measure)
         if state.key != key:        # buffers once per call shape; a new shape starts a new loop
@@ -613,6 +633,53 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
             state.cur, state.prev = state.prev, state.cur       # the previous modulated input is replaced at EVERY step
         state.steps += 1
 
+    def _first_block_begin(self, state, f, timestep, guidance, pooled_projections):
+        """``step_cache_begin`` of the first-block mode: both embedders into the workspace stream, the step's modulation, block 0
+        on the route the plain forward takes.  With ``state.measure`` the image stream is copied to ``state.h0`` in front of
+        block 0 and, behind it, ``state.cur = r1 = bf16(h1 - h0)``: at step 0 by ``ops.residual_save``, later by
+        ``ops.residual_absdiff_sums``, which also leaves (sum |r1 - ref|, sum |ref|) in ``state.sums`` -- ``state.prev`` is the
+        reference, the ``r1`` of the last computed step."""
+        D, dev = self.inner_dim, f.ws.s.device
+        key = (f.B, f.S_img, D, dev, state.measure, state.mode)
+        if state.key != key:
+            e = lambda: torch.empty((f.B, f.S_img, D), device=dev, dtype=BF16)  # noqa: E731
+            # h0: the image stream in front of block 0 (measure), then in front of block 1 (a computed step); r: what blocks 1 .. end added
+            state.key, state.h0, state.r, state.have_residual, state.steps = key, e(), e(), False, 0
+            if state.measure:
+                state.cur, state.prev = e(), e()
+                state.sums = torch.zeros(2, device=dev, dtype=torch.float32)
+                state.absdiff_ws = ops.absdiff_ws(dev)
+        ops.gemm(f.hs, self.p("x_embedder.weight"), self.p("x_embedder.bias"), out=f.h)
+        ops.gemm(f.enc, self.p("context_embedder.weight"), self.p("context_embedder.bias"), out=f.cx)
+        state.f, state.mod = f, self._infer_modulation(f, timestep, guidance, pooled_projections)
+        if state.measure:
+            state.h0.copy_(f.h)
+        self._infer_blocks(f, state.mod, state.key_mask, blocks=(0, 1))
+        if state.measure:
+            if state.steps > 0:
+                ops.residual_absdiff_sums(f.h, state.h0, state.prev, r_out=state.cur, out=state.sums, ws=state.absdiff_ws)
+            else:
+                ops.residual_save(f.h, state.h0, state.cur)
+        state.steps += 1
+
+    def _first_block_end(self, state, f, mod, compute):
+        """``step_cache_end`` of the first-block mode.  ``compute=True``: keep h1, run blocks 1 .. end, ``state.r = h - h1``, and
+        this step's ``r1`` becomes the reference.  ``compute=False``: ``h = h1 + state.r`` in place on the stream."""
+        if compute:
+            state.h0.copy_(f.h)
+            pk = f.pk
+            self._infer_blocks(f, mod, state.key_mask, blocks=(1, len(pk.double) + len(pk.single)))
+            ops.residual_save(f.h, state.h0, state.r)
+            if state.measure:
+                state.cur, state.prev = state.prev, state.cur
+            state.have_residual = True
+            state.block_passes += 1
+        else:
+            if not state.have_residual:
+                raise RuntimeError("step cache: a skipped step before any computed one has no residual to add")
+            ops.residual_apply(f.h, state.r, out=f.h)
+        return self._infer_head(f, mod)
+
     @torch.no_grad()
     def step_cache_end(self, state, compute):
         """Second phase.  ``compute=True``: h0 into the workspace stream, ``context_embedder``, the blocks (on the route the
@@ -622,6 +689,8 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
         if f is None:
             raise RuntimeError("step_cache_end without step_cache_begin")
         state.f = None
+        if state.mode == "first_block":
+            return self._first_block_end(state, f, mod, compute)
         if compute:
             f.h.copy_(state.h0)
             ops.gemm(f.enc, self.p("context_embedder.weight"), self.p("context_embedder.bias"), out=f.cx)
@@ -635,7 +704,7 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
             ops.residual_apply(state.h0, state.r, out=f.h)
         return self._infer_head(f, mod)
 
-    def _blocks_by_kernel_calls(self, ws, pk, mod, cos, sin, cs, B, S_txt, key_mask=None):
+    def _blocks_by_kernel_calls(self, ws, pk, mod, cos, sin, cs, B, S_txt, key_mask=None, blocks=None):
         """The 19 + 38 blocks as one ctypes call per kernel launch (FK_BLOCK_API=0; also the route of the A/B switches
         FK_FUSE_QKV=0, FK_MLP_FIRST=1, FK_OVERLAP_MLP, and of a forward with an attention mask: ``key_mask``, packed)."""
         P, D = self.p, self.inner_dim
@@ -647,7 +716,9 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
             return mod[:, off + j * D: off + (j + 1) * D]
 
         # -- double-stream blocks ----------------------------------------------------------------------
-        for i, blk in enumerate(pk.double):
+        dr, sr = self._block_ranges(pk, blocks)
+        for i in dr:
+            blk = pk.double[i]
             p = f"transformer_blocks.{i}."
             mi, mt = blk.mod_img, blk.mod_txt  # chunks: shift, scale, gate, shift_mlp, scale_mlp, gate_mlp
             # text + image streams share every launch: joint LN+modulate, grouped GEMMs (one grid, two weights)
@@ -691,7 +762,8 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
         if side is not None:
             main = torch.cuda.current_stream()
             ev_n, ev_mlp = self._side_events
-        for i, blk in enumerate(pk.single):
+        for i in sr:
+            blk = pk.single[i]
             p = f"single_transformer_blocks.{i}."
             m0 = blk.mod  # chunks: shift, scale, gate
             ops.ln_modulate(s, chunk(m0, 0), chunk(m0, 1), out=n)
@@ -724,7 +796,7 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
                      epilogue=ops.FK_EPI_GATE_RES, res=s, gate=chunk(m0, 2))
 
 
-    def _blocks_by_kernel_calls_mx(self, ws, pk, mod, cs, S_txt):
+    def _blocks_by_kernel_calls_mx(self, ws, pk, mod, cs, S_txt, blocks=None):
         """MXFP8 blocks as one ctypes call per launch (FK_BLOCK_API=0): the launches of fk_double_block_fwd_mx /
         fk_single_block_fwd_mx in their order -- each block GEMM as quantize (activation) + gemm_mxfp8 -- hence their bits."""
         P, D = self.p, self.inner_dim
@@ -741,7 +813,9 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
             # the long-K launches (ff.net.2, proj_out) as the C entry points set them up: blocks.hip set_ws / mx_launch_controls
             ops.gemm_mxfp8_grouped(problems, epilogue=epilogue, splitk=MX_SPLITK and problems[0]["w"][0].shape[1] >= 6144)
 
-        for i, (blk, w) in enumerate(zip(pk.double, pk.mx_double)):
+        dr, sr = self._block_ranges(pk, blocks)
+        for i in dr:
+            blk, w = pk.double[i], pk.mx_double[i]
             p = f"transformer_blocks.{i}."
             mi, mt = blk.mod_img, blk.mod_txt
             ops.ln_modulate2(s, chunk(mt, 0), chunk(mt, 1), chunk(mi, 0), chunk(mi, 1), S_txt, out=n)
@@ -761,7 +835,8 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
             mm([dict(a=ws.ff[:, S_txt:], w=w.ff2, bias=P(p + "ff.net.2.bias"), out=h, res=h, gate=chunk(mi, 5)),
                 dict(a=ws.ff[:, :S_txt], w=w.ff2_ctx, bias=P(p + "ff_context.net.2.bias"), out=cx, res=cx, gate=chunk(mt, 5))],
                ops.FK_EPI_GATE_RES)
-        for i, (blk, w) in enumerate(zip(pk.single, pk.mx_single)):
+        for i in sr:
+            blk, w = pk.single[i], pk.mx_single[i]
             p = f"single_transformer_blocks.{i}."
             m0 = blk.mod
             ops.ln_modulate(s, chunk(m0, 0), chunk(m0, 1), out=n)
@@ -772,7 +847,7 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
             mm([dict(a=n, w=w.mlp, bias=P(p + "proj_mlp.bias"), out=ws.cat[:, :, D:])], ops.FK_EPI_GELU_TANH)
             mm([dict(a=ws.cat, w=w.out, bias=P(p + "proj_out.bias"), out=s, res=s, gate=chunk(m0, 2))], ops.FK_EPI_GATE_RES)
 
-    def _blocks_by_kernel_calls_mx_fused(self, ws, pk, mod, cs, B, S_txt):
+    def _blocks_by_kernel_calls_mx_fused(self, ws, pk, mod, cs, B, S_txt, blocks=None):
         """The fused MXFP8 schedule (FK_MX_FUSED_QUANT=1) as one ctypes call per launch: the launches of fk_double_block_fwd_mx /
         fk_single_block_fwd_mx with fk_mx_ws.fused set, in their order and on the same workspace layout -- n8 (img rows, then txt
         rows) in front, the block's consumer operand (o8 / ff8 / cat8) behind it.  The bf16 n, ff and cat[:, D:] are not written;
@@ -796,7 +871,9 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
         n8_img, n8_txt = streams(0, D)
         o8_img, o8_txt = streams(M * D, D)
         ff8_img, ff8_txt = streams(M * D, 4 * D)
-        for i, (blk, w) in enumerate(zip(pk.double, pk.mx_double)):
+        dr, sr = self._block_ranges(pk, blocks)
+        for i in dr:
+            blk, w = pk.double[i], pk.mx_double[i]
             p = f"transformer_blocks.{i}."
             mi, mt = blk.mod_img, blk.mod_txt
             ops.ln_modulate2_mxfp8(s, chunk(mt, 0), chunk(mt, 1), chunk(mi, 0), chunk(mi, 1), S_txt, out=n8_txt, out_b=n8_img)
@@ -828,7 +905,8 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
         n8 = region(0, M, D)
         cat8 = region(M * D, M, 5 * D)
         cat8_attn = (cat8[0][:, :D], cat8[1][:, :D // 32])
-        for i, (blk, w) in enumerate(zip(pk.single, pk.mx_single)):
+        for i in sr:
+            blk, w = pk.single[i], pk.mx_single[i]
             p = f"single_transformer_blocks.{i}."
             m0 = blk.mod
             ops.ln_modulate_mxfp8(s, chunk(m0, 0), chunk(m0, 1), out=n8)
@@ -895,7 +973,7 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
             self.__dict__["_block_structs"] = st
         return st
 
-    def _blocks_by_c_entry(self, ws, pk, mod, cs, B, S_txt, S_img, api):
+    def _blocks_by_c_entry(self, ws, pk, mod, cs, B, S_txt, S_img, api, blocks=None):
         """The same launches through the block-level C entry points: argument structs built once per (weights, workspace)
         and re-used; per forward only the modulation pointer changes."""
         import ctypes
@@ -927,25 +1005,32 @@ class HipFluxTransformer2DModel(LoraMixin, ParamTreeMixin, nn.Module):
         c.gemm_variant_used = ctypes.pointer(ops._variant_slot())
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         mp, mbs = ctypes.c_void_p(mod.data_ptr()), mod.stride(0)
+        dr, sr = self._block_ranges(pk, blocks)
+
+        def at(arr, r):      # pointer to the range's first struct: the array itself (today's argument) for a range from 0
+            return arr if r.start == 0 or not len(r) else ctypes.pointer(arr[r.start])
+
         if pk.format == "mxfp8":
             sx, mxw = self._block_mx_structs(pk), bw[3]
             if api >= 2:
-                libfk.check(lib.fk_mmdit_blocks_fwd_mx(ctypes.byref(c), ctypes.byref(mxw), st.dbl, sx.dbl, st.nd, st.sgl, sx.sgl,
-                                                       st.ns, mp, mbs, stream), "fk_mmdit_blocks_fwd_mx")
+                libfk.check(lib.fk_mmdit_blocks_fwd_mx(ctypes.byref(c), ctypes.byref(mxw), at(st.dbl, dr), at(sx.dbl, dr), len(dr),
+                                                       at(st.sgl, sr), at(sx.sgl, sr), len(sr), mp, mbs, stream),
+                            "fk_mmdit_blocks_fwd_mx")
                 return
-            for i in range(st.nd):
+            for i in dr:
                 libfk.check(lib.fk_double_block_fwd_mx(ctypes.byref(c), ctypes.byref(mxw), ctypes.byref(st.dbl[i]),
                                                        ctypes.byref(sx.dbl[i]), mp, mbs, stream), "fk_double_block_fwd_mx")
-            for i in range(st.ns):
+            for i in sr:
                 libfk.check(lib.fk_single_block_fwd_mx(ctypes.byref(c), ctypes.byref(mxw), ctypes.byref(st.sgl[i]),
                                                        ctypes.byref(sx.sgl[i]), mp, mbs, stream), "fk_single_block_fwd_mx")
             return
         if api >= 2:
-            libfk.check(lib.fk_mmdit_blocks_fwd(ctypes.byref(c), st.dbl, st.nd, st.sgl, st.ns, mp, mbs, stream), "fk_mmdit_blocks_fwd")
+            libfk.check(lib.fk_mmdit_blocks_fwd(ctypes.byref(c), at(st.dbl, dr), len(dr), at(st.sgl, sr), len(sr), mp, mbs, stream),
+                        "fk_mmdit_blocks_fwd")
             return
-        for i in range(st.nd):
+        for i in dr:
             libfk.check(lib.fk_double_block_fwd(ctypes.byref(c), ctypes.byref(st.dbl[i]), mp, mbs, stream), "fk_double_block_fwd")
-        for i in range(st.ns):
+        for i in sr:
             libfk.check(lib.fk_single_block_fwd(ctypes.byref(c), ctypes.byref(st.sgl[i]), mp, mbs, stream), "fk_single_block_fwd")
 
     # The reference training code calls this on the denoiser (train_denoiser.py:486) because its 80 GB GPUs cannot hold

@@ -721,6 +721,14 @@ int fk_residual_save_bf16(const void* h_out, fk_rows ro, const void* h0, fk_rows
 /* out = bf16(float(h0) + float(r)).  out may BE h0 (same pointer and strides); any other overlap of the three is FK_EINVAL. */
 int fk_residual_apply_bf16(const void* h0, fk_rows r0, const void* r, fk_rows rr, void* out, fk_rows ro, int64_t M, int32_t D,
                            int32_t is_bf16, fk_stream_t stream);
+/* The first-block measure of the step cache as one pass over three bf16 views: r = bf16(float(h1) - float(h0)), exactly
+ * fk_residual_save_bf16's value, written to r_out when r_out is non-NULL (rr is ignored otherwise), and out[0] = sum |float(r) -
+ * float(ref)|, out[1] = sum |float(ref)| with fk_absdiff_sums_bf16's decomposition, summation order and workspace: out holds the
+ * bits of fk_residual_save_bf16(h1, h0, r) followed by fk_absdiff_sums_bf16(r, ref).  The inputs may overlap one another; r_out
+ * overlapping an input, or r_out rows that overlap each other, is FK_EINVAL, as is everything fk_absdiff_sums_bf16 refuses. */
+int fk_residual_absdiff_sums_bf16(const void* h1, fk_rows r1, const void* h0, fk_rows r0, const void* ref, fk_rows rf, void* r_out,
+                                  fk_rows rr, int64_t M, int32_t D, int32_t is_bf16, float* out, float* ws, int64_t ws_floats,
+                                  fk_stream_t stream);
 /* dst[r, c] = src[c, r] for a [R, C] bf16 matrix with leading dimensions lds/ldd (elements);
  * batched over `batch` with the given batch strides. */
 int fk_transpose_bf16(const void* src, int64_t lds, int64_t src_batch_stride, void* dst, int64_t ldd,
