@@ -1,5 +1,6 @@
 // Small HBM-/latency-bound kernels around the MMDiT forward and the Euler update (K6, K8).
 #include "fk_common.h"
+#include "step_common.h"
 
 namespace {
 
@@ -74,14 +75,8 @@ __global__ __launch_bounds__(256) void euler_kernel(bf16_t* x, int64_t x_bs, con
   }
 }
 
-// keep-region value of a masked edit (FlowMatchEulerDiscreteScheduler.scale_noise on bf16 tensors): the preserved picture
-// re-noised to the level the repainted region has after the step.  sb = bf16(sigma), omsb = bf16(1 - sb); shared by the
-// inpaint step and fk_scale_noise_bf16, so the start tokens and the per-step keep values cannot drift apart.
-FK_DEV float keep_f(float sb, float omsb, float noise, float x0) {
-  return round_bf(round_bf(sb * noise) + round_bf(omsb * x0));
-}
-
-// Euler step + keep-region blend.  One 8-vector spans two channels of one token (C % 8 == 0), and element j of a token is
+// Euler step + keep-region blend (keep_f, ew_grid and host_round_bf: step_common.h, shared with solver_step.hip).
+// One 8-vector spans two channels of one token (C % 8 == 0), and element j of a token is
 // sub-pixel j % 4, so the vector's mask pattern is the token's four values twice: one 8-byte load per vector.
 __global__ __launch_bounds__(256) void euler_inpaint_kernel(bf16_t* x, int64_t x_bs, const bf16_t* v, int64_t v_bs,
                                                             const bf16_t* x0, int64_t x0_bs, const bf16_t* noise,
@@ -208,21 +203,6 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* x, bf16_
       }
     }
   }
-}
-
-inline int ew_grid(int64_t nvec) {
-  int64_t g = (nvec + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
-
-// float -> bf16 -> float on the host (round-to-nearest-even): a 0-dim fp32 tensor multiplied into a bf16 tensor is cast first
-inline float host_round_bf(float f) {
-  uint32_t u;
-  __builtin_memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  u &= 0xffff0000u;
-  __builtin_memcpy(&f, &u, 4);
-  return f;
 }
 
 }  // namespace

@@ -124,8 +124,9 @@ def build_parser():
                    help="mxfp8 only: let the long-K block GEMMs run as split-K pairs (FK_MX_SPLITK=1; default off)")
     p.add_argument("--mx_fused_attn", action="store_true",
                    help="mxfp8 with FK_MX_FUSED_QUANT=1 only: the attention emits MXFP8 itself (FK_MX_FUSED_ATTN=1; default off)")
-    from ..serve.cli import add_step_cache_arguments
+    from ..serve.cli import add_solver_argument, add_step_cache_arguments
     add_step_cache_arguments(p)
+    add_solver_argument(p)
     from ..lora import add_cli_arguments
     add_cli_arguments(p)
     return p
@@ -172,7 +173,8 @@ def main(args):
     if getattr(args, "mx_fused_attn", False):
         cli.transformer.set_mx_fused_attn(True)
     pipe, tokenizers, text_encoders = cli.load_pipe(args.model_path, args.flux_path, device,
-                                                    weight_format=getattr(args, "weight_format", "bf16"))
+                                                    weight_format=getattr(args, "weight_format", "bf16"),
+                                                    **cli.solver_kwargs(args))
     cli.lora.load_cli_adapters(pipe, getattr(args, "lora", None))
     if args.t5_only:
         def edit_fn(prompt, image_path):

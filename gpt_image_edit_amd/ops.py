@@ -753,6 +753,31 @@ def euler_inpaint_step(x, v, s_tgt, dsigma, sigma_next, x0, noise, mask=None):
     return x
 
 
+def ab2_step(x, v, hist, s_tgt, c_v, c_h, use_hist, sigma_next=0.0, x0=None, noise=None, mask=None):
+    """In place on x[:, :s_tgt]: the second-order multistep update bf16(x + c_v * v [+ c_h * hist]), summed in fp32 with the
+    coefficients as the fp32 numbers they are, and hist <- v[:, :s_tgt] in the same pass (include/fk.h: fk_ab2_step_bf16).
+    ``use_hist`` 0: a first-order step that does not read ``hist`` (the first step, whose history is whatever the buffer held).
+    ``mask``: as in :func:`euler_inpaint_step`, with this update where it is 1; None = ones, and ``x0`` / ``noise`` /
+    ``sigma_next`` are not used."""
+    _need_cuda(x, v, hist, x0, noise, mask)
+    B, _, C = x.shape
+    for name, t in (("x", x), ("v", v), ("hist", hist)) + ((("x0", x0), ("noise", noise)) if mask is not None else ()):
+        _token_rows(name, t, B, s_tgt, C)
+    m_bs = 0
+    if mask is not None:
+        if mask.dtype != BF16 or mask.dim() != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (s_tgt, 4) \
+                or not mask.is_contiguous():
+            raise ValueError(f"mask must be contiguous bf16 [1 or {B}, {s_tgt}, 4], got {tuple(mask.shape)} {mask.dtype}")
+        m_bs = mask.stride(0) if mask.shape[0] == B and B > 1 else 0
+    else:
+        x0 = noise = None
+    libfk.check(libfk.load().fk_ab2_step_bf16(
+        _ptr(x), x.stride(0), _ptr(v), v.stride(0), _ptr(hist), hist.stride(0), _ptr(x0), 0 if x0 is None else x0.stride(0),
+        _ptr(noise), 0 if noise is None else noise.stride(0), _ptr(mask), m_bs, B, s_tgt, C, float(c_v), float(c_h),
+        int(use_hist), float(sigma_next), _stream()), "fk_ab2_step_bf16")
+    return x
+
+
 def scale_noise(x0, noise, sigma, out=None):
     """bf16(bf16(sigma) * noise) + bf16(1 - bf16(sigma)) * x0 with one rounding per bf16 tensor op
     (FlowMatchEulerDiscreteScheduler.scale_noise): the start tokens of an edit that begins inside the schedule."""

@@ -444,6 +444,12 @@ class FluxKontextPipeline:
             ops.scale_noise(x0, noise, float(self.scheduler._sigmas_host[t_start]), out=tokens[:, :S_tgt])
         steps = range(t_start, t_start + len(timesteps))
         model_tokens = torch.empty((model_batch, *tokens.shape[1:]), device=device, dtype=BF16) if do_true_cfg else tokens
+        # a second-order multistep scheduler: every step's (c_v, c_h, use_hist) and the previous velocity's buffer, once per call
+        solver_order = getattr(self.scheduler, "solver_order", 1)
+        if solver_order not in (1, 2):
+            raise NotImplementedError(f"the denoise loop has a first- and a second-order step, not solver_order={solver_order}")
+        ab2 = [self.scheduler.coefficients(i, i > t_start) for i in steps] if solver_order == 2 else None
+        hist = torch.empty((batch_size, S_tgt, tokens.shape[2]), device=device, dtype=BF16) if ab2 is not None else None
 
         # 6. denoising loop: no allocation, no host sync
         L = SimpleNamespace(tokens=tokens, model_tokens=model_tokens, t_model=t_model, guidance=guidance, pooled=model_pooled,
@@ -454,7 +460,7 @@ class FluxKontextPipeline:
                             sigma_next=[self.scheduler.sigma_next(i) for i in steps] if inpaint else [],
                             # without a mask the fused step is the Euler update alone and reads neither x0 nor noise
                             x0=x0 if mask is not None else None, noise=noise if mask is not None else None, mask=mask,
-                            step_cache=step_cache, cache_state=None)
+                            step_cache=step_cache, cache_state=None, ab2=ab2, hist=hist)
         graphable = self.use_graph and callback_on_step_end is None and not joint_attention_kwargs and not self._interrupt
         if graphable and step_cache is not None and step_cache.adaptive:
             # the adaptive rule needs the step's two sums on the host before it can choose the step's launches
@@ -508,7 +514,11 @@ class FluxKontextPipeline:
                 noise_pred = self.transformer.step_cache_end(st, compute)
             if L.do_true_cfg:
                 noise_pred = ops.true_cfg(noise_pred[:B], noise_pred[B:], L.true_cfg_scale)
-            if L.inpaint:   # Euler update where the mask is 1, the preserved picture at sigma[i+1] where it is 0
+            if L.ab2 is not None:   # second-order multistep update (and hist <- this velocity), blended like the Euler one
+                c_v, c_h, use_hist = L.ab2[i]
+                ops.ab2_step(tokens, noise_pred, L.hist, L.S_tgt, c_v, c_h, use_hist,
+                             L.sigma_next[i] if L.inpaint else 0.0, L.x0, L.noise, L.mask)
+            elif L.inpaint:   # Euler update where the mask is 1, the preserved picture at sigma[i+1] where it is 0
                 ops.euler_inpaint_step(tokens, noise_pred, L.S_tgt, L.dsigma[i], L.sigma_next[i], L.x0, L.noise, L.mask)
             else:
                 ops.euler_step(tokens, noise_pred, L.S_tgt, L.dsigma[i])
@@ -536,11 +546,8 @@ class FluxKontextPipeline:
 
     _GRAPH_INPUTS = ("tokens", "t_model", "guidance", "pooled", "embeds", "text_ids", "latent_ids", "x0", "noise", "mask")
 
-    def _denoise_graph(self, L):
-        """The same work as ONE graph launch.  The captured kernels read and write fixed buffers, so the call's tensors
-        are copied into the graph's own (a few MB); everything the host decides during an eager pass -- launch plans,
-        cached RoPE tables, the rows of the prepared conditioning, the Euler step sizes -- is frozen into the graph and
-        therefore part of its key.  Returns the token buffer the graph updates."""
+    def _graph_key(self, L):
+        """Everything a captured loop freezes: a call whose key differs captures anew."""
         # weights rewritten in place since the last forward (load_state_dict, a LoRA merge, an optimiser step): packed() checks
         # the source parameters' version stamps, re-packs the fused copies if needed and bumps the serial the key carries --
         # a replay never mixes fresh unfused weights with stale fused ones
@@ -553,7 +560,17 @@ class FluxKontextPipeline:
                # their presence, the mask's batch form and the keep region's noise levels are frozen into the graph
                L.inpaint, None if L.mask is None else tuple(L.mask.shape), tuple(L.sigma_next),
                # step cache: which steps run the blocks, and which blocks a skipped step still runs, is frozen into the graph
-               None if L.step_cache is None else (L.step_cache.schedule, L.step_cache.measure))
+               None if L.step_cache is None else (L.step_cache.schedule, L.step_cache.measure),
+               # the solver: its order and every step's coefficients are frozen into the graph's step launches
+               1 if L.ab2 is None else 2, None if L.ab2 is None else tuple(L.ab2))
+        return key
+
+    def _denoise_graph(self, L):
+        """The same work as ONE graph launch.  The captured kernels read and write fixed buffers, so the call's tensors
+        are copied into the graph's own (a few MB); everything the host decides during an eager pass -- launch plans,
+        cached RoPE tables, the rows of the prepared conditioning, the Euler step sizes -- is frozen into the graph and
+        therefore part of its key.  Returns the token buffer the graph updates."""
+        key = self._graph_key(L)
         cur = torch.cuda.current_stream()
         if self._loop_graph is None or self._loop_graph[0] != key:
             self._loop_graph = None
@@ -562,6 +579,8 @@ class FluxKontextPipeline:
                 t = getattr(L, n)
                 setattr(G, n, None if t is None else t.clone())
             G.model_tokens = torch.empty_like(L.model_tokens) if L.do_true_cfg else G.tokens
+            if L.hist is not None:          # the previous velocity is the graph's own buffer, not an input: step 0 never reads it
+                G.hist = torch.empty_like(L.hist)
             if L.step_cache is not None:    # the cache state (h0, the residual) belongs to the graph's own buffers
                 G.cache_state = self.transformer.step_cache_state(measure=False, mode=L.step_cache.measure)
             side = torch.cuda.Stream(device=L.tokens.device)

@@ -7,6 +7,7 @@ Masked edits and ``strength`` (diffusers' inpaint pipeline of this model family)
 other than 0.
 The sigma schedule is host arithmetic in float32 (28 numbers); the update itself is
 ``fk_euler_step_bf16`` with the reference's rounding (bf16(dsigma) * v in bf16, sum in fp32 -> bf16).
+``FlowMatchMultistepScheduler`` is the opt-in second-order (Adams-Bashforth 2) rule on the same schedule: ``fk_ab2_step_bf16``.
 """
 import math
 
@@ -95,6 +96,61 @@ class FlowMatchEulerDiscreteScheduler:
         prev = sample.contiguous().clone()
         B, S, _ = prev.shape
         ops.euler_step(prev, model_output.contiguous(), S, self.dsigma(self._step_index))
+        self._step_index += 1
+        if not return_dict:
+            return (prev,)
+        return {"prev_sample": prev}
+
+
+class FlowMatchMultistepScheduler(FlowMatchEulerDiscreteScheduler):
+    """Second-order Adams-Bashforth rule on the parent's (non-uniform) sigma grid: one model call per step, the previous
+    velocity as the only state.  With d_i = sigma[i+1] - sigma[i] and r = d_i / d_{i-1} the update is
+    ``x + d_i (1 + r/2) v_i - d_i (r/2) v_{i-1}``; the first executed step (no history yet) and, with ``lower_order_final``,
+    the last step of the schedule are first-order steps ``x + d_i v_i``.  The sum is formed in float32 with float32
+    coefficients and rounded to bf16 once (``fk_ab2_step_bf16``) -- unlike the parent's step, which mirrors the reference's
+    bf16 scheduler arithmetic.  Timesteps, sigmas, ``scale_noise`` and the begin index are the parent's."""
+    order = 1               # model calls per step
+    solver_order = 2
+
+    def __init__(self, lower_order_final=True, **config):
+        super().__init__(**config)
+        self.lower_order_final = bool(lower_order_final)
+        self._hist = None
+
+    def set_timesteps(self, num_inference_steps=None, device=None, sigmas=None, mu=None):
+        super().set_timesteps(num_inference_steps=num_inference_steps, device=device, sigmas=sigmas, mu=mu)
+        self._hist = None
+        if not (np.diff(self._sigmas_host.astype(np.float64)) < 0).all():     # a NaN fails this too
+            self.timesteps = self.sigmas = self._sigmas_host = None
+            raise ValueError("the multistep rule divides by the step size: the sigmas (with the final 0) must be strictly "
+                             "decreasing")
+
+    def coefficients(self, i, have_history):
+        """(c_v, c_h, use_hist) of step ``i``: the float32 values ``fk_ab2_step_bf16`` receives, computed in float64 from the
+        float32 sigmas.  ``have_history``: a velocity of step ``i - 1`` exists (False at the first executed step, which sits at
+        the begin index when the loop starts inside the schedule; step 0 has no predecessor whatever is passed)."""
+        s = self._sigmas_host.astype(np.float64)
+        d = s[i + 1] - s[i]
+        last = i == len(s) - 2
+        if not have_history or i == 0 or (last and self.lower_order_final):
+            return float(np.float32(d)), 0.0, 0
+        r = d / (s[i] - s[i - 1])
+        return float(np.float32(d * (1 + r / 2))), float(np.float32(-d * r / 2)), 1
+
+    def step(self, model_output, timestep, sample, return_dict=True, **unused):
+        """The rule out of place, for callers that drive the scheduler themselves; the history tensor is allocated at the
+        first step of a run and dropped by ``set_timesteps``."""
+        first = self._step_index is None
+        if first:
+            self._init_step_index(timestep)
+        if model_output.dtype != torch.bfloat16 or sample.dtype != torch.bfloat16:
+            raise TypeError("the HIP scheduler step works on bf16 latents")
+        prev = sample.contiguous().clone()
+        B, S, _ = prev.shape
+        if first or self._hist is None or self._hist.shape != prev.shape or self._hist.device != prev.device:
+            self._hist, first = torch.empty_like(prev), True
+        c_v, c_h, use_hist = self.coefficients(self._step_index, not first)
+        ops.ab2_step(prev, model_output.contiguous(), self._hist, S, c_v, c_h, use_hist)
         self._step_index += 1
         if not return_dict:
             return (prev,)

@@ -20,7 +20,7 @@ import torch
 from .. import checkpoint, flux_spec, lora
 from ..anyres_util import dynamic_resize
 from ..pipeline import FluxKontextPipeline
-from ..scheduler import FlowMatchEulerDiscreteScheduler
+from ..scheduler import FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler
 from .. import transformer
 from ..transformer import HipFluxTransformer2DModel
 from ..vae import HipAutoencoderKL
@@ -29,14 +29,30 @@ seed = 42  # cli.py:20-26 seeds everything with 42 and draws the edit's noise fr
 generate_image_temp = "./generate_image_{}.png"
 
 
-def load_pipe(denoiser, flux_path, device, weight_format="bf16"):
+SOLVERS = {"euler": FlowMatchEulerDiscreteScheduler, "ab2": FlowMatchMultistepScheduler}
+
+
+def add_solver_argument(parser):
+    parser.add_argument("--solver", choices=tuple(SOLVERS), default="euler",
+                        help="integrator of the denoise loop: euler -- the reference's first-order step; ab2 -- second-order "
+                             "Adams-Bashforth on the same sigma schedule (one model call per step, fp32 sum, one bf16 rounding)")
+
+
+def solver_kwargs(args):
+    """``--solver`` as ``load_pipe``'s ``solver`` (nothing for the default: the call ``load_pipe`` always got)."""
+    solver = getattr(args, "solver", None) or "euler"
+    return {} if solver == "euler" else {"solver": solver}
+
+
+def load_pipe(denoiser, flux_path, device, weight_format="bf16", solver="euler"):
     """``FluxKontextPipeline.from_pretrained(flux_path, transformer=denoiser, torch_dtype=bf16).to(device)``.
 
     ``denoiser``: a ``HipFluxTransformer2DModel``, or a checkpoint directory (a UniWorld model directory with
     ``denoise_tower.denoiser.*`` keys, cli.py:127, or a diffusers FLUX directory), or None = ``flux_path``'s own
     transformer.  Returns (pipe, tokenizers, text_encoders) like the reference; the T5/CLIP encoders are loaded
     with ``transformers`` when ``flux_path`` holds them, else the two lists contain None.  ``weight_format``: "bf16" or
-    "mxfp8" (``HipFluxTransformer2DModel.set_weight_format``: opt-in MXFP8 block GEMMs, inference only)."""
+    "mxfp8" (``HipFluxTransformer2DModel.set_weight_format``: opt-in MXFP8 block GEMMs, inference only).  ``solver``: "euler"
+    or "ab2" -- the scheduler class the pipeline is built with (``SOLVERS``)."""
     if not isinstance(denoiser, HipFluxTransformer2DModel):
         src = denoiser or flux_path
         cfg = checkpoint.flux_transformer_config(flux_path) if os.path.isdir(os.path.join(flux_path, "transformer")) else None
@@ -46,7 +62,7 @@ def load_pipe(denoiser, flux_path, device, weight_format="bf16"):
     denoiser.set_weight_format(weight_format)
     vae = HipAutoencoderKL(device=device)
     checkpoint.load_vae(vae, flux_path)
-    sched = FlowMatchEulerDiscreteScheduler(**checkpoint.scheduler_config(flux_path))
+    sched = SOLVERS[solver](**checkpoint.scheduler_config(flux_path))
     tokenizers, text_encoders = [None, None], [None, None]
     try:  # reused as-is; absent offline
         from transformers import CLIPTextModel, CLIPTokenizer, T5EncoderModel, T5TokenizerFast
@@ -222,6 +238,7 @@ def build_parser():
                         help="in (0, 1]: below 1 the edit starts from the re-noised input image instead of from noise and "
                              "runs the last F of the steps (with --prompt_embeds / --t5_only)")
     add_step_cache_arguments(parser)
+    add_solver_argument(parser)
     lora.add_cli_arguments(parser)
     return parser
 
@@ -236,7 +253,8 @@ def main(args):
         raise SystemExit("--mask / --strength go with --prompt_embeds or --t5_only")
     step_cache_kwargs(args)      # a bad threshold / schedule / coefficient list fails before the weights load
     pipe, tokenizers, text_encoders = load_pipe(args.model_path, args.flux_path, device,
-                                                weight_format=getattr(args, "weight_format", "bf16"))
+                                                weight_format=getattr(args, "weight_format", "bf16"),
+                                                **solver_kwargs(args))
     lora.load_cli_adapters(pipe, getattr(args, "lora", None))
     if args.prompt_embeds:
         blob = torch.load(args.prompt_embeds, map_location="cpu", weights_only=True)

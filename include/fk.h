@@ -700,6 +700,23 @@ int fk_euler_inpaint_step_bf16(void* x, int64_t x_batch_stride, const void* v, i
  * (the `keep` of fk_euler_inpaint_step_bf16, one device function). */
 int fk_scale_noise_bf16(const void* x0, int64_t x0_batch_stride, const void* noise, int64_t noise_batch_stride, void* out,
                         int64_t out_batch_stride, int32_t B, int32_t S_tgt, int32_t C, float sigma, fk_stream_t stream);
+/* Second-order multistep (Adams-Bashforth 2) step of the denoise loop on a non-uniform sigma grid (csrc/solver_step.hip;
+ * scheduler.py: FlowMatchMultistepScheduler.coefficients), in place on rows s < S_tgt of x.  Per element, in fp32 with every
+ * product and every sum rounded once (never an fma), and ONE rounding to bf16:
+ *   s = x + c_v * v;   if (use_hist) s = s + c_h * hist;   p = bf16(s)
+ * c_v and c_h are used as the fp32 numbers they are (not rounded to bf16 as fk_euler_step_bf16 rounds dsigma).  The same pass
+ * stores hist <- v; every element's hist is read (use_hist == 1) before it is written, and with use_hist == 0 hist is never
+ * read (it may hold anything) and still written.  hist: [B, S_tgt, C] rows at hist_batch_stride, a buffer of its own.
+ * mask NULL: x = p; x0, noise and sigma_next are not read.  With a mask (the layout of fk_euler_inpaint_step_bf16):
+ *   x = bf16(bf16(bf16(1 - mask[j % 4]) * keep) + bf16(mask[j % 4] * p)),  keep as in fk_euler_inpaint_step_bf16
+ * FK_EINVAL, nothing launched: x, v or hist NULL, hist == v or hist == x, B, S_tgt or C < 1, C % 8 != 0, a pointer or batch
+ * stride that is not 16-byte aligned (the mask and its stride: 8 bytes), use_hist outside {0, 1}, a mask without x0 and noise. */
+int fk_ab2_step_bf16(void* x, int64_t x_batch_stride, const void* v, int64_t v_batch_stride,
+                     void* hist, int64_t hist_batch_stride,
+                     const void* x0, int64_t x0_batch_stride, const void* noise, int64_t noise_batch_stride,
+                     const void* mask, int64_t mask_batch_stride,
+                     int32_t B, int32_t S_tgt, int32_t C, float c_v, float c_h, int32_t use_hist,
+                     float sigma_next, fk_stream_t stream);
 /* ---- step cache: residual caching across denoise steps (csrc/step_cache.hip; gpt_image_edit_amd/step_cache.py) ----
  * All views are bf16 [B, R, D] with contiguous rows, M = B * R rows addressed through fk_rows (strides in elements, >= D and
  * >= 0), e.g. the image part n[:, S_txt:] of a joint buffer.  is_bf16 states the type of the caller's tensors (as fk_sumsq's g_is_bf16
