@@ -204,7 +204,8 @@ def main(args):
             out = pipe(image=cli.prepare_condition_pixels(image_paths), prompt_embeds=prompt_embeds,
                        pooled_prompt_embeds=pooled, height=gen_h, width=gen_w, num_inference_steps=args.num_inference_steps,
                        guidance_scale=args.guidance_scale, num_images_per_prompt=args.num_images_per_prompt,
-                       **cli.step_cache_kwargs(args), **cli.lora_kwargs(args))
+                       **cli.step_cache_kwargs(args), **cli.lora_kwargs(args),
+                       **cli.latent_state_kwargs(args))
             return out.images[0], out.latents[:1]
     res = run(args, edit_fn, rank, world)
     print(f"[rank {rank}/{world}] edited {len(res['done'])}, skipped {len(res['skipped'])} existing", flush=True)

@@ -207,6 +207,8 @@ SIGNATURES = {
     "fk_scale_noise_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "fk_ab2_step_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32,
                                  c_f32, c_f32, c_i32, c_f32, c_vp]),
+    "fk_solver_step_f32": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                   c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_i32, c_f32, c_vp]),
     "fk_absdiff_ws_floats": (c_i64, []),
     "fk_absdiff_sums_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "fk_residual_absdiff_sums_bf16": (c_i32, [c_vp, Rows, c_vp, Rows, c_vp, Rows, c_vp, Rows, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64,

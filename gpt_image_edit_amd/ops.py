@@ -778,6 +778,36 @@ def ab2_step(x, v, hist, s_tgt, c_v, c_h, use_hist, sigma_next=0.0, x0=None, noi
     return x
 
 
+def solver_step_f32(state, x, v, s_tgt, c_v, c_h=0.0, use_hist=0, load_state=1, hist=None, sigma_next=0.0, x0=None, noise=None,
+                    mask=None):
+    """The loop's step on a float32 latent state, in place on ``state`` (fp32 [B, s_tgt, C]) and on x[:, :s_tgt], which receives
+    the state's one rounding to bf16 (include/fk.h: fk_solver_step_f32): state + c_v * v [+ c_h * hist] in float32, from
+    float(x) instead of ``state`` when ``load_state`` is 0 (the first step: ``state`` is then not read).  Euler: ``use_hist`` 0,
+    ``hist`` None, ``c_v`` the unrounded float32 step size; AB2: :func:`ab2_step`'s coefficients and ``hist``, which receives
+    v[:, :s_tgt] in the same pass.  ``mask``: as in :func:`euler_inpaint_step`, blended in float32; None = ones."""
+    _need_cuda(state, x, v, hist, x0, noise, mask)
+    B, _, C = x.shape
+    for name, t in (("x", x), ("v", v)) + ((("hist", hist),) if hist is not None else ()) + \
+            ((("x0", x0), ("noise", noise)) if mask is not None else ()):
+        _token_rows(name, t, B, s_tgt, C)
+    if state.dtype != torch.float32 or tuple(state.shape) != (B, s_tgt, C) or state.stride(2) != 1 or state.stride(1) != C:
+        raise ValueError(f"state must be fp32 [{B}, {s_tgt}, {C}] with contiguous rows, got {tuple(state.shape)} {state.dtype}")
+    m_bs = 0
+    if mask is not None:
+        if mask.dtype != BF16 or mask.dim() != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (s_tgt, 4) \
+                or not mask.is_contiguous():
+            raise ValueError(f"mask must be contiguous bf16 [1 or {B}, {s_tgt}, 4], got {tuple(mask.shape)} {mask.dtype}")
+        m_bs = mask.stride(0) if mask.shape[0] == B and B > 1 else 0
+    else:
+        x0 = noise = None
+    libfk.check(libfk.load().fk_solver_step_f32(
+        _ptr(state), state.stride(0), _ptr(x), x.stride(0), _ptr(v), v.stride(0), _ptr(hist),
+        0 if hist is None else hist.stride(0), _ptr(x0), 0 if x0 is None else x0.stride(0), _ptr(noise),
+        0 if noise is None else noise.stride(0), _ptr(mask), m_bs, B, s_tgt, C, float(c_v), float(c_h), int(use_hist),
+        int(load_state), float(sigma_next), _stream()), "fk_solver_step_f32")
+    return x
+
+
 def scale_noise(x0, noise, sigma, out=None):
     """bf16(bf16(sigma) * noise) + bf16(1 - bf16(sigma)) * x0 with one rounding per bf16 tensor op
     (FlowMatchEulerDiscreteScheduler.scale_noise): the start tokens of an edit that begins inside the schedule."""

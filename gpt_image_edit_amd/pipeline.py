@@ -303,7 +303,8 @@ class FluxKontextPipeline:
                  pooled_prompt_embeds=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None,
                  output_type="pil", return_dict=True, joint_attention_kwargs=None, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=("latents",), max_sequence_length=512,
-                 max_area=1024 ** 2, _auto_resize=True, mask_image=None, strength=1.0, init_image=None, step_cache=None):
+                 max_area=1024 ** 2, _auto_resize=True, mask_image=None, strength=1.0, init_image=None, step_cache=None,
+                 latent_state="bf16"):
         """``mask_image`` / ``strength`` / ``init_image`` (diffusers' ``FluxKontextInpaintPipeline``): repaint only where the
         mask is 1 and keep ``init_image`` (default: ``image``, resized to the target size) elsewhere; ``strength`` < 1 starts
         the loop inside the schedule from the re-noised ``init_image`` instead of from noise.  ``image`` stays the Kontext
@@ -315,8 +316,15 @@ class FluxKontextPipeline:
         ``StepCache(..., measure="first_block")`` runs block 0 at every step, measures what it added to the image stream and
         skips only the blocks behind it.  ``None`` is today's call, launch for launch.
 
+        ``latent_state``: "bf16" is today's call, launch for launch -- the latents are rounded to bf16 at every step, as the
+        reference's loop rounds them.  "fp32" carries them in a float32 buffer of the call's own ([B, S_tgt, 64], seeded from
+        the bf16 start tokens) through ``fk_solver_step_f32``, for whichever scheduler is installed; the model still reads the
+        bf16 token rows, which receive the state's one rounding per step, and the returned latents are those rows.
+
         ``joint_attention_kwargs["scale"]`` (default 1.0): the call scale of the loaded LoRA adapters (``load_lora_weights``)."""
         device = self.device
+        if latent_state not in ("bf16", "fp32"):
+            raise ValueError(f'`latent_state` is "bf16" or "fp32", not {latent_state!r}')
         if joint_attention_kwargs and "scale" in joint_attention_kwargs:
             # the LoRA call scale: merged into the weights before the loop and left there until another scale is asked for;
             # without adapters it is ignored.  It is no argument of the transformer call, so it leaves the kwargs here
@@ -450,6 +458,9 @@ class FluxKontextPipeline:
             raise NotImplementedError(f"the denoise loop has a first- and a second-order step, not solver_order={solver_order}")
         ab2 = [self.scheduler.coefficients(i, i > t_start) for i in steps] if solver_order == 2 else None
         hist = torch.empty((batch_size, S_tgt, tokens.shape[2]), device=device, dtype=BF16) if ab2 is not None else None
+        # a float32 latent state: one buffer per call, never an input -- the first executed step seeds it from the start tokens
+        state = torch.empty((batch_size, S_tgt, tokens.shape[2]), device=device, dtype=torch.float32) \
+            if latent_state == "fp32" else None
 
         # 6. denoising loop: no allocation, no host sync
         L = SimpleNamespace(tokens=tokens, model_tokens=model_tokens, t_model=t_model, guidance=guidance, pooled=model_pooled,
@@ -460,7 +471,7 @@ class FluxKontextPipeline:
                             sigma_next=[self.scheduler.sigma_next(i) for i in steps] if inpaint else [],
                             # without a mask the fused step is the Euler update alone and reads neither x0 nor noise
                             x0=x0 if mask is not None else None, noise=noise if mask is not None else None, mask=mask,
-                            step_cache=step_cache, cache_state=None, ab2=ab2, hist=hist)
+                            step_cache=step_cache, cache_state=None, ab2=ab2, hist=hist, latent_state=latent_state, state=state)
         graphable = self.use_graph and callback_on_step_end is None and not joint_attention_kwargs and not self._interrupt
         if graphable and step_cache is not None and step_cache.adaptive:
             # the adaptive rule needs the step's two sums on the host before it can choose the step's launches
@@ -495,6 +506,7 @@ class FluxKontextPipeline:
         if sc is not None:
             st = self._step_cache_state(L)
             sc.begin(len(L.dsigma))
+        seed = True     # float32 state: the next step widens the bf16 token rows instead of reading the state
         for i in range(len(L.dsigma)):
             if self._interrupt:
                 continue
@@ -514,7 +526,12 @@ class FluxKontextPipeline:
                 noise_pred = self.transformer.step_cache_end(st, compute)
             if L.do_true_cfg:
                 noise_pred = ops.true_cfg(noise_pred[:B], noise_pred[B:], L.true_cfg_scale)
-            if L.ab2 is not None:   # second-order multistep update (and hist <- this velocity), blended like the Euler one
+            if L.state is not None:   # either rule on the float32 state; the token rows receive its rounding to bf16
+                c_v, c_h, use_hist = L.ab2[i] if L.ab2 is not None else (L.dsigma[i], 0.0, 0)
+                ops.solver_step_f32(L.state, tokens, noise_pred, L.S_tgt, c_v, c_h, use_hist, 0 if seed else 1, L.hist,
+                                    L.sigma_next[i] if L.inpaint else 0.0, L.x0, L.noise, L.mask)
+                seed = False
+            elif L.ab2 is not None:   # second-order multistep update (and hist <- this velocity), blended like the Euler one
                 c_v, c_h, use_hist = L.ab2[i]
                 ops.ab2_step(tokens, noise_pred, L.hist, L.S_tgt, c_v, c_h, use_hist,
                              L.sigma_next[i] if L.inpaint else 0.0, L.x0, L.noise, L.mask)
@@ -526,6 +543,7 @@ class FluxKontextPipeline:
                 out = callback_on_step_end(self, i, timesteps[i], {"latents": tokens[:, :L.S_tgt]})
                 if out and "latents" in out:
                     tokens[:, :L.S_tgt].copy_(out["latents"])
+                    seed = True     # the callback's bf16 latents become the state at the next step
         if sc is not None:
             sc.block_passes = st.block_passes
 
@@ -561,6 +579,8 @@ class FluxKontextPipeline:
                L.inpaint, None if L.mask is None else tuple(L.mask.shape), tuple(L.sigma_next),
                # step cache: which steps run the blocks, and which blocks a skipped step still runs, is frozen into the graph
                None if L.step_cache is None else (L.step_cache.schedule, L.step_cache.measure),
+               # the latent state's type selects the step kernel
+               L.latent_state,
                # the solver: its order and every step's coefficients are frozen into the graph's step launches
                1 if L.ab2 is None else 2, None if L.ab2 is None else tuple(L.ab2))
         return key
@@ -581,6 +601,8 @@ class FluxKontextPipeline:
             G.model_tokens = torch.empty_like(L.model_tokens) if L.do_true_cfg else G.tokens
             if L.hist is not None:          # the previous velocity is the graph's own buffer, not an input: step 0 never reads it
                 G.hist = torch.empty_like(L.hist)
+            if L.state is not None:         # so is the float32 state: every replay's first step seeds it from the tokens
+                G.state = torch.empty_like(L.state)
             if L.step_cache is not None:    # the cache state (h0, the residual) belongs to the graph's own buffers
                 G.cache_state = self.transformer.step_cache_state(measure=False, mode=L.step_cache.measure)
             side = torch.cuda.Stream(device=L.tokens.device)

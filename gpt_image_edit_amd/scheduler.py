@@ -8,6 +8,8 @@ other than 0.
 The sigma schedule is host arithmetic in float32 (28 numbers); the update itself is
 ``fk_euler_step_bf16`` with the reference's rounding (bf16(dsigma) * v in bf16, sum in fp32 -> bf16).
 ``FlowMatchMultistepScheduler`` is the opt-in second-order (Adams-Bashforth 2) rule on the same schedule: ``fk_ab2_step_bf16``.
+The pipeline's ``latent_state="fp32"`` runs either rule on a float32 state (``fk_solver_step_f32``) with this module's ``dsigma``
+/ ``coefficients``; the ``step()`` methods here, the hand-driven out-of-place forms, stay bf16.
 """
 import math
 

@@ -36,12 +36,21 @@ def add_solver_argument(parser):
     parser.add_argument("--solver", choices=tuple(SOLVERS), default="euler",
                         help="integrator of the denoise loop: euler -- the reference's first-order step; ab2 -- second-order "
                              "Adams-Bashforth on the same sigma schedule (one model call per step, fp32 sum, one bf16 rounding)")
+    parser.add_argument("--latent_state", choices=("bf16", "fp32"), default="bf16",
+                        help="the loop's latents between steps: bf16 -- rounded at every step, as the reference's loop does; "
+                             "fp32 -- carried in a float32 buffer by either solver, the model still reads their bf16 rounding")
 
 
 def solver_kwargs(args):
     """``--solver`` as ``load_pipe``'s ``solver`` (nothing for the default: the call ``load_pipe`` always got)."""
     solver = getattr(args, "solver", None) or "euler"
     return {} if solver == "euler" else {"solver": solver}
+
+
+def latent_state_kwargs(args):
+    """``--latent_state`` as the pipeline's ``latent_state`` (nothing for the default: the call the pipeline always got)."""
+    state = getattr(args, "latent_state", None) or "bf16"
+    return {} if state == "bf16" else {"latent_state": state}
 
 
 def load_pipe(denoiser, flux_path, device, weight_format="bf16", solver="euler"):
@@ -173,6 +182,7 @@ def generate_image(pipe, prompt_embeds, pooled_prompt_embeds, history_image_path
         **inpaint_kwargs(args),
         **step_cache_kwargs(args),
         **lora_kwargs(args),
+        **latent_state_kwargs(args),
     ).images[0]
 
 
@@ -204,6 +214,7 @@ def run_t5_only(pipe, text_encoders, tokenizers, text, image1=None, image2=None,
         **inpaint_kwargs(args),
         **step_cache_kwargs(args),
         **lora_kwargs(args),
+        **latent_state_kwargs(args),
     ).images
 
 

@@ -717,6 +717,31 @@ int fk_ab2_step_bf16(void* x, int64_t x_batch_stride, const void* v, int64_t v_b
                      const void* mask, int64_t mask_batch_stride,
                      int32_t B, int32_t S_tgt, int32_t C, float c_v, float c_h, int32_t use_hist,
                      float sigma_next, fk_stream_t stream);
+/* The denoise loop's step on a float32 latent state (csrc/solver_step.hip), for the Euler and the AB2 rule alike: the state is
+ * carried unrounded from step to step in `state`, fp32 [B, S_tgt, C] rows at state_batch_stride, and rows s < S_tgt of the bf16
+ * token buffer x receive its rounding, the model's next input.  Per element, every product and every sum is ONE float32
+ * operation (never an fma), and the only rounding to bf16 is the one stored to x:
+ *   xs  = load_state ? state : float(x)          load_state == 0 (the first executed step, or the step after the caller
+ *                                                replaced the token rows) seeds the state from x: `state` is then NOT read
+ *                                                and may hold anything, NaN bits included
+ *   s   = xs + c_v * v;   if (use_hist) s = s + c_h * hist          (hist is not read when use_hist == 0)
+ *   mask NULL:   out = s                                            (x0, noise and sigma_next are not read)
+ *   with a mask: k   = sigma_next * noise + om * x0,  om = float32(1 - sigma_next) formed once on the host
+ *                out = (1 - mask[j % 4]) * k + mask[j % 4] * s      (float32: sigma_next, k and the blend are NOT rounded to bf16)
+ *   state <- out;   x <- bf16(out);   hist <- v in the same pass when hist is non-NULL
+ * A mask value of 1 gives s bit for bit and 0 gives k, which is x0 exactly when sigma_next == 0.  Euler: use_hist = 0, hist NULL,
+ * c_v = sigma[i+1] - sigma[i] as the float32 difference it is (fk_euler_step_bf16 rounds it to bf16; this entry does not).  Every
+ * element's hist is read (use_hist == 1) before it is written.  mask, x0, noise: the layouts of fk_euler_inpaint_step_bf16.
+ * FK_EINVAL, nothing launched: state, x or v NULL, B, S_tgt or C < 1, C % 8 != 0, a bf16 pointer or batch stride that is not
+ * 16-byte aligned (the mask and its stride: 8 bytes; the state: a 16-byte aligned pointer and a stride that is a multiple of 4
+ * elements), use_hist or load_state outside {0, 1}, use_hist == 1 with hist NULL, hist == x, v or state, state == x, a mask
+ * without x0 and noise. */
+int fk_solver_step_f32(float* state, int64_t state_batch_stride, void* x, int64_t x_batch_stride,
+                       const void* v, int64_t v_batch_stride, void* hist, int64_t hist_batch_stride,
+                       const void* x0, int64_t x0_batch_stride, const void* noise, int64_t noise_batch_stride,
+                       const void* mask, int64_t mask_batch_stride,
+                       int32_t B, int32_t S_tgt, int32_t C, float c_v, float c_h, int32_t use_hist, int32_t load_state,
+                       float sigma_next, fk_stream_t stream);
 /* ---- step cache: residual caching across denoise steps (csrc/step_cache.hip; gpt_image_edit_amd/step_cache.py) ----
  * All views are bf16 [B, R, D] with contiguous rows, M = B * R rows addressed through fk_rows (strides in elements, >= D and
  * >= 0), e.g. the image part n[:, S_txt:] of a joint buffer.  is_bf16 states the type of the caller's tensors (as fk_sumsq's g_is_bf16
