@@ -1,6 +1,6 @@
-// Small HBM-/latency-bound kernels around the MMDiT forward and the Euler update (K6, K8).
+// Small HBM-/latency-bound kernels around the MMDiT forward (K6, K8).  The denoise loop's step kernels are in solver_step.hip.
 #include "fk_common.h"
-#include "step_common.h"
+#include "step_common.h"   // ew_grid
 
 namespace {
 
@@ -54,76 +54,6 @@ __global__ void timestep_proj_kernel(const void* v, int v_is_fp32, const float* 
   const float ang = __fmul_rn(t, freqs[k]);
   out[(int64_t)b * 256 + k] = f2bf(cosf(ang));
   out[(int64_t)b * 256 + 128 + k] = f2bf(sinf(ang));
-}
-
-__global__ __launch_bounds__(256) void euler_kernel(bf16_t* x, int64_t x_bs, const bf16_t* v, int64_t v_bs,
-                                                    int S_tgt, int C, float dsig_bf) {
-  const int b = blockIdx.y;
-  const int64_t nvec = (int64_t)S_tgt * C / 8;
-  bf16_t* xb = x + (int64_t)b * x_bs;
-  const bf16_t* vb = v + (int64_t)b * v_bs;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
-    const u32x4_t xw = *(const u32x4_t*)(xb + i * 8), vw = *(const u32x4_t*)(vb + i * 8);
-    u32x4_t ow;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float p0 = round_bf(dsig_bf * bf_lo(vw[e]));
-      const float p1 = round_bf(dsig_bf * bf_hi(vw[e]));
-      ow[e] = pack_bf2(bf_lo(xw[e]) + p0, bf_hi(xw[e]) + p1);
-    }
-    *(u32x4_t*)(xb + i * 8) = ow;
-  }
-}
-
-// Euler step + keep-region blend (keep_f, ew_grid and host_round_bf: step_common.h, shared with solver_step.hip).
-// One 8-vector spans two channels of one token (C % 8 == 0), and element j of a token is
-// sub-pixel j % 4, so the vector's mask pattern is the token's four values twice: one 8-byte load per vector.
-__global__ __launch_bounds__(256) void euler_inpaint_kernel(bf16_t* x, int64_t x_bs, const bf16_t* v, int64_t v_bs,
-                                                            const bf16_t* x0, int64_t x0_bs, const bf16_t* noise,
-                                                            int64_t n_bs, const bf16_t* mask, int64_t m_bs, int S_tgt,
-                                                            int C, float dsig_bf, float sb, float omsb) {
-  const int b = blockIdx.y;
-  const int64_t cvec = C / 8, nvec = (int64_t)S_tgt * cvec;
-  bf16_t* xb = x + (int64_t)b * x_bs;
-  const bf16_t* vb = v + (int64_t)b * v_bs;
-  const bf16_t* x0b = x0 + (int64_t)b * x0_bs;
-  const bf16_t* nb = noise + (int64_t)b * n_bs;
-  const bf16_t* mb = mask + (int64_t)b * m_bs;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
-    const u32x4_t xw = *(const u32x4_t*)(xb + i * 8), vw = *(const u32x4_t*)(vb + i * 8);
-    const u32x4_t zw = *(const u32x4_t*)(x0b + i * 8), nw = *(const u32x4_t*)(nb + i * 8);
-    const u32x2_t mw = *(const u32x2_t*)(mb + (i / cvec) * 4);
-    u32x4_t ow;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float m0 = bf_lo(mw[e & 1]), m1 = bf_hi(mw[e & 1]);
-      const float p0 = round_bf(bf_lo(xw[e]) + round_bf(dsig_bf * bf_lo(vw[e])));
-      const float p1 = round_bf(bf_hi(xw[e]) + round_bf(dsig_bf * bf_hi(vw[e])));
-      const float k0 = keep_f(sb, omsb, bf_lo(nw[e]), bf_lo(zw[e]));
-      const float k1 = keep_f(sb, omsb, bf_hi(nw[e]), bf_hi(zw[e]));
-      ow[e] = pack_bf2(round_bf(round_bf(1.0f - m0) * k0) + round_bf(m0 * p0),
-                       round_bf(round_bf(1.0f - m1) * k1) + round_bf(m1 * p1));
-    }
-    *(u32x4_t*)(xb + i * 8) = ow;
-  }
-}
-
-__global__ __launch_bounds__(256) void scale_noise_kernel(const bf16_t* x0, int64_t x0_bs, const bf16_t* noise,
-                                                          int64_t n_bs, bf16_t* out, int64_t o_bs, int S_tgt, int C,
-                                                          float sb, float omsb) {
-  const int b = blockIdx.y;
-  const int64_t nvec = (int64_t)S_tgt * C / 8;
-  const bf16_t* x0b = x0 + (int64_t)b * x0_bs;
-  const bf16_t* nb = noise + (int64_t)b * n_bs;
-  bf16_t* ob = out + (int64_t)b * o_bs;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
-    const u32x4_t zw = *(const u32x4_t*)(x0b + i * 8), nw = *(const u32x4_t*)(nb + i * 8);
-    u32x4_t ow;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      ow[e] = pack_bf2(keep_f(sb, omsb, bf_lo(nw[e]), bf_lo(zw[e])), keep_f(sb, omsb, bf_hi(nw[e]), bf_hi(zw[e])));
-    *(u32x4_t*)(ob + i * 8) = ow;
-  }
 }
 
 // [R, C] -> [C, R] through a 64x64 LDS tile (padded), 256 threads.
@@ -244,65 +174,6 @@ extern "C" int fk_timestep_proj(const void* v, int32_t v_is_fp32, const float* f
   hipLaunchKernelGGL(timestep_proj_kernel, dim3(B), dim3(128), 0, (hipStream_t)stream, v, v_is_fp32, freqs,
                      (bf16_t*)out, B);
   FK_CHECK_LAUNCH("fk_timestep_proj");
-  return FK_OK;
-}
-
-extern "C" int fk_euler_step_bf16(void* x, int64_t x_batch_stride, const void* v, int64_t v_batch_stride,
-                                  int32_t B, int32_t S_tgt, int32_t C, float dsigma, fk_stream_t stream) {
-  FK_CHECK_ARG(x && v && B > 0 && S_tgt > 0 && C > 0 && C % 8 == 0, "fk_euler_step_bf16: bad sizes");
-  FK_CHECK_ARG(x_batch_stride % 8 == 0 && v_batch_stride % 8 == 0 && ((uintptr_t)x % 16 == 0) &&
-                   ((uintptr_t)v % 16 == 0), "fk_euler_step_bf16: alignment");
-  // the reference multiplies a 0-dim fp32 tensor into a bf16 tensor: the scalar is first cast to bf16
-  const float dsig_bf = host_round_bf(dsigma);
-  const int64_t nvec = (int64_t)S_tgt * C / 8;
-  hipLaunchKernelGGL(euler_kernel, dim3(ew_grid(nvec), B), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x,
-                     x_batch_stride, (const bf16_t*)v, v_batch_stride, S_tgt, C, dsig_bf);
-  FK_CHECK_LAUNCH("fk_euler_step_bf16");
-  return FK_OK;
-}
-
-extern "C" int fk_euler_inpaint_step_bf16(void* x, int64_t x_batch_stride, const void* v, int64_t v_batch_stride,
-                                          const void* x0, int64_t x0_batch_stride, const void* noise,
-                                          int64_t noise_batch_stride, const void* mask, int64_t mask_batch_stride,
-                                          int32_t B, int32_t S_tgt, int32_t C, float dsigma, float sigma_next,
-                                          fk_stream_t stream) {
-  FK_CHECK_ARG(x && v && B > 0 && S_tgt > 0 && C > 0 && C % 8 == 0 && C % 4 == 0, "fk_euler_inpaint_step_bf16: bad sizes");
-  FK_CHECK_ARG(x_batch_stride % 8 == 0 && v_batch_stride % 8 == 0 && ((uintptr_t)x % 16 == 0) &&
-                   ((uintptr_t)v % 16 == 0), "fk_euler_inpaint_step_bf16: alignment");
-  const float dsig_bf = host_round_bf(dsigma);
-  const int64_t nvec = (int64_t)S_tgt * C / 8;
-  if (!mask) {  // a mask of ones selects the Euler update everywhere: x0 and noise are not read (and may be NULL)
-    hipLaunchKernelGGL(euler_kernel, dim3(ew_grid(nvec), B), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x,
-                       x_batch_stride, (const bf16_t*)v, v_batch_stride, S_tgt, C, dsig_bf);
-    FK_CHECK_LAUNCH("fk_euler_inpaint_step_bf16");
-    return FK_OK;
-  }
-  FK_CHECK_ARG(x0 && noise, "fk_euler_inpaint_step_bf16: a mask needs x0 and noise");
-  FK_CHECK_ARG(x0_batch_stride % 8 == 0 && noise_batch_stride % 8 == 0 && ((uintptr_t)x0 % 16 == 0) &&
-                   ((uintptr_t)noise % 16 == 0), "fk_euler_inpaint_step_bf16: alignment of x0 / noise");
-  FK_CHECK_ARG(mask_batch_stride % 4 == 0 && ((uintptr_t)mask % 8 == 0), "fk_euler_inpaint_step_bf16: alignment of the mask");
-  const float sb = host_round_bf(sigma_next), omsb = host_round_bf(1.0f - sb);
-  hipLaunchKernelGGL(euler_inpaint_kernel, dim3(ew_grid(nvec), B), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x,
-                     x_batch_stride, (const bf16_t*)v, v_batch_stride, (const bf16_t*)x0, x0_batch_stride,
-                     (const bf16_t*)noise, noise_batch_stride, (const bf16_t*)mask, mask_batch_stride, S_tgt, C, dsig_bf,
-                     sb, omsb);
-  FK_CHECK_LAUNCH("fk_euler_inpaint_step_bf16");
-  return FK_OK;
-}
-
-extern "C" int fk_scale_noise_bf16(const void* x0, int64_t x0_batch_stride, const void* noise, int64_t noise_batch_stride,
-                                   void* out, int64_t out_batch_stride, int32_t B, int32_t S_tgt, int32_t C, float sigma,
-                                   fk_stream_t stream) {
-  FK_CHECK_ARG(x0 && noise && out && B > 0 && S_tgt > 0 && C > 0 && C % 8 == 0, "fk_scale_noise_bf16: bad sizes");
-  FK_CHECK_ARG(x0_batch_stride % 8 == 0 && noise_batch_stride % 8 == 0 && out_batch_stride % 8 == 0 &&
-                   ((uintptr_t)x0 % 16 == 0) && ((uintptr_t)noise % 16 == 0) && ((uintptr_t)out % 16 == 0),
-               "fk_scale_noise_bf16: alignment");
-  const float sb = host_round_bf(sigma), omsb = host_round_bf(1.0f - sb);
-  const int64_t nvec = (int64_t)S_tgt * C / 8;
-  hipLaunchKernelGGL(scale_noise_kernel, dim3(ew_grid(nvec), B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x0,
-                     x0_batch_stride, (const bf16_t*)noise, noise_batch_stride, (bf16_t*)out, out_batch_stride, S_tgt, C,
-                     sb, omsb);
-  FK_CHECK_LAUNCH("fk_scale_noise_bf16");
   return FK_OK;
 }
 

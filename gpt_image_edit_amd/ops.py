@@ -726,10 +726,29 @@ def euler_step(x, v, s_tgt, dsigma):
     return x
 
 
-def _token_rows(name, t, B, s_tgt, C):
-    if t.dtype != BF16 or t.dim() != 3 or t.shape[0] != B or t.shape[1] < s_tgt or t.shape[2] != C or \
-            t.stride(2) != 1 or t.stride(1) != C:
-        raise ValueError(f"{name} must be bf16 [{B}, >= {s_tgt}, {C}] with contiguous rows, got {tuple(t.shape)} {t.dtype}")
+def _token_rows(B, s_tgt, C, mask=True, **rows):
+    """Checks that every given row tensor is bf16 [B, >= s_tgt, C] with contiguous rows; returns their [pointer, batch stride, ...]
+    as the C ABI takes them.  None = an operand the call does not have (NULL, 0), and so are x0 / noise when ``mask`` is None."""
+    args = []
+    for name, t in rows.items():
+        if t is None or (mask is None and name in ("x0", "noise")):
+            args += (None, 0)
+            continue
+        if t.dtype != BF16 or t.dim() != 3 or t.shape[0] != B or t.shape[1] < s_tgt or t.shape[2] != C or \
+                t.stride(2) != 1 or t.stride(1) != C:
+            raise ValueError(f"{name} must be bf16 [{B}, >= {s_tgt}, {C}] with contiguous rows, got {tuple(t.shape)} {t.dtype}")
+        args += (ctypes.c_void_p(t.data_ptr()), t.stride(0))
+    return args
+
+
+def _mask_args(mask, B, s_tgt):
+    """[pointer, batch stride] of the compact mask of :func:`pack_inpaint_mask`, checked; stride 0 = one mask for the batch."""
+    if mask is None:
+        return None, 0
+    if mask.dtype != BF16 or mask.dim() != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (s_tgt, 4) \
+            or not mask.is_contiguous():
+        raise ValueError(f"mask must be contiguous bf16 [1 or {B}, {s_tgt}, 4], got {tuple(mask.shape)} {mask.dtype}")
+    return ctypes.c_void_p(mask.data_ptr()), mask.stride(0) if mask.shape[0] == B and B > 1 else 0
 
 
 def euler_inpaint_step(x, v, s_tgt, dsigma, sigma_next, x0, noise, mask=None):
@@ -738,18 +757,9 @@ def euler_inpaint_step(x, v, s_tgt, dsigma, sigma_next, x0, noise, mask=None):
     [1 or B, s_tgt, 4] bf16 mask of :func:`pack_inpaint_mask`; None = ones, the values of :func:`euler_step`."""
     _need_cuda(x, v, x0, noise, mask)
     B, _, C = x.shape
-    for name, t in (("x", x), ("v", v)) + ((("x0", x0), ("noise", noise)) if mask is not None else ()):
-        _token_rows(name, t, B, s_tgt, C)
-    m_bs = 0
-    if mask is not None:
-        if mask.dtype != BF16 or mask.dim() != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (s_tgt, 4) \
-                or not mask.is_contiguous():
-            raise ValueError(f"mask must be contiguous bf16 [1 or {B}, {s_tgt}, 4], got {tuple(mask.shape)} {mask.dtype}")
-        m_bs = mask.stride(0) if mask.shape[0] == B and B > 1 else 0
-    libfk.check(libfk.load().fk_euler_inpaint_step_bf16(
-        _ptr(x), x.stride(0), _ptr(v), v.stride(0), _ptr(x0), 0 if x0 is None else x0.stride(0), _ptr(noise),
-        0 if noise is None else noise.stride(0), _ptr(mask), m_bs, B, s_tgt, C, float(dsigma), float(sigma_next),
-        _stream()), "fk_euler_inpaint_step_bf16")
+    rows = _token_rows(B, s_tgt, C, mask, x=x, v=v, x0=x0, noise=noise)
+    libfk.check(libfk.load().fk_euler_inpaint_step_bf16(*rows, *_mask_args(mask, B, s_tgt), B, s_tgt, C, float(dsigma),
+                                                        float(sigma_next), _stream()), "fk_euler_inpaint_step_bf16")
     return x
 
 
@@ -761,20 +771,9 @@ def ab2_step(x, v, hist, s_tgt, c_v, c_h, use_hist, sigma_next=0.0, x0=None, noi
     ``sigma_next`` are not used."""
     _need_cuda(x, v, hist, x0, noise, mask)
     B, _, C = x.shape
-    for name, t in (("x", x), ("v", v), ("hist", hist)) + ((("x0", x0), ("noise", noise)) if mask is not None else ()):
-        _token_rows(name, t, B, s_tgt, C)
-    m_bs = 0
-    if mask is not None:
-        if mask.dtype != BF16 or mask.dim() != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (s_tgt, 4) \
-                or not mask.is_contiguous():
-            raise ValueError(f"mask must be contiguous bf16 [1 or {B}, {s_tgt}, 4], got {tuple(mask.shape)} {mask.dtype}")
-        m_bs = mask.stride(0) if mask.shape[0] == B and B > 1 else 0
-    else:
-        x0 = noise = None
-    libfk.check(libfk.load().fk_ab2_step_bf16(
-        _ptr(x), x.stride(0), _ptr(v), v.stride(0), _ptr(hist), hist.stride(0), _ptr(x0), 0 if x0 is None else x0.stride(0),
-        _ptr(noise), 0 if noise is None else noise.stride(0), _ptr(mask), m_bs, B, s_tgt, C, float(c_v), float(c_h),
-        int(use_hist), float(sigma_next), _stream()), "fk_ab2_step_bf16")
+    rows = _token_rows(B, s_tgt, C, mask, x=x, v=v, hist=hist, x0=x0, noise=noise)
+    libfk.check(libfk.load().fk_ab2_step_bf16(*rows, *_mask_args(mask, B, s_tgt), B, s_tgt, C, float(c_v), float(c_h),
+                                              int(use_hist), float(sigma_next), _stream()), "fk_ab2_step_bf16")
     return x
 
 
@@ -787,23 +786,11 @@ def solver_step_f32(state, x, v, s_tgt, c_v, c_h=0.0, use_hist=0, load_state=1, 
     v[:, :s_tgt] in the same pass.  ``mask``: as in :func:`euler_inpaint_step`, blended in float32; None = ones."""
     _need_cuda(state, x, v, hist, x0, noise, mask)
     B, _, C = x.shape
-    for name, t in (("x", x), ("v", v)) + ((("hist", hist),) if hist is not None else ()) + \
-            ((("x0", x0), ("noise", noise)) if mask is not None else ()):
-        _token_rows(name, t, B, s_tgt, C)
+    rows = _token_rows(B, s_tgt, C, mask, x=x, v=v, hist=hist, x0=x0, noise=noise)
     if state.dtype != torch.float32 or tuple(state.shape) != (B, s_tgt, C) or state.stride(2) != 1 or state.stride(1) != C:
         raise ValueError(f"state must be fp32 [{B}, {s_tgt}, {C}] with contiguous rows, got {tuple(state.shape)} {state.dtype}")
-    m_bs = 0
-    if mask is not None:
-        if mask.dtype != BF16 or mask.dim() != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (s_tgt, 4) \
-                or not mask.is_contiguous():
-            raise ValueError(f"mask must be contiguous bf16 [1 or {B}, {s_tgt}, 4], got {tuple(mask.shape)} {mask.dtype}")
-        m_bs = mask.stride(0) if mask.shape[0] == B and B > 1 else 0
-    else:
-        x0 = noise = None
     libfk.check(libfk.load().fk_solver_step_f32(
-        _ptr(state), state.stride(0), _ptr(x), x.stride(0), _ptr(v), v.stride(0), _ptr(hist),
-        0 if hist is None else hist.stride(0), _ptr(x0), 0 if x0 is None else x0.stride(0), _ptr(noise),
-        0 if noise is None else noise.stride(0), _ptr(mask), m_bs, B, s_tgt, C, float(c_v), float(c_h), int(use_hist),
+        _ptr(state), state.stride(0), *rows, *_mask_args(mask, B, s_tgt), B, s_tgt, C, float(c_v), float(c_h), int(use_hist),
         int(load_state), float(sigma_next), _stream()), "fk_solver_step_f32")
     return x
 
@@ -815,10 +802,8 @@ def scale_noise(x0, noise, sigma, out=None):
     B, S, C = x0.shape
     if out is None:
         out = torch.empty((B, S, C), device=x0.device, dtype=BF16)
-    for name, t in (("x0", x0), ("noise", noise), ("out", out)):
-        _token_rows(name, t, B, S, C)
-    libfk.check(libfk.load().fk_scale_noise_bf16(_ptr(x0), x0.stride(0), _ptr(noise), noise.stride(0), _ptr(out),
-                                                 out.stride(0), B, S, C, float(sigma), _stream()), "fk_scale_noise_bf16")
+    rows = _token_rows(B, S, C, x0=x0, noise=noise, out=out)
+    libfk.check(libfk.load().fk_scale_noise_bf16(*rows, B, S, C, float(sigma), _stream()), "fk_scale_noise_bf16")
     return out
 
 

@@ -526,19 +526,8 @@ class FluxKontextPipeline:
                 noise_pred = self.transformer.step_cache_end(st, compute)
             if L.do_true_cfg:
                 noise_pred = ops.true_cfg(noise_pred[:B], noise_pred[B:], L.true_cfg_scale)
-            if L.state is not None:   # either rule on the float32 state; the token rows receive its rounding to bf16
-                c_v, c_h, use_hist = L.ab2[i] if L.ab2 is not None else (L.dsigma[i], 0.0, 0)
-                ops.solver_step_f32(L.state, tokens, noise_pred, L.S_tgt, c_v, c_h, use_hist, 0 if seed else 1, L.hist,
-                                    L.sigma_next[i] if L.inpaint else 0.0, L.x0, L.noise, L.mask)
-                seed = False
-            elif L.ab2 is not None:   # second-order multistep update (and hist <- this velocity), blended like the Euler one
-                c_v, c_h, use_hist = L.ab2[i]
-                ops.ab2_step(tokens, noise_pred, L.hist, L.S_tgt, c_v, c_h, use_hist,
-                             L.sigma_next[i] if L.inpaint else 0.0, L.x0, L.noise, L.mask)
-            elif L.inpaint:   # Euler update where the mask is 1, the preserved picture at sigma[i+1] where it is 0
-                ops.euler_inpaint_step(tokens, noise_pred, L.S_tgt, L.dsigma[i], L.sigma_next[i], L.x0, L.noise, L.mask)
-            else:
-                ops.euler_step(tokens, noise_pred, L.S_tgt, L.dsigma[i])
+            self._solver_step(L, i, noise_pred, seed)
+            seed = False
             if callback_on_step_end is not None:
                 out = callback_on_step_end(self, i, timesteps[i], {"latents": tokens[:, :L.S_tgt]})
                 if out and "latents" in out:
@@ -546,6 +535,22 @@ class FluxKontextPipeline:
                     seed = True     # the callback's bf16 latents become the state at the next step
         if sc is not None:
             sc.block_passes = st.block_passes
+
+    def _solver_step(self, L, i, noise_pred, seed):
+        """Step i of the loop on the token rows, one launch: the rule (Euler or AB2) on the state type (bf16 rows or the float32
+        state) the call chose, blended with the keep region of a masked edit.  ``seed``: the float32 state is not yet valid, and
+        the step widens the bf16 token rows instead of reading it."""
+        sigma_next = L.sigma_next[i] if L.inpaint else 0.0     # the keep region's noise level after the step
+        c_v, c_h, use_hist = L.ab2[i] if L.ab2 is not None else (L.dsigma[i], 0.0, 0)
+        if L.state is not None:   # either rule on the float32 state; the token rows receive its rounding to bf16
+            ops.solver_step_f32(L.state, L.tokens, noise_pred, L.S_tgt, c_v, c_h, use_hist, 0 if seed else 1, L.hist, sigma_next,
+                                L.x0, L.noise, L.mask)
+        elif L.ab2 is not None:   # second-order multistep update (and hist <- this velocity), blended like the Euler one
+            ops.ab2_step(L.tokens, noise_pred, L.hist, L.S_tgt, c_v, c_h, use_hist, sigma_next, L.x0, L.noise, L.mask)
+        elif L.inpaint:           # Euler update where the mask is 1, the preserved picture at sigma[i+1] where it is 0
+            ops.euler_inpaint_step(L.tokens, noise_pred, L.S_tgt, c_v, sigma_next, L.x0, L.noise, L.mask)
+        else:
+            ops.euler_step(L.tokens, noise_pred, L.S_tgt, c_v)
 
     def _step_cache_state(self, L):
         """The loop's cache state, reset for a new call: the graph route keeps one among the graph's own buffers

@@ -82,9 +82,22 @@ def test_it_lives_in_the_file_that_is_built_without_contraction():
     src = open(os.path.join(ROOT, "gpt_image_edit_amd", "csrc", "solver_step.hip")).read()
     assert re.search(r"^solver_step\.o:\s*EXTRA\s*:=.*-ffp-contract=off", mk, flags=re.M)
     assert 'extern "C" int ' + NAME in src
-    body = src[src.index("void state_kernel"):src.index('extern "C" int ' + NAME)]
-    assert "__fmul_rn" in body and "__fadd_rn" in body and "fmaf" not in body and "keep_f" not in body and "round_bf" not in body
     common = open(os.path.join(ROOT, "gpt_image_edit_amd", "csrc", "step_common.h")).read()
+    # the kernel's arithmetic is its own text plus the step_common.h helpers it calls, and the ones those call: each must be one
+    # this test knows, and the float32 rule holds over all of that text together
+    helpers = {m.group(1): m.group(0) for m in re.finditer(r"^FK_DEV [^\n(]*?\b(\w+)\([^\n]*\{\n.*?^\}\n", common, flags=re.M | re.S)}
+    assert {"widen8", "pack8", "axpy8_rn", "load_keep8", "blend8_bf16", "blend8_f32", "keep_f"} <= set(helpers)
+    body = src[src.index("void state_kernel"):src.index('extern "C" int ' + NAME)]
+    called, todo = set(), [body]
+    while todo:
+        text = todo.pop()
+        for name in helpers:
+            if name not in called and re.search(r"\b" + name + r"\(", text.split("{", 1)[1]):
+                called.add(name)
+                todo.append(helpers[name])
+    assert called == {"widen8", "axpy8_rn", "blend8_f32", "load_keep8", "pack8"}, called
+    body += "".join(helpers[name] for name in sorted(called))
+    assert "__fmul_rn" in body and "__fadd_rn" in body and "fmaf" not in body and "keep_f" not in body and "round_bf" not in body
     assert "ew_grid" in common and "ew_grid(nvec)" in src[src.index('extern "C" int ' + NAME):]
 
 
