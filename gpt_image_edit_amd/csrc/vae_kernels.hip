@@ -4,6 +4,7 @@
 //   apply : y = act(bf16((x - mean) * rstd * gamma + beta)), vectorised 16 bytes per lane
 // (the convolutions themselves are the implicit-GEMM path in gemm_bf16.hip).
 #include "fk_common.h"
+#include "pixel_common.h"   // pixel_norm, image_unit: shared with mask_ops.hip
 
 namespace {
 
@@ -195,8 +196,7 @@ __global__ __launch_bounds__(256) void pixels_u8_to_nhwc_kernel(const uint8_t* s
       const int yi = min((int)floorf(__fmul_rn((float)y, sy)), Hin - 1);
       const int xi = min((int)floorf(__fmul_rn((float)x, sx)), Win - 1);
       const float u = (float)sb[((int64_t)yi * Win + xi) * 3 + c];
-      v = __fdiv_rn(__fsub_rn(__fdiv_rn(u, 255.0f), 0.5f), 0.5f);
-      if (renorm) v = __fsub_rn(__fmul_rn(2.0f, v), 1.0f);
+      v = pixel_norm(u, renorm);
     }
     db[i] = f2bf(v);
   }
@@ -213,11 +213,7 @@ __global__ __launch_bounds__(256) void image_to_u8_kernel(const T* src, uint8_t*
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c = (int)(i % C);
     const int64_t p = i / C;
-    float t;
-    if constexpr (sizeof(T) == 4) t = __fadd_rn(__fdiv_rn(sb[(int64_t)c * HW + p], 2.0f), 0.5f);
-    else t = round_bf(round_bf(bf2f(sb[(int64_t)c * HW + p]) * 0.5f) + 0.5f);
-    t = fminf(fmaxf(t, 0.f), 1.f);
-    db[i] = (uint8_t)rintf(__fmul_rn(t, 255.0f));
+    db[i] = (uint8_t)rintf(__fmul_rn(image_unit(sb[(int64_t)c * HW + p]), 255.0f));
   }
 }
 

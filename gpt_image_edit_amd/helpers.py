@@ -5,6 +5,8 @@ Same behaviour as the static helpers of the reference's ``FluxKontextPipeline``
 (``train_denoiser.py:925,1009,1021,1098``) so the names and argument orders are kept.
 Checked against golden vectors produced by the reference itself (tests/golden/helpers.npz).
 """
+import math
+
 import torch
 
 # (width, height) pairs, univa/utils/flux_pipeline.py:85-103
@@ -65,3 +67,51 @@ def strength_t_start(num_inference_steps, strength):
         raise ValueError(f"The value of strength should be in (0, 1] but is {strength}")
     init_timestep = min(num_inference_steps * float(strength), num_inference_steps)
     return int(max(num_inference_steps - init_timestep, 0))
+
+
+MASK_BLUR_MAX_SIGMA = 64.0      # R = ceil(3 sigma) <= 192 = FK_MASK_BLUR_MAX_RADIUS (include/fk.h)
+
+
+def gaussian_taps(sigma):
+    """The 2R + 1 taps of the mask feather (fk_mask_blur_u8), R = ceil(3 sigma): float64 exp(-k^2 / (2 sigma^2)) divided by their
+    float64 sum, rounded to fp32.  Symmetric; they sum to 1 within (2R + 1) * 2^-24."""
+    sigma = float(sigma)
+    if not 0.0 < sigma <= MASK_BLUR_MAX_SIGMA:
+        raise ValueError(f"`mask_blur` is a sigma in (0, {MASK_BLUR_MAX_SIGMA:g}] pixels, not {sigma}")
+    R = int(math.ceil(3.0 * sigma))
+    w = [math.exp(-(k * k) / (2.0 * sigma * sigma)) for k in range(-R, R + 1)]
+    total = math.fsum(w)
+    return torch.tensor([v / total for v in w], dtype=torch.float64).to(torch.float32)
+
+
+def _grow(lo, hi, want, limit):
+    """[lo, hi) grown to `want` samples about its centre (the odd one to the far side), shifted back inside [0, limit) and, if it
+    is still larger, clamped to it."""
+    grow = max(want - (hi - lo), 0)
+    lo, hi = lo - grow // 2, hi + (grow - grow // 2)
+    if lo < 0:
+        lo, hi = 0, hi - lo
+    if hi > limit:
+        lo, hi = lo - (hi - limit), limit
+    return max(lo, 0), hi
+
+
+def mask_crop_box(bbox, W, H, pad, target_w, target_h):
+    """The box a cropped masked edit works on (diffusers' ``get_crop_region``, restated in integer arithmetic): the mask's bounding
+    box ``(x0, y0, x1, y1)`` (exclusive ends) padded by ``pad`` and clamped to the W x H picture; then the side that is short for
+    the target's aspect grows until ``bw * target_h`` and ``bh * target_w`` are as close as integers allow; then the box is shifted
+    back inside the picture.  A box that is still larger than the picture is clamped: its aspect then differs from the target's,
+    and the resize stretches."""
+    x0, y0, x1, y1 = (int(v) for v in bbox)
+    W, H, pad, target_w, target_h = int(W), int(H), int(pad), int(target_w), int(target_h)
+    if x1 <= x0 or y1 <= y0:
+        raise ValueError("the mask is empty: there is no box to crop to")
+    if pad < 0 or min(W, H, target_w, target_h) <= 0 or x0 < 0 or y0 < 0 or x1 > W or y1 > H:
+        raise ValueError(f"bad crop arguments: bbox {(x0, y0, x1, y1)} in a {W} x {H} picture, pad {pad}")
+    x0, y0, x1, y1 = max(x0 - pad, 0), max(y0 - pad, 0), min(x1 + pad, W), min(y1 + pad, H)
+    bw, bh = x1 - x0, y1 - y0
+    if bw * target_h < bh * target_w:       # narrow for the target: the width that brings bw * target_h nearest bh * target_w
+        x0, x1 = _grow(x0, x1, (2 * bh * target_w + target_h) // (2 * target_h), W)
+    elif bw * target_h > bh * target_w:
+        y0, y1 = _grow(y0, y1, (2 * bw * target_h + target_w) // (2 * target_w), H)
+    return x0, y0, x1, y1

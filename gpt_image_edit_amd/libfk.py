@@ -243,6 +243,11 @@ SIGNATURES = {
     "fk_nhwc_to_nchw": (c_i32, [c_vp, c_vp] + [c_i32] * 6 + [c_f32, c_f32, c_vp]),
     "fk_pixels_u8_to_nhwc_bf16": (c_i32, [c_vp, c_vp] + [c_i32] * 7 + [c_vp]),
     "fk_image_to_u8_nhwc": (c_i32, [c_vp, c_i32, c_vp] + [c_i32] * 4 + [c_vp]),
+    "fk_mask_bbox_ws_ints": (c_i64, []),
+    "fk_mask_bbox_u8": (c_i32, [c_vp] + [c_i32] * 4 + [c_vp, c_vp, c_i64, c_vp]),
+    "fk_mask_blur_u8": (c_i32, [c_vp] * 4 + [c_i32] * 4 + [c_vp]),
+    "fk_pixels_u8_box_to_nhwc_bf16": (c_i32, [c_vp, c_vp] + [c_i32] * 11 + [c_vp]),
+    "fk_image_overlay_u8": (c_i32, [c_vp] + [c_i32] * 3 + [c_vp, c_i32, c_vp, c_i32, c_vp] + [c_i32] * 7 + [c_vp]),
     "fk_double_block_fwd": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(DoubleBlockWeights), c_vp, c_i64, c_vp]),
     "fk_single_block_fwd": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(SingleBlockWeights), c_vp, c_i64, c_vp]),
     "fk_single_block_bwd": (c_i32, [ctypes.POINTER(BwdWs), ctypes.POINTER(BlockSaved), ctypes.POINTER(SingleBlockWeights),

@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from . import libfk, param_tree
+from . import helpers, libfk, param_tree
 from .libfk import (FK_EPI_GATE_RES, FK_EPI_GELU_TANH, FK_EPI_NONE, FK_EPI_QKV, FK_EPI_RES, FK_EPI_SCALE,  # noqa: F401
                     FK_EPI_SILU, GemmArgs, GemmMxfp8Args, GemmMxfp8QArgs, Rows)
 
@@ -1494,6 +1494,92 @@ def image_to_u8(img):
     out = torch.empty((B, H, W, C), device=img.device, dtype=torch.uint8)
     libfk.check(libfk.load().fk_image_to_u8_nhwc(_ptr(img), int(img.dtype == torch.float32), _ptr(out), B, C, H, W,
                                                  _stream()), "fk_image_to_u8_nhwc")
+    return out
+
+
+# ---- masked edits on the masked box (include/fk.h: fk_mask_bbox_u8, fk_mask_blur_u8, fk_pixels_u8_box_to_nhwc_bf16,
+# fk_image_overlay_u8) -----------------------------------------------------------------------------------------------
+def _mask_u8(mask, what):
+    _need_cuda(mask)
+    if mask.dtype != torch.uint8 or mask.dim() != 3 or not mask.is_contiguous():
+        raise TypeError(f"{what} takes a contiguous uint8 [Bm, H, W] mask")
+    return mask.shape
+
+
+def _box(box):
+    x0, y0, x1, y1 = (int(v) for v in box)
+    return x0, y0, x1, y1
+
+
+def mask_bbox(mask_u8, threshold=1, out=None, ws=None):
+    """int32 [4] on the device: (min x, min y, max x + 1, max y + 1) over all samples of the pixels with byte >= ``threshold``;
+    (W, H, 0, 0) when there are none.  ``ws``: the partials workspace (allocated per call when None)."""
+    Bm, H, W = _mask_u8(mask_u8, "mask_bbox")
+    lib = libfk.load()
+    if out is None:
+        out = torch.empty(4, device=mask_u8.device, dtype=torch.int32)
+    if ws is None:
+        ws = torch.empty(lib.fk_mask_bbox_ws_ints(), device=mask_u8.device, dtype=torch.int32)
+    _need_cuda(out, ws)
+    if out.dtype != torch.int32 or out.numel() < 4 or not out.is_contiguous() or ws.dtype != torch.int32 or not ws.is_contiguous():
+        raise ValueError("out must be int32 [4], ws a contiguous int32 workspace")
+    libfk.check(lib.fk_mask_bbox_u8(_ptr(mask_u8), Bm, H, W, int(threshold), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+                "fk_mask_bbox_u8")
+    return out
+
+
+def mask_blur(mask_u8, sigma, out=None):
+    """The mask feathered with a separable Gaussian of ``sigma`` pixels (taps: ``helpers.gaussian_taps``), uint8 [Bm, H, W]."""
+    Bm, H, W = _mask_u8(mask_u8, "mask_blur")
+    taps = helpers.gaussian_taps(sigma).to(mask_u8.device)
+    plane = torch.empty((Bm, H, W), device=mask_u8.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty_like(mask_u8)
+    _mask_u8(out, "mask_blur")
+    if out.shape != mask_u8.shape:
+        raise ValueError("out must have the mask's shape")
+    libfk.check(libfk.load().fk_mask_blur_u8(_ptr(mask_u8), _ptr(out), _ptr(plane), _ptr(taps), (taps.numel() - 1) // 2, Bm, H, W,
+                                             _stream()), "fk_mask_blur_u8")
+    return out
+
+
+def pixels_box_to_nhwc(u8, box, out_h, out_w, cpad=32, renorm=False, out=None):
+    """:func:`pixels_to_nhwc` reading the source box ``(x0, y0, x1, y1)`` with bilinear weights (half-pixel centres)."""
+    _need_cuda(u8, out)
+    if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3 or not u8.is_contiguous():
+        raise TypeError("pixels_box_to_nhwc takes a contiguous uint8 [B, H, W, 3] tensor")
+    B, Hin, Win, _ = u8.shape
+    if out is None:
+        out = torch.empty((B, out_h, out_w, cpad), device=u8.device, dtype=BF16)
+    if out.dtype != BF16 or tuple(out.shape) != (B, out_h, out_w, cpad) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous bf16 [B, out_h, out_w, cpad] tensor")
+    libfk.check(libfk.load().fk_pixels_u8_box_to_nhwc_bf16(_ptr(u8), _ptr(out), B, Hin, Win, *_box(box), out_h, out_w, cpad,
+                                                           int(bool(renorm)), _stream()), "fk_pixels_u8_box_to_nhwc_bf16")
+    return out
+
+
+def image_overlay(img, orig_u8, alpha_u8, box, out=None):
+    """Decoder output [B,3,h,w] (bf16/fp32) resampled into ``box`` of the original picture uint8 [1 or B,H,W,3] and blended
+    over its bytes with ``alpha_u8`` (uint8 [1 or B,H,W], None = 255 everywhere) -> uint8 [B,H,W,3]."""
+    _need_cuda(img, orig_u8, alpha_u8, out)
+    if img.dtype not in (BF16, torch.float32) or img.dim() != 4 or img.shape[1] != 3 or not img.is_contiguous():
+        raise TypeError("image_overlay takes a contiguous fp32/bf16 [B, 3, h, w] tensor")
+    if orig_u8.dtype != torch.uint8 or orig_u8.dim() != 4 or orig_u8.shape[3] != 3 or not orig_u8.is_contiguous():
+        raise TypeError("image_overlay takes the original as a contiguous uint8 [1 or B, H, W, 3] tensor")
+    B, _, h, w = img.shape
+    N, H, W, _ = orig_u8.shape
+    Bm = 0
+    if alpha_u8 is not None:
+        Bm, Ha, Wa = _mask_u8(alpha_u8, "image_overlay")
+        if (Ha, Wa) != (H, W):
+            raise ValueError(f"alpha is {Ha} x {Wa}, the original {H} x {W}")
+    if out is None:
+        out = torch.empty((B, H, W, 3), device=img.device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, 3) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 [B, H, W, 3] tensor")
+    libfk.check(libfk.load().fk_image_overlay_u8(_ptr(img), int(img.dtype == torch.float32), h, w, _ptr(orig_u8), N,
+                                                 _ptr(alpha_u8), Bm, _ptr(out), B, H, W, *_box(box), _stream()),
+                "fk_image_overlay_u8")
     return out
 
 

@@ -241,9 +241,14 @@ class FluxKontextPipeline:
             latents = latents.to(device=device, dtype=dtype)
         return latents, image_latents, latent_ids, image_ids
 
-    def _prepare_mask(self, mask_image, batch_size, height, width, device):
+    def _prepare_mask(self, mask_image, batch_size, height, width, device, edit=None):
         """``mask_image`` (float [1 or B, 1, Hm, Wm] in [0, 1]; uint8 tensor / numpy / PIL greyscale, 255 = repaint) -> the
-        compact token mask [1 or B, S_tgt, 4] of the fused step: binarised at 0.5, nearest-resized to the latent size."""
+        compact token mask [1 or B, S_tgt, 4] of the fused step: binarised at 0.5, nearest-resized to the latent size.
+
+        ``edit`` (``_check_pixel_edit``; None: today's path): the mask as bytes on the device, feathered (``fk_mask_blur_u8``) when
+        ``mask_blur`` > 0, and from then on THE mask -- the overlay's alpha, the source of the crop box (``fk_mask_bbox_u8`` on
+        alpha >= 1, the call's one read-back, then ``helpers.mask_crop_box``) and, sliced to that box, of the token mask
+        (``_prepare_edit_mask``)."""
         m = mask_image
         if hasattr(m, "convert"):
             m = [m]
@@ -256,6 +261,8 @@ class FluxKontextPipeline:
             m = torch.from_numpy(np.ascontiguousarray(m))
         if not torch.is_tensor(m):
             raise ValueError("pass `mask_image` as a [1 or B, 1, H, W] tensor in [0, 1], or as uint8 / PIL greyscale")
+        if edit is not None:
+            return self._prepare_edit_mask(m, edit, batch_size, height, width, device)
         m = m.float() / 255.0 if m.dtype == torch.uint8 else m.float()
         if m.dim() == 2:
             m = m[None]
@@ -268,13 +275,75 @@ class FluxKontextPipeline:
         sf = self.vae_scale_factor * 2
         return ops.pack_inpaint_mask(m, 2 * (int(height) // sf), 2 * (int(width) // sf)).to(device)
 
-    def _encode_init_image(self, init_image, batch_size, num_channels_latents, height, width, device):
+    def _prepare_edit_mask(self, m, edit, batch_size, height, width, device):
+        """``_prepare_mask`` of a call with ``padding_mask_crop`` / ``mask_blur`` / ``overlay``: fills ``edit.alpha`` (uint8
+        [1 or B, Hm, Wm] on the device), ``edit.box`` and ``edit.renorm``, returns the token mask of the box."""
+        if m.dtype != torch.uint8:          # a float mask's bytes: rint(255 m)
+            m = m.float().clamp(0, 1).mul(255).round().to(torch.uint8)
+        if m.dim() == 4 and m.shape[1] == 1:
+            m = m[:, 0]
+        if m.dim() == 2:
+            m = m[None]
+        if m.dim() != 3:
+            raise ValueError(f"`mask_image` must be [1 or B, 1, H, W], got {tuple(m.shape)}")
+        if m.shape[0] not in (1, batch_size):
+            raise ValueError(f"`mask_image` has batch {m.shape[0]}: must be 1 or the batch size {batch_size}")
+        Hm, Wm = m.shape[1:]
+        if edit.pic is not None and tuple(edit.pic.shape[1:3]) != (Hm, Wm):
+            raise ValueError(f"`mask_image` is {Hm} x {Wm}, the preserved picture {edit.pic.shape[1]} x {edit.pic.shape[2]}: "
+                             "a crop or an overlay needs both at one size")
+        a = m.to(device).contiguous()
+        if edit.sigma > 0:
+            a = ops.mask_blur(a, edit.sigma)
+        edit.alpha, edit.box = a, (0, 0, Wm, Hm)
+        if edit.crop:
+            bbox = ops.mask_bbox(a, 1).tolist()             # 16 bytes: the call's one read-back
+            if bbox[2] <= bbox[0] or bbox[3] <= bbox[1]:
+                raise ValueError("`mask_image` is empty: `padding_mask_crop` has no box to crop to")
+            x0, y0, x1, y1 = edit.box = helpers.mask_crop_box(bbox, Wm, Hm, edit.pad, width, height)
+            # the existing quirk, stated for the box: a second normalisation iff no normalised value of it is negative
+            edit.renorm = bool(edit.pic[:, y0:y1, x0:x1].min() >= 128)
+            a = a[:, y0:y1, x0:x1]
+        if edit.pic is not None:
+            edit.pic = edit.pic.to(device).contiguous()
+        sf = self.vae_scale_factor * 2
+        return ops.pack_inpaint_mask(a[:, None].float() / 255.0, 2 * (int(height) // sf), 2 * (int(width) // sf)).to(device)
+
+    def _check_pixel_edit(self, image, init_image, mask_image, padding_mask_crop, mask_blur, overlay, output_type):
+        """The refusals of ``padding_mask_crop`` / ``mask_blur`` / ``overlay``, before any work, and what the call carries from
+        here on: sigma, pad, whether it crops and overlays, and the preserved picture's bytes (``pic``, uint8 [N, H, W, 3])."""
+        sigma = float(mask_blur)
+        if not 0.0 <= sigma <= helpers.MASK_BLUR_MAX_SIGMA:
+            raise ValueError(f"`mask_blur` is a sigma in [0, {helpers.MASK_BLUR_MAX_SIGMA:g}] pixels, not {mask_blur!r}")
+        crop = padding_mask_crop is not None
+        if crop and (isinstance(padding_mask_crop, bool) or not isinstance(padding_mask_crop, (int, np.integer))
+                     or padding_mask_crop < 0):
+            raise ValueError(f"`padding_mask_crop` is an int >= 0 or None, not {padding_mask_crop!r}")
+        if mask_image is None:
+            raise ValueError("`padding_mask_crop` / `mask_blur` / `overlay` need `mask_image`")
+        if overlay is None:                 # a crop is pasted back, except where the caller asks for the crop's latents
+            overlay = crop and output_type != "latent"
+        if overlay and output_type not in ("pil", "np_uint8"):
+            raise ValueError(f'`overlay` returns uint8 pixels: `output_type` is "pil" or "np_uint8", not {output_type!r}')
+        pic = None
+        if crop or overlay:
+            pic = image_processor.as_uint8_nhwc(image if init_image is None else init_image)
+            if pic is None:
+                raise ValueError("`padding_mask_crop` / `overlay` need the preserved picture as uint8 pixels (PIL / numpy / uint8 "
+                                 "tensor [N,H,W,3]): a float tensor or latents have no bytes to keep")
+        return SimpleNamespace(sigma=sigma, pad=None if not crop else int(padding_mask_crop), crop=crop, overlay=bool(overlay),
+                               pic=pic, alpha=None, box=None, renorm=False)
+
+    def _encode_init_image(self, init_image, batch_size, num_channels_latents, height, width, device, edit=None):
         """Packed latents [B, S_tgt, 64] of the picture a masked edit preserves, at the target size: the condition image's
         own routes (uint8 pixels through the fused gather, float tensors through resize + preprocess) without the
-        preferred-resolution snap; pre-encoded latents must already have the target's latent size."""
+        preferred-resolution snap; pre-encoded latents must already have the target's latent size.  A cropped edit
+        (``edit.crop``) samples the picture's box instead (``fk_pixels_u8_box_to_nhwc_bf16``, bilinear)."""
         h_lat, w_lat = height // self.vae_scale_factor, width // self.vae_scale_factor
         u8 = image_processor.as_uint8_nhwc(init_image)
-        if u8 is not None:
+        if edit is not None and edit.crop:
+            lat = self._encode_vae_image(self._crop_pixels(edit, height, width).tensor, nhwc=True)
+        elif u8 is not None:
             px = image_processor.pixels_to_latent_input(u8, height, width, device)
             lat = self._encode_vae_image(px.tensor, nhwc=True)
         elif isinstance(init_image, torch.Tensor) and init_image.dim() == 4 and init_image.size(1) == self.latent_channels:
@@ -296,6 +365,11 @@ class FluxKontextPipeline:
             raise ValueError(f"Cannot duplicate the preserved picture of batch size {n} to batch size {batch_size}.")
         return self._pack_latents(lat, batch_size, num_channels_latents, h_lat, w_lat).contiguous()
 
+    @staticmethod
+    def _crop_pixels(edit, height, width):
+        """The preserved picture's box at height x width, as the VAE encoder's input."""
+        return image_processor.NhwcPixels(ops.pixels_box_to_nhwc(edit.pic, edit.box, height, width, 32, edit.renorm))
+
     @torch.no_grad()
     def __call__(self, image=None, prompt=None, prompt_2=None, negative_prompt=None, negative_prompt_2=None,
                  true_cfg_scale=1.0, height=None, width=None, num_inference_steps=28, sigmas=None,
@@ -304,7 +378,7 @@ class FluxKontextPipeline:
                  output_type="pil", return_dict=True, joint_attention_kwargs=None, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=("latents",), max_sequence_length=512,
                  max_area=1024 ** 2, _auto_resize=True, mask_image=None, strength=1.0, init_image=None, step_cache=None,
-                 latent_state="bf16"):
+                 padding_mask_crop=None, mask_blur=0.0, overlay=None, latent_state="bf16"):
         """``mask_image`` / ``strength`` / ``init_image`` (diffusers' ``FluxKontextInpaintPipeline``): repaint only where the
         mask is 1 and keep ``init_image`` (default: ``image``, resized to the target size) elsewhere; ``strength`` < 1 starts
         the loop inside the schedule from the re-noised ``init_image`` instead of from noise.  ``image`` stays the Kontext
@@ -320,6 +394,18 @@ class FluxKontextPipeline:
         reference's loop rounds them.  "fp32" carries them in a float32 buffer of the call's own ([B, S_tgt, 64], seeded from
         the bf16 start tokens) through ``fk_solver_step_f32``, for whichever scheduler is installed; the model still reads the
         bf16 token rows, which receive the state's one rounding per step, and the returned latents are those rows.
+
+        ``padding_mask_crop`` / ``mask_blur`` / ``overlay`` (diffusers' ``padding_mask_crop`` + ``apply_overlay``; parity with PIL's
+        GaussianBlur and lanczos resize unpinned): work on the masked box and paste the result back.  They need ``mask_image``;
+        a crop or an overlay also needs the preserved picture (``init_image``, else ``image``) as uint8 pixels of the mask's size.
+        ``mask_blur`` (sigma in pixels of the mask image, at most 64) feathers the mask, which from then on is the mask everywhere.
+        ``padding_mask_crop`` (int >= 0): one box per call -- the bounding box over the mask batch of alpha >= 1, padded and grown
+        to the target's aspect (``helpers.mask_crop_box``) -- is sampled bilinearly at ``height`` x ``width`` and edited in place
+        of the picture; without ``init_image`` the Kontext condition is the same crop.  ``overlay`` (None: on with a crop, except
+        for ``output_type="latent"``, which returns the crop's latents): the returned image has the preserved picture's size and
+        its own bytes outside the box and wherever alpha is 0, the alpha blend of the resampled result elsewhere; without a crop
+        the box is the whole picture.  The output carries ``crop_box``.  With all three at their defaults the call is today's
+        call, launch for launch.  Not built: antialiased resampling.
 
         ``joint_attention_kwargs["scale"]`` (default 1.0): the call scale of the loaded LoRA adapters (``load_lora_weights``)."""
         device = self.device
@@ -341,6 +427,9 @@ class FluxKontextPipeline:
         inpaint = mask_image is not None or init_image is not None or strength < 1.0
         if (mask_image is not None or strength < 1.0) and image is None and init_image is None:
             raise ValueError("`mask_image` / `strength` < 1 need a picture to preserve: pass `image` or `init_image`")
+        edit = None
+        if padding_mask_crop is not None or mask_blur or overlay:
+            edit = self._check_pixel_edit(image, init_image, mask_image, padding_mask_crop, mask_blur, overlay, output_type)
         if prompt is not None and prompt_embeds is not None:
             raise ValueError(f"Cannot forward both `prompt`: {prompt} and `prompt_embeds`: {prompt_embeds}. Please make "
                              "sure to only forward one of the two.")   # :510-514
@@ -390,12 +479,25 @@ class FluxKontextPipeline:
             model_embeds, model_pooled = prompt_embeds, pooled_prompt_embeds
         model_batch = model_embeds.shape[0]
 
-        mask = None if mask_image is None else self._prepare_mask(mask_image, batch_size, height, width, device)
+        if edit is None:
+            mask = None if mask_image is None else self._prepare_mask(mask_image, batch_size, height, width, device)
+        else:
+            if edit.pic is not None and edit.pic.shape[0] not in (1, batch_size):
+                raise ValueError(f"the preserved picture has batch {edit.pic.shape[0]}: must be 1 or the batch size {batch_size}")
+            mask = self._prepare_mask(mask_image, batch_size, height, width, device, edit)
 
         # 3. condition image: preferred-resolution snap + nearest resize (VaeImageProcessor tensor path)
         image_in, cond_hw = image, None             # cond_hw: pixel size the condition latents stand for
         u8 = image_processor.as_uint8_nhwc(image) if image is not None else None
-        if u8 is not None:
+        if edit is not None and edit.crop and init_image is None:
+            # `image` stands in as the preserved picture: the condition is the same crop, at the size the box snaps to
+            ih, iw = self.image_processor.get_default_height_width(None, edit.box[3] - edit.box[1], edit.box[2] - edit.box[0])
+            ih, iw = helpers.preferred_condition_size(ih, iw, multiple_of, _auto_resize) if min(ih, iw) > 0 else (0, 0)
+            if min(ih, iw) <= 0:
+                raise ValueError(f"the crop box {edit.box} is smaller than one {multiple_of}-pixel token: raise `padding_mask_crop`")
+            image = self._crop_pixels(edit, ih, iw)
+            cond_hw = (ih, iw)
+        elif u8 is not None:
             # uint8 pixels: cli.prepare_condition_images + resize + preprocess + .to(bf16) as ONE HIP gather
             ih, iw = self.image_processor.get_default_height_width(u8.permute(0, 3, 1, 2))
             ih, iw = helpers.preferred_condition_size(ih, iw, multiple_of, _auto_resize)
@@ -430,7 +532,7 @@ class FluxKontextPipeline:
                 x0 = image_latents
             else:
                 x0 = self._encode_init_image(image_in if init_image is None else init_image, batch_size,
-                                             num_channels_latents, height, width, device)
+                                             num_channels_latents, height, width, device, edit)
             noise = latents.contiguous()            # a caller-supplied `latents` serves as the noise, as in diffusers
 
         # 5. timesteps (host float32 arithmetic, like diffusers' numpy path)
@@ -492,10 +594,18 @@ class FluxKontextPipeline:
             z = self._unpack_latents(latents, height, width, self.vae_scale_factor).contiguous()
             vcfg = self.vae.config
             img = self.vae.decode(z, return_dict=False, pre_div=vcfg.scaling_factor, pre_add=vcfg.shift_factor)[0]
-            image_out = self.postprocess(img, output_type)
+            if edit is not None and edit.overlay:
+                # the result resampled into the box and blended over the picture's own bytes: they are kept, not decoded
+                image_out = ops.image_overlay(img.contiguous(), edit.pic, edit.alpha, edit.box).cpu().numpy()
+                if output_type == "pil":
+                    from PIL import Image
+                    image_out = [Image.fromarray(a) for a in image_out]
+            else:
+                image_out = self.postprocess(img, output_type)
         if not return_dict:
             return (image_out,)
-        return FluxPipelineOutput(images=image_out, latents=latents)  # .latents: packed final latents (DP gather)
+        # .latents: packed final latents (DP gather); .crop_box: (x0, y0, x1, y1) of a cropped masked edit, else None
+        return FluxPipelineOutput(images=image_out, latents=latents, crop_box=edit.box if edit is not None and edit.crop else None)
 
     def _denoise(self, L, callback_on_step_end=None, timesteps=None):
         """Conditioning of all steps in one pass, then the loop (flux_pipeline.py:1052-1120) over the persistent buffers."""

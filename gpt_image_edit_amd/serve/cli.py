@@ -132,6 +132,14 @@ def inpaint_kwargs(args):
         kw["mask_image"] = Image.open(args.mask).convert("L")
     if getattr(args, "strength", None) is not None and args.strength != 1.0:
         kw["strength"] = args.strength
+    # the masked box at full model resolution, a feathered mask, the input's own bytes outside the repainted region: each is
+    # passed only when asked for, so without them the call is the one the pipeline always got
+    if getattr(args, "mask_crop_padding", None) is not None:
+        kw["padding_mask_crop"] = args.mask_crop_padding
+    if getattr(args, "mask_blur", None):
+        kw["mask_blur"] = args.mask_blur
+    if getattr(args, "overlay", False):
+        kw["overlay"] = True
     return kw
 
 
@@ -248,6 +256,14 @@ def build_parser():
     parser.add_argument("--strength", type=float, default=1.0, metavar="F",
                         help="in (0, 1]: below 1 the edit starts from the re-noised input image instead of from noise and "
                              "runs the last F of the steps (with --prompt_embeds / --t5_only)")
+    parser.add_argument("--mask_crop_padding", type=int, default=None, metavar="N",
+                        help="with --mask: edit only the mask's bounding box, padded by N pixels and grown to the target's aspect, "
+                             "at the full model resolution, and paste the result back into the input image")
+    parser.add_argument("--mask_blur", type=float, default=0.0, metavar="F",
+                        help="with --mask: feather the mask with a Gaussian of sigma F pixels (at most 64) before it is used")
+    parser.add_argument("--overlay", action="store_true",
+                        help="with --mask: return the input image's own bytes wherever the mask is black (implied by "
+                             "--mask_crop_padding)")
     add_step_cache_arguments(parser)
     add_solver_argument(parser)
     lora.add_cli_arguments(parser)
@@ -262,6 +278,9 @@ def main(args):
         transformer.set_mx_fused_attn(True)
     if (getattr(args, "mask", None) or getattr(args, "strength", 1.0) != 1.0) and not (args.prompt_embeds or args.t5_only):
         raise SystemExit("--mask / --strength go with --prompt_embeds or --t5_only")
+    if (getattr(args, "mask_crop_padding", None) is not None or getattr(args, "mask_blur", 0.0) or getattr(args, "overlay", False)) \
+            and not getattr(args, "mask", None):
+        raise SystemExit("--mask_crop_padding / --mask_blur / --overlay go with --mask")
     step_cache_kwargs(args)      # a bad threshold / schedule / coefficient list fails before the weights load
     pipe, tokenizers, text_encoders = load_pipe(args.model_path, args.flux_path, device,
                                                 weight_format=getattr(args, "weight_format", "bf16"),

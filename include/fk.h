@@ -880,6 +880,51 @@ int fk_pixels_u8_to_nhwc_bf16(const void* src, void* dst, int32_t B, int32_t Hin
 int fk_image_to_u8_nhwc(const void* src, int32_t src_is_fp32, void* dst, int32_t B, int32_t C, int32_t H, int32_t W,
                         fk_stream_t stream);
 
+/* ---- Masked edits on the masked box (pipeline.py: padding_mask_crop / mask_blur / overlay; csrc/mask_ops.hip).  The rules are
+ * written from the description of diffusers' VaeImageProcessor.get_crop_region / .blur / .apply_overlay; parity with PIL's
+ * GaussianBlur and lanczos resize is unpinned.  Every product, sum and division below is one fp32 operation (the file is built
+ * without contraction) -- except in K3, where each is one fp64 operation; every index is clamped before its load; no atomics.  A refused call returns FK_EINVAL with a message and
+ * writes nothing.  Not built: antialiased downsampling (a box smaller than the model resolution on the way out, larger on the
+ * way in, is point-sampled bilinear).
+ *
+ * The bilinear rule (K3, K4), per axis, output position X of n_out over a source of n_in samples:
+ *   s = clamp((X + 0.5) * (n_in / n_out) - 0.5, 0, n_in - 1),  i0 = floor(s),  i1 = min(i0 + 1, n_in - 1),  f = s - i0
+ *   u = (1-fy) * ((1-fx) * p00 + fx * p01) + fy * ((1-fx) * p10 + fx * p11)
+ * Equal sizes give s = X, f = 0 and u = p00 exactly. ---- */
+
+/* K1.  mask [Bm, H, W] uint8 -> out4 = (min x, min y, max x + 1, max y + 1) over all samples of the pixels with byte >= threshold
+ * (0..255); (W, H, 0, 0) when there are none.  Per-block partials in `ws` (fk_mask_bbox_ws_ints() int32, caller-owned, one per
+ * stream of ordered launches) and a one-block finish.  out4 and ws: device int32, 4-byte aligned. */
+int64_t fk_mask_bbox_ws_ints(void);
+int fk_mask_bbox_u8(const void* mask, int32_t Bm, int32_t H, int32_t W, int32_t threshold, int32_t* out4, int32_t* ws,
+                    int64_t ws_ints, fk_stream_t stream);
+/* K2.  Separable Gaussian feather of src [Bm, H, W] uint8 into dst (same shape; dst may be src).  taps: device fp32 [2R + 1],
+ * made on the host (helpers.gaussian_taps: R = ceil(3 sigma), float64 exp(-k^2 / (2 sigma^2)) divided by their float64 sum,
+ * rounded to fp32), 0 <= R <= FK_MASK_BLUR_MAX_RADIUS.  Horizontal pass into `plane` (caller-owned fp32 [Bm, H, W]):
+ *   acc = 0;  for k = -R..R ascending: acc = acc + w[k] * float(src[y, clamp(x + k, 0, W-1)])
+ * vertical pass: the same over y on that plane; dst = uint8(rint(clamp(v, 0, 255))).  The order of operations is the contract. */
+#define FK_MASK_BLUR_MAX_RADIUS 192
+int fk_mask_blur_u8(const void* src, void* dst, float* plane, const float* taps, int32_t R, int32_t Bm, int32_t H, int32_t W,
+                    fk_stream_t stream);
+/* K3.  fk_pixels_u8_to_nhwc_bf16 reading the source box [x0, x1) x [y0, y1) of src [B, Hin, Win, 3] with the bilinear rule
+ * (n_in = the box's side, n_out = Wout / Hout) on the bytes, then that kernel's normalisation, `renorm` flag (the caller checks
+ * that every byte of the box is >= 128) and bf16 cast.  Every element is within 1 bf16 ulp of the rule's exact value, which fp32
+ * cannot give where the normalised value crosses 0: s, f, u, ((u / 255) - 0.5) / 0.5 and 2v - 1 are evaluated in fp64, in this
+ * order, and rounded to fp32, then bf16.  A sample on a source pixel (fx == fy == 0) takes that kernel's fp32 value of the byte
+ * (at most 1 bf16 ulp from the fp64 one), so a box that is the whole picture at equal size gives that kernel's bits. */
+int fk_pixels_u8_box_to_nhwc_bf16(const void* src, void* dst, int32_t B, int32_t Hin, int32_t Win, int32_t x0, int32_t y0,
+                                  int32_t x1, int32_t y1, int32_t Hout, int32_t Wout, int32_t Cpad, int32_t renorm,
+                                  fk_stream_t stream);
+/* K4.  img: decoder output NCHW [B, 3, h, w] (bf16 or fp32); orig: uint8 [orig_batch, H, W, 3], orig_batch 1 or B; alpha: uint8
+ * [alpha_batch, H, W], alpha_batch 1 or B, or NULL (alpha_batch 0) meaning 255 everywhere; dst: uint8 [B, H, W, 3], a buffer of
+ * its own.  Outside the box [x0, x1) x [y0, y1): the original's bytes.  Inside, with o the original's byte and a the alpha:
+ *   t = fk_image_to_u8_nhwc's clamp(x / 2 + 0.5, 0, 1) per decoded pixel,  g = the bilinear rule from (h, w) to the box on t,
+ *   c = g * 255;   a == 0: o, taken;   a == 255: c, taken;   otherwise (a * c + (255 - a) * o) / 255
+ * then rint(clamp(., 0, 255)).  The whole picture as the box at equal size with alpha 255 or NULL gives fk_image_to_u8_nhwc's bits. */
+int fk_image_overlay_u8(const void* img, int32_t img_is_fp32, int32_t h, int32_t w, const void* orig, int32_t orig_batch,
+                        const void* alpha, int32_t alpha_batch, void* dst, int32_t B, int32_t H, int32_t W, int32_t x0, int32_t y0,
+                        int32_t x1, int32_t y1, fk_stream_t stream);
+
 /* ---- LoRA merge (transformer.py: load_lora_adapter / set_adapters / set_lora_scale; the reference's pipeline is a
  * FluxLoraLoaderMixin, univa/utils/flux_pipeline.py:195).  Adapters become part of a bf16 weight [N, K]:
  *   out[n, k] = bf16_rne( float(base[n, k]) + sum_t scale_t * acc_t[n, k] ),  acc_t[n, k] = sum_j up_t[n, j] * down_t[j, k]

@@ -1,6 +1,7 @@
 """Timing of the masked-edit step on one MI355X (development aid; bench.py is the contract benchmark).
 
     python tools/bench_inpaint.py [--no-edit] [--out profiles/inpaint_timing.json]
+    python tools/bench_inpaint.py --overlay [--no-edit] [--out profiles/inpaint_overlay.json]
 
 1. ``fk_euler_inpaint_step_bf16`` (with a mask) beside ``fk_euler_step_bf16`` per launch at the 512^2 and 1024^2 edit shapes
    (S_tgt = 1024 / 4096 target rows in a [1, 2 S_tgt, 64] token buffer, C = 64): HIP events around windows of back-to-back
@@ -8,6 +9,11 @@
    microsecond kernel measure the launch rate as much as the kernel: the figure is time per launch, not kernel time.
 2. Edited images per second of a masked edit (half the picture repainted) beside the plain edit, full-size model, the
    flagship 512^2 workload of bench.py, alternating, each call ended by a device synchronise.
+
+``--overlay``: the same two measurements for the crop / feather / overlay kernels -- per-launch time of ``fk_mask_bbox_u8``,
+``fk_mask_blur_u8`` (sigma 4), ``fk_pixels_u8_box_to_nhwc_bf16`` and ``fk_image_overlay_u8`` at a 1024^2 picture with a 512^2 box,
+beside ``fk_pixels_u8_to_nhwc_bf16`` and ``fk_image_to_u8_nhwc`` at 512^2 in the same run, and images per second of a crop +
+overlay edit beside the plain masked edit (both return uint8 pixels).
 """
 import argparse
 import json
@@ -84,13 +90,85 @@ def edit_timing(reps=3):
                     graph=bool(pipe.use_graph)) for k, v in secs.items()}
 
 
+def overlay_kernel_timing(launches=500, windows=7):
+    P, S, box = 1024, 512, (256, 256, 768, 768)
+    g = torch.Generator(device="cuda").manual_seed(P)
+    pic = torch.randint(0, 256, (1, P, P, 3), generator=g, device="cuda", dtype=torch.uint8)
+    small = pic[:, :S, :S].contiguous()
+    mask = torch.zeros(1, P, P, device="cuda", dtype=torch.uint8)
+    mask[:, box[1]:box[3], box[0]:box[2]] = 255
+    img = (torch.rand(1, 3, S, S, generator=g, device="cuda") * 2 - 1).to(BF)
+    out4, ws = torch.empty(4, device="cuda", dtype=torch.int32), torch.empty(16384, device="cuda", dtype=torch.int32)
+    blurred, crop, over = torch.empty_like(mask), torch.empty(1, S, S, 32, device="cuda", dtype=BF), torch.empty_like(pic)
+    fns = {"fk_mask_bbox_u8": lambda: ops.mask_bbox(mask, 1, out=out4, ws=ws),
+           "fk_mask_blur_u8(sigma=4)": lambda: ops.mask_blur(mask, 4.0, out=blurred),        # + its tap upload and plane allocation
+           "fk_pixels_u8_box_to_nhwc_bf16": lambda: ops.pixels_box_to_nhwc(pic, box, S, S, 32, False, out=crop),
+           "fk_image_overlay_u8": lambda: ops.image_overlay(img, pic, mask, box, out=over),
+           "fk_pixels_u8_to_nhwc_bf16": lambda: ops.pixels_to_nhwc(small, S, S, 32, False),
+           "fk_image_to_u8_nhwc": lambda: ops.image_to_u8(img)}
+    bytes_ = {"fk_mask_bbox_u8": P * P, "fk_mask_blur_u8(sigma=4)": P * P * (1 + 4 + 4 + 1),
+              "fk_pixels_u8_box_to_nhwc_bf16": S * S * 3 + S * S * 32 * 2, "fk_image_overlay_u8": S * S * 3 * 2 + P * P * (3 + 1 + 3),
+              "fk_pixels_u8_to_nhwc_bf16": S * S * 3 + S * S * 32 * 2, "fk_image_to_u8_nhwc": S * S * 3 * (2 + 1)}
+    for fn in fns.values():
+        window(fn, 50)
+    samples = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            samples[k].append(window(fn, launches))
+    return {k: dict(picture=P, box=S, us_per_launch_median=statistics.median(v_), us_per_launch_min=min(v_),
+                    us_per_launch_max=max(v_), launches_per_window=launches, windows=windows, algorithmic_bytes=bytes_[k])
+            for k, v_ in samples.items()}
+
+
+def overlay_edit_timing(reps=3):
+    import bench
+    wl = "cfg2_single_512x512_28step"
+    pipe = bench.build_pipeline("cuda")
+    inp = bench.make_inputs(wl, "cuda", 0)
+    H, W = inp["H"], inp["W"]
+    lat = pipe._pack_latents(inp["noise"], inp["B"], 16, H // 8, W // 8)
+    g = torch.Generator().manual_seed(0)
+    pic = torch.randint(0, 256, (1, 2 * H, 2 * W, 3), generator=g, dtype=torch.uint8)     # a picture four times the model's area
+    mask = torch.zeros(2 * H, 2 * W, dtype=torch.uint8)
+    mask[H // 2:H // 2 + H, W // 2:W // 2 + W] = 255                                      # the box is the model's resolution
+    kw = dict(image=pic, mask_image=mask, prompt_embeds=inp["emb"], pooled_prompt_embeds=inp["pooled"], height=H, width=W,
+              num_inference_steps=28, guidance_scale=3.5, latents=lat, output_type="np_uint8", max_area=H * W, _auto_resize=False)
+    calls = {"masked_edit": lambda: pipe(**kw), "crop_overlay_edit": lambda: pipe(padding_mask_crop=0, **kw),
+             "crop_blur_overlay_edit": lambda: pipe(padding_mask_crop=32, mask_blur=4.0, **kw)}
+    for fn in calls.values():
+        fn()
+    torch.cuda.synchronize()
+    secs = {k: [] for k in calls}
+    for _ in range(reps):
+        for k, fn in calls.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            secs[k].append(time.perf_counter() - t0)
+    return {k: dict(workload=wl, picture=[2 * H, 2 * W], batch=inp["B"], images_per_s_median=inp["B"] / statistics.median(v),
+                    seconds=v, graph=bool(pipe.use_graph)) for k, v in secs.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-edit", action="store_true")
-    ap.add_argument("--out", default="profiles/inpaint_timing.json")
+    ap.add_argument("--overlay", action="store_true", help="time the crop / feather / overlay kernels and edits instead")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or ("profiles/inpaint_overlay.json" if args.overlay else "profiles/inpaint_timing.json")
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU: a timing from anything else says nothing")
+    if args.overlay:
+        res = {"kernels": overlay_kernel_timing()}
+        print(json.dumps(res["kernels"], indent=1), flush=True)
+        if not args.no_edit:
+            res["edit"] = overlay_edit_timing()
+            print(json.dumps(res["edit"], indent=1), flush=True)
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     res = {"step": [step_timing(S) for S in (1024, 4096)]}
     print(json.dumps(res["step"], indent=1), flush=True)
     if not args.no_edit:
