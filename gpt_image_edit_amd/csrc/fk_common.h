@@ -43,6 +43,18 @@ FK_DEV void round_bf_pair(float& a, float& b) {
   b = bf_hi(w);
 }
 
+// a b + c d with BOTH products rounded to fp32 before the sum, as a torch graph that multiplies and then adds computes it (the
+// rotary embedding of q, k: oracle/mmdit.py apply_rope).  __fmul_rn / __fadd_rn are plain operators to hipcc, and under its
+// default -ffp-contract=fast-honor-pragmas the expression becomes a multiply and an fma -- one product exact -- which moves
+// about 1e-5 of the bf16 outputs by an ulp (tests/test_forward_ref.py counts them).  The pragma is function-scoped: nothing
+// around a call site changes.
+FK_DEV float mul2_add(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+  const float ab = a * b;
+  const float cd = c * d;
+  return ab + cd;
+}
+
 FK_DEV float gelu_tanh_f(float x) {
   // torch: 0.5 * x * (1 + tanh(u)), u = sqrt(2/pi) * (x + 0.044715 x^3).  Since 0.5 * (1 + tanh(u)) = sigmoid(2u):
   //   y = x / (1 + exp(-2u)) = x * rcp(1 + exp2(-x * (c + c*k1*x^2))),  c = 2 * sqrt(2/pi) * log2(e)

@@ -263,8 +263,9 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
           re *= bf_lo(ww[e]);
           im *= bf_hi(ww[e]);
           round_bf_pair(re, im);
-          const float o0 = __fadd_rn(__fmul_rn(re, cs[e]), __fmul_rn(-im, sn[e]));
-          const float o1 = __fadd_rn(__fmul_rn(im, cs[e]), __fmul_rn(re, sn[e]));
+          // the same two rounded products and one sum as qkv_post_kernel (FK_EPI_QKV is held bit-identical to it)
+          const float o0 = mul2_add(re, cs[e], -im, sn[e]);
+          const float o1 = mul2_add(im, cs[e], re, sn[e]);
           ow[e] = pack_bf2(o0, o1);
         }
         // head-major row index in 32 bits (the launcher checks batches * heads * s_total < 2^31)

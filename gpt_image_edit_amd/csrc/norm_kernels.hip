@@ -183,10 +183,10 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(const bf16_t* qkv, bf16_t
       u32x4_t ow;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        // out = x*cos + rot(x)*sin with rot = (-x_imag, x_real); fp32, no contraction
+        // out = x*cos + rot(x)*sin with rot = (-x_imag, x_real); fp32, both products rounded before the sum (mul2_add)
         const float re = y[2 * e], im = y[2 * e + 1];
-        const float o0 = __fadd_rn(__fmul_rn(re, cs[2 * e]), __fmul_rn(-im, sn[2 * e]));
-        const float o1 = __fadd_rn(__fmul_rn(im, cs[2 * e + 1]), __fmul_rn(re, sn[2 * e + 1]));
+        const float o0 = mul2_add(re, cs[2 * e], -im, sn[2 * e]);
+        const float o1 = mul2_add(im, cs[2 * e + 1], re, sn[2 * e + 1]);
         ow[e] = pack_bf2(o0, o1);
       }
       *(u32x4_t*)(dst + (((int64_t)b * H + h) * S + s) * HD + chunk * 8) = ow;

@@ -87,7 +87,8 @@ def test_new_kernels_stay_in_registers_and_the_existing_mxfp8_kernels_keep_their
     old = {n: m for n, m in meta.items() if "gemm_mxfp8_kernel" in n}
     assert len(old) == 10
     for n, (scratch, vgprs, spills) in old.items():
-        want = 220 if "ELi256EEE" in n else (144 if "ILi6ELi128" in n else 132)     # the fused-QKV 256 x 128 form always took 144
+        # the fused-QKV 256 x 128 form took 144 while its RoPE was a product and an fma; 142 with both products rounded (mul2_add)
+        want = 220 if "ELi256EEE" in n else (142 if "ILi6ELi128" in n else 132)
         assert (scratch, spills, vgprs) == (0, 0, want), f"{n}: {scratch} B scratch, {spills} spills, {vgprs} VGPRs (was {want})"
     _, ln = _metadata("norm_kernels.hip", tmp_path)
     lnmx = {n: m for n, m in ln.items() if "ln_modulate_mx_kernel" in n}
