@@ -89,7 +89,19 @@ def gemm_last_variant():
     return int(_variant_slot().value)
 
 
-def _gemm_args(a, w, bias, out, epilogue, res, gate, out_fp32, alpha, qkv=None, layout=0):
+def _check_splitk_ws(splitk_ws):
+    """(buffer, slots) of a caller-owned split-K workspace: a contiguous uint8 tensor of at least ``slots`` x
+    FK_SPLITK_SLOT_BYTES bytes, 16-byte aligned.  The caller zeroes it once and keeps ``slots`` fixed for its lifetime (the
+    control words lie behind ``slots`` partial tiles and are never reset)."""
+    ws, slots = splitk_ws
+    _need_cuda(ws)
+    if (ws.dtype != torch.uint8 or not ws.is_contiguous() or int(slots) < 1 or ws.numel() < int(slots) * libfk.FK_SPLITK_SLOT_BYTES
+            or ws.data_ptr() % 16 != 0):
+        raise ValueError("splitk_ws: (contiguous 16-byte aligned uint8 tensor of >= slots * FK_SPLITK_SLOT_BYTES bytes, slots >= 1)")
+    return ws, int(slots)
+
+
+def _gemm_args(a, w, bias, out, epilogue, res, gate, out_fp32, alpha, qkv=None, layout=0, splitk_ws=None):
     _need_cuda(a, w, bias, out, res, gate)
     if a.dtype != BF16 or w.dtype != BF16:
         raise TypeError("fk_gemm_bf16 takes bf16 operands")
@@ -145,7 +157,10 @@ def _gemm_args(a, w, bias, out, epilogue, res, gate, out_fp32, alpha, qkv=None, 
     if int(out_fp32) == 1:       # fp32-class VAE encoder: fp32 bias / fp32 residual added to the fp32 output
         args.f32_flags = ((1 if bias is not None and bias.dtype == torch.float32 else 0) |
                           (2 if res is not None and res.dtype == torch.float32 and epilogue == FK_EPI_NONE else 0))
-    if K >= 6144 and N % 256 == 0 and M <= 256 * SPLITK_SLOTS and int(out_fp32) != 1 and layout == 0:   # the only shapes the planner may split
+    if splitk_ws is not None:    # the caller's own workspace instead of the stream's (any K: forced pairs / ranges below 6144)
+        ws, slots = _check_splitk_ws(splitk_ws)
+        args.splitk_ws, args.splitk_slots = ws.data_ptr(), slots
+    elif K >= 6144 and N % 256 == 0 and M <= 256 * SPLITK_SLOTS and int(out_fp32) != 1 and layout == 0:   # the only shapes the planner may split
         ws, slots = splitk_workspace(a.device)
         args.splitk_ws, args.splitk_slots = ws.data_ptr(), slots
     if epilogue == FK_EPI_QKV:
@@ -165,7 +180,8 @@ def _set_qkv(args, qkv):
     args.qkv_s_offset, args.qkv_s_total, args.qkv_heads = qkv["s_offset"], qkv["q_out"].shape[2], qkv["q_out"].shape[1]
 
 
-def gemm(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=None, out_fp32=False, alpha=1.0, qkv=None, layout=0):
+def gemm(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=None, out_fp32=False, alpha=1.0, qkv=None, layout=0,
+         splitk_ws=None):
     """out = epilogue(a @ w.T + bias).  a: [M,K] / [B,R,K] view; w: [N,K]; out likewise (may alias res).
 
     out_fp32: True / 1 = fp32(acc + bias) by the 128 x 128 register-staged kernel; 2 = the same from the LARGE-TILE kernels'
@@ -180,8 +196,10 @@ def gemm(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=None, o
     qkv (FK_EPI_QKV): dict(q_out, k_out [B,H,S_total,128], wq, wk [128], cs fp32 [S_total,64,2] (pack_rope; or cos, sin
     fp32 [S_total,128], packed per call), s_offset)
     -- the fused QKV projection: q / k thirds get RMSNorm + RoPE + head-major layout, the v third lands in out.
+    splitk_ws: ``(uint8 tensor, slots)`` -- a split-K workspace of the caller's own (zeroed once, >= slots x
+    FK_SPLITK_SLOT_BYTES bytes, ``slots`` fixed for its lifetime) instead of this stream's; None = the stream's at K >= 6144.
     """
-    args, out = _gemm_args(a, w, bias, out, epilogue, res, gate, out_fp32, alpha, qkv, layout)
+    args, out = _gemm_args(a, w, bias, out, epilogue, res, gate, out_fp32, alpha, qkv, layout, splitk_ws)
     libfk.check(libfk.load().fk_gemm_bf16(ctypes.byref(args), _stream()), "fk_gemm_bf16")
     return out
 
@@ -275,15 +293,15 @@ def _apply_gemm_launch(args):
     args.variant, args.plan, args.group_m, args.mfma = LAUNCH.gemm_variant, launch_plan(), LAUNCH.gemm_group_m, LAUNCH.gemm_mfma
 
 
-def gemm_grouped(problems, epilogue=FK_EPI_NONE):
+def gemm_grouped(problems, epilogue=FK_EPI_NONE, splitk_ws=None):
     """Several independent GEMMs sharing (N, K, epilogue) in ONE launch.  ``problems`` is a list of dicts
-    with the keyword arguments of :func:`gemm` (a, w, bias, out, res, gate); returns the outputs."""
+    with the keyword arguments of :func:`gemm` (a, w, bias, out, res, gate); returns the outputs.  splitk_ws: as :func:`gemm`."""
     n = len(problems)
     arr = (GemmArgs * n)()
     outs = []
     for i, pr in enumerate(problems):
         args, out = _gemm_args(pr["a"], pr["w"], pr.get("bias"), pr.get("out"), epilogue, pr.get("res"),
-                               pr.get("gate"), False, 1.0, pr.get("qkv"), pr.get("layout", 0))
+                               pr.get("gate"), False, 1.0, pr.get("qkv"), pr.get("layout", 0), splitk_ws)
         arr[i] = args
         outs.append(out)
     libfk.check(libfk.load().fk_gemm_bf16_grouped(arr, n, _stream()), "fk_gemm_bf16_grouped")

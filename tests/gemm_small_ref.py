@@ -31,11 +31,12 @@ def _fp32_exact(y):
     return torch.equal(y.to(F32).to(F64), y)
 
 
-def expected(a, w, bias=None):
+def expected(a, w, bias=None, product=None):
     """fp64 `a @ w^T (+ bias)` over the flattened rows of `a`, as fp64.  Asserts what makes it THE value of an fp32
     accumulation in any order: |y| < 2^24 and y representable in fp32 (integers, or integers times a power of two); and
-    that no value could be mistaken for untouched memory."""
-    y = a.to(F64).reshape(-1, a.shape[-1]) @ w.to(F64).T
+    that no value could be mistaken for untouched memory.  product: an earlier `expected(a, w)` of the same operands, so a
+    large product is formed once."""
+    y = a.to(F64).reshape(-1, a.shape[-1]) @ w.to(F64).T if product is None else product
     if bias is not None:
         y = y + bias.to(F64)
     assert y.abs().max().item() < 2 ** 24, "sums leave the range in which fp32 holds every integer"
@@ -175,8 +176,9 @@ def guarded(rows, N, dtype=BF, device="cpu"):
 
 
 def check_guarded(buf, idx, want, what):
-    """Equality of buf[idx] with `want` and an untouched sentinel everywhere else."""
-    got = buf.cpu()
+    """Equality of buf[idx] with `want` and an untouched sentinel everywhere else.  (A `want` that lies on the device is
+    compared there: the outputs of tens of millions of elements.)"""
+    got = buf if want.is_cuda else buf.cpu()
     inner = got[idx]
     want = want.reshape(inner.shape)
     assert inner.dtype == want.dtype, f"{what}: dtype {inner.dtype} vs {want.dtype}"
@@ -206,3 +208,36 @@ def check_ulp(buf, idx, want, what, max_ulp=1):
     mask[idx] = False
     assert (got[mask] == SENTINEL).all(), f"{what}: the guard band around C was written"
     return exact, worst
+
+
+# ---- deliberate mistakes of the kind a tiled kernel makes (the CPU tests plant them and expect the checks above to object) -----
+# d: dict(a [B, rows, K], w, bias, res, gate, y = expected(a, w, bias)); finish: y -> the output a kernel would store.
+
+def _drop_last_k_tile(d, finish):
+    K = d["a"].shape[-1]
+    return finish(expected(d["a"][..., :K - 64], d["w"][:, :K - 64], d["bias"]))
+
+
+def _swap_rows(d, finish):
+    out = finish(d["y"]).clone()
+    out[[3, 77]] = out[[77, 3]]
+    return out
+
+
+def _shift_column_group(d, finish):
+    out = finish(d["y"]).clone()
+    out[:, 8:16] = finish(d["y"])[:, 16:24]
+    return out
+
+
+def _gate_of_the_tile(d, finish):
+    """The rows of batch 1 that lie in the 128-row tile which began in batch 0 take batch 0's gate."""
+    rows = d["a"].shape[1]
+    right = finish(d["y"])
+    wrong = epi_gate_res(d["y"], d["res"], d["gate"][[0] * d["gate"].shape[0]], rows)
+    out = right.clone()
+    out[rows:128] = wrong[rows:128]
+    return out
+
+
+MISTAKES = [_drop_last_k_tile, _swap_rows, _shift_column_group, _gate_of_the_tile]

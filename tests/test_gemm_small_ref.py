@@ -110,32 +110,7 @@ def test_guarded_views():
 
 # ---- the comparison functions see the mistakes a tiled kernel makes --------------------------------------------------------
 
-def _drop_last_k_tile(d, finish):
-    return finish(R.expected(d["a"][..., :K - 64], d["w"][:, :K - 64], d["bias"]))
-
-
-def _swap_rows(d, finish):
-    out = finish(d["y"]).clone()
-    out[[3, 77]] = out[[77, 3]]
-    return out
-
-
-def _shift_column_group(d, finish):
-    out = finish(d["y"]).clone()
-    out[:, 8:16] = finish(d["y"])[:, 16:24]
-    return out
-
-
-def _gate_of_the_tile(d, finish):
-    """Rows 70 .. 127 lie in batch 1 but in the tile that began in batch 0: they take batch 0's gate."""
-    right = finish(d["y"])
-    wrong = R.epi_gate_res(d["y"], d["res"], d["gate"][[0, 0]], ROWS)
-    out = right.clone()
-    out[ROWS:128] = wrong[ROWS:128]
-    return out
-
-
-MISTAKES = [_drop_last_k_tile, _swap_rows, _shift_column_group, _gate_of_the_tile]
+MISTAKES = R.MISTAKES
 
 
 def _in_buffer(out):
