@@ -464,6 +464,9 @@ extern "C" int fk_ln_modulate_bwd_bf16(const void* x, fk_rows xr, const void* dn
                "fk_ln_modulate_bwd_bf16: pointers must be 16-byte aligned");
   FK_CHECK_ARG(xr.ld % 8 == 0 && dnr.ld % 8 == 0 && dxo.ld % 8 == 0 && mod_batch_stride % 8 == 0 && (!dx_in || dxi.ld % 8 == 0),
                "fk_ln_modulate_bwd_bf16: strides must be multiples of 8 elements");
+  // one finalising pass writes both sums: the 2D-wide partial row is one vector, so dscale has to follow dshift at +D
+  FK_CHECK_ARG(dscale == dshift + D,
+               "fk_ln_modulate_bwd_bf16: dscale must be dshift + D (the (shift, scale) chunk pair of the modulation vector)");
   hipStream_t stream = (hipStream_t)stream_;
   int chunks = pick_chunks(rows_per_batch, 4 * 4, 512);
   while (chunks > 1 && (int64_t)B * chunks * 2 * D > fk_bwd_ws_floats()) chunks /= 2;
@@ -486,13 +489,7 @@ extern "C" int fk_ln_modulate_bwd_bf16(const void* x, fk_rows xr, const void* dn
   FK_CHECK_LAUNCH("fk_ln_modulate_bwd_bf16");
   // partial rows are [b][chunk][2][D]: dshift = first D of each, dscale = second D
   const dim3 fgrid((2 * D + 63) / 64, B);
-  // one pass writes both: treat the 2D-wide row as one vector when dscale follows dshift at +D ...
-  if (dscale == dshift + D) {
-    hipLaunchKernelGGL(finalize_partials_kernel, fgrid, block, 0, stream, ws, dshift, dmod_batch_stride, chunks, 2 * D, 0);
-  } else {
-    fk_set_error("fk_ln_modulate_bwd_bf16: dscale must be dshift + D (the (shift, scale) chunk pair of the modulation vector)");
-    return FK_EINVAL;
-  }
+  hipLaunchKernelGGL(finalize_partials_kernel, fgrid, block, 0, stream, ws, dshift, dmod_batch_stride, chunks, 2 * D, 0);
   FK_CHECK_LAUNCH("fk_ln_modulate_bwd_bf16 (finalize)");
   return FK_OK;
 }
