@@ -37,8 +37,11 @@ UP_STEP, DN_STEP = 32, 64          # csrc/lora_grad.hip: LG_UP_STEP, LG_DN_STEP
 # (N, K, r) of tests/test_hip_lora_grad_kernel.py.  The last two are the smallest shapes at which a reduction is split into two
 # partials (csrc/lora_grad.hip's header: K = 257 second UP chunk, N = 129 second DOWN chunk), rounded up to K % 8 == 0 / a
 # ragged N; N = 65 / K = 33 / K = 129 (second strips and steps) are crossed by (65, 136, 33).
+# The launcher picks the kernel's rank tile by rank_pad / 32 = ceil(r / 32) in 1 .. 4 (RT = 2, 4, 6, 8): the last three are the
+# first rank, an ordinary rank and the last rank of the third tile (tests/test_lora_grad_ref.py holds the list to all four).
+RANK_TILE, MAX_RANK = 32, 128
 SHAPES = [(1, 8, 1), (16, 32, 32), (63, 72, 5), (65, 136, 33), (128, 64, 128), (64, 3072, 16), (3072, 64, 16), (3072, 3072, 16),
-          (16, 264, 8), (131, 16, 8)]
+          (16, 264, 8), (131, 16, 8), (65, 136, 65), (131, 72, 80), (128, 64, 96)]
 
 
 def f32(x):

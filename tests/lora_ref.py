@@ -33,10 +33,13 @@ import torch
 U32 = 2.0 ** -24
 BF16 = torch.bfloat16
 
-# (N, K, r) of tests/test_hip_lora_kernel.py
+# (N, K, r) of tests/test_hip_lora_kernel.py.  The kernel walks r_pad = 32 * ceil(r / 32) in trips of 32, 1 .. 4 of them; the last
+# two shapes are the first and the last rank that take three (tests/test_lora_ref.py holds the list to all four trip counts).
+RANK_TILE, MAX_RANK = 32, 128
 SHAPES = [(1, 8, 1), (16, 32, 32), (63, 72, 5), (65, 136, 33), (128, 64, 128), (64, 3072, 16), (3072, 64, 16),
-          (3072, 12288, 64)]
+          (3072, 12288, 64), (65, 136, 65), (128, 64, 96)]
 MIXED_RANKS = (5, 32, 33, 128)
+MIXED_RANKS_96 = (96, 5, 80, 33)        # three trips first, then one, three again, two
 
 
 def r_pad(rank):

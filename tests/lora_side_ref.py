@@ -43,7 +43,12 @@ T_STEP, U_STEP, M_STEP = 32, 64, 64          # csrc/lora_side_grad.hip: LS_T_STE
 # (B, R, N, K, r) of tests/test_hip_lora_side_kernel.py.  csrc/lora_side_grad.hip's header: M = 65 second stage-1 strip and
 # second stage-2 step, K = 33 / N = 65 second stage-1 step, N = 129 / K = 129 second stage-2 strip, r = 33 second pair of rank
 # tiles -- all crossed by the ragged (1, 65, 131, 136, 33); M = 129 splits the m reduction of both roles into two chunks.
-SHAPES = [(1, 1, 1, 8, 1), (1, 64, 16, 32, 32), (1, 65, 131, 136, 33), (1, 129, 16, 8, 8), (3, 43, 9, 20, 4), (2, 96, 128, 64, 128)]
+# The launcher picks the kernels' rank tile by rank_pad / 32 = ceil(r / 32) in 1 .. 4 (RT = 2, 4, 6, 8): r = 65, 80 and 96 are the
+# first rank, an ordinary rank and the last rank of the third tile -- ragged everywhere; batched with both stage-2 reductions
+# split (M = 140); with a second chunk (M = 129).  tests/test_lora_side_ref.py holds the list to all four tiles.
+RANK_TILE, MAX_RANK = 32, 128
+SHAPES = [(1, 1, 1, 8, 1), (1, 64, 16, 32, 32), (1, 65, 131, 136, 33), (1, 129, 16, 8, 8), (3, 43, 9, 20, 4), (2, 96, 128, 64, 128),
+          (1, 65, 131, 136, 65), (2, 70, 72, 40, 80), (1, 129, 136, 72, 96)]
 PRODUCTION = (1, 2560, 3072, 3072, 16)
 
 

@@ -226,7 +226,8 @@ def test_single_valid_key(ops):
 def test_masked_first_tile_with_large_logits(ops):
     """first-empty with q scaled by 8: the matched rows' logits sit ~117 log2 units above the typical score, at the edge of the
     exponent window around a reference that must come from tile 1 -- rows that outgrow it send the workgroup through the
-    restart (exact maxima from the K-only pre-pass, which has to skip the masked tile as well).  Whether it ran is not asserted;
+    restart (exact maxima from the K-only pre-pass, which has to skip the masked tile as well).  Whether it ran is not asserted
+    (tests/test_hip_attention_orders.py, M6 / M7, has inputs for which it must);
     that lse of every row is the fp64 log-sum-exp over the valid keys is (and o at the restart test's bound, 3e-2 / 1e-3 of absmax)."""
     S = 320
     q, k, v, dout = ar.make_inputs(B, H, S, seed=24800)

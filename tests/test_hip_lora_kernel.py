@@ -1,9 +1,10 @@
 """fk_lora_merge_bf16 on the GPU against tests/lora_ref.py: the fp64 merge within the bound derived there, exact cases at
 0 ulp, the in-place form, strided views with guards, untouched inputs and every refusal.
 
-Observed worst |out - ref| / bound on an MI355X: 0.9949 over the eight shapes (N = 3072, K = 64, r = 16), 0.9893 over the
+Observed worst |out - ref| / bound on an MI355X: 0.9949 over the ten shapes (N = 3072, K = 64, r = 16), 0.9893 over the
 mixed-rank cases -- the bf16 rounding's half ulp, 2^-8 |ref| just above a power of two, is nearly all of it; the smallest is
-0.4643 at (1, 8, 1)."""
+0.4643 at (1, 8, 1).  The three-trip ranks: 0.9870 at (65, 136, 65), 0.9769 at (128, 64, 96), 0.9583 / 0.9762 with the ranks
+(96, 5, 80, 33)."""
 import ctypes
 
 import pytest
@@ -42,9 +43,17 @@ def test_mixed_ranks_and_negative_scales(ops, N, K, n_terms):
     R.check(f"{n_terms} terms", ops.lora_merge(base, terms, out=torch.empty_like(base)), base, terms)
 
 
+@pytest.mark.parametrize("N,K", [(65, 136), (128, 64)])
+def test_mixed_ranks_with_a_rank_96_term(ops, N, K):
+    """(96, 5, 80, 33): three trips of the r_pad loop, one, three again, two -- the trip count changes from term to term."""
+    base, terms = R.data(N, K, R.MIXED_RANKS_96, seed=7 * 96, device=DEV)
+    assert terms[1][2] < 0
+    R.check("4 terms, 96 first", ops.lora_merge(base, terms, out=torch.empty_like(base)), base, terms)
+
+
 @pytest.mark.parametrize("N,K,ranks", [(1, 8, (1,)), (16, 32, (32,)), (63, 72, (5,)), (65, 136, (33,)), (128, 64, (128,)),
                                        (65, 136, R.MIXED_RANKS), (130, 200, (128, 5, 33)), (64, 3072, (16, 32)),
-                                       (3072, 64, (16,))])
+                                       (3072, 64, (16,)), (63, 72, (80,)), (130, 200, (96, 5, 65))])
 def test_exact_cases_are_0_ulp(ops, N, K, ranks):
     base, terms = R.exact_data(N, K, ranks, seed=N + K, device=DEV)
     want = R.exact_merge(base, terms)
@@ -70,8 +79,8 @@ def test_all_scales_zero_gives_base(ops):
 
 @pytest.mark.parametrize("pad", [8, 3])       # row strides that keep / break the 16-byte alignment of the rows
 @pytest.mark.parametrize("N,K", [(63, 72), (65, 136)])
-def test_strided_views_and_guards(ops, N, K, pad):
-    base0, terms0 = R.exact_data(N, K, (5, 33), seed=pad + N, device=DEV)
+def test_strided_views_and_guards(ops, N, K, pad, ranks=(5, 33)):
+    base0, terms0 = R.exact_data(N, K, ranks, seed=pad + N, device=DEV)
     want = R.exact_merge(base0, terms0)
     S = 7.0                                   # sentinel
     big_base = torch.full((N + 2, K + pad + 8), S, device=DEV, dtype=BF16)
@@ -98,6 +107,12 @@ def test_strided_views_and_guards(ops, N, K, pad):
     chk = big_base.clone()
     chk[1:N + 1, 8:8 + K] = S
     assert torch.equal(chk, keep_base)
+
+
+@pytest.mark.parametrize("pad", [8, 3])
+def test_strided_views_and_guards_at_rank_80(ops, pad):
+    """The same views with a three-trip term between a one-trip and a two-trip one."""
+    test_strided_views_and_guards(ops, 65, 136, pad, ranks=(5, 80, 33))
 
 
 def test_refusals_write_nothing(ops):

@@ -28,7 +28,16 @@ def test_fp32_emulation_is_inside_the_bound(N, K, r):
     R.check("emulation", du, dd, dw, up, down, s)
 
 
-@pytest.mark.parametrize("N,K,r", R.SHAPES[:5])
+def test_shapes_reach_every_rank_tile():
+    """The launcher instantiates one kernel per ceil(r / 32) in 1 .. 4: the GPU files' shape list must reach each of them, the
+    first and the last rank of the tile that went unvisited longest (65, 96) by name."""
+    ranks = [s[-1] for s in R.SHAPES]
+    assert all(1 <= r <= R.MAX_RANK for r in ranks)
+    assert {-(-r // R.RANK_TILE) for r in ranks} == set(range(1, R.MAX_RANK // R.RANK_TILE + 1)) == {1, 2, 3, 4}
+    assert {65, 96} <= set(ranks)
+
+
+@pytest.mark.parametrize("N,K,r", R.SHAPES[:5] + R.SHAPES[-3:])
 def test_exact_cases_are_exact(N, K, r):
     dw, up, down, s = R.exact_data(N, K, r, seed=N + K)
     fu, fd = R.exact_grads(dw, up, down, s)

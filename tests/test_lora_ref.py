@@ -12,19 +12,40 @@ def test_emulation_is_inside_the_bound(N, K, r):
     assert R.check("emulated", R.emulate(base, terms), base, terms) <= 1.0
 
 
+def test_shapes_reach_every_rank_tile():
+    """The merge kernel walks ceil(r / 32) = 1 .. 4 trips of its r_pad loop: the GPU file's shape list must reach each count,
+    the first and the last rank of the one that went unvisited longest (65, 96) by name."""
+    ranks = [s[-1] for s in R.SHAPES]
+    assert all(1 <= r <= R.MAX_RANK for r in ranks)
+    assert {-(-r // R.RANK_TILE) for r in ranks} == set(range(1, R.MAX_RANK // R.RANK_TILE + 1)) == {1, 2, 3, 4}
+    assert {65, 96} <= set(ranks)
+
+
 @pytest.mark.parametrize("n_terms", [1, 2, 3, 4])
 def test_emulation_with_mixed_ranks_is_inside_the_bound(n_terms):
     base, terms = R.data(65, 136, R.MIXED_RANKS[:n_terms], seed=n_terms)
     assert R.check("emulated mixed", R.emulate(base, terms), base, terms) <= 1.0
 
 
-def test_exact_cases_are_exact_in_any_order():
-    base, terms = R.exact_data(65, 136, R.MIXED_RANKS, seed=3)
+@pytest.mark.parametrize("N,K", [(65, 136), (128, 64)])
+def test_emulation_with_a_rank_96_term_among_others_is_inside_the_bound(N, K):
+    base, terms = R.data(N, K, R.MIXED_RANKS_96, seed=7 * 96)       # the data of the GPU file's case
+    assert terms[1][2] < 0
+    assert R.check("emulated mixed, 96", R.emulate(base, terms), base, terms) <= 1.0
+
+
+def test_exact_cases_are_exact_in_any_order(ranks=R.MIXED_RANKS, N=65, K=136, seed=3):
+    base, terms = R.exact_data(N, K, ranks, seed=seed)
     want = R.exact_merge(base, terms)
     assert torch.equal(R.emulate(base, terms), want)
     flipped = [(up.flip(1), down.flip(0), s) for up, down, s in terms]        # the rank summed in the opposite order
     assert torch.equal(R.emulate(base, flipped), want)
     assert not torch.equal(want, base)
+
+
+@pytest.mark.parametrize("N,K,ranks", [(63, 72, (80,)), (130, 200, (96, 5, 65))])
+def test_exact_cases_with_three_trips_are_exact_in_any_order(N, K, ranks):
+    test_exact_cases_are_exact_in_any_order(ranks, N, K, seed=N + K)     # the data of the GPU file's cases
 
 
 def _case():

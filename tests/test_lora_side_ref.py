@@ -43,6 +43,15 @@ def test_exact_cases_are_exact(B, R_, N, K, r):
     assert torch.equal(du, fu) and torch.equal(dd, fd)
 
 
+def test_shapes_reach_every_rank_tile():
+    """The launcher instantiates one kernel per ceil(r / 32) in 1 .. 4: the GPU files' shape list must reach each of them, the
+    first and the last rank of the tile that went unvisited longest (65, 96) by name."""
+    ranks = [s[-1] for s in R.SHAPES]
+    assert all(1 <= r <= R.MAX_RANK for r in ranks)
+    assert {-(-r // R.RANK_TILE) for r in ranks} == set(range(1, R.MAX_RANK // R.RANK_TILE + 1)) == {1, 2, 3, 4}
+    assert {65, 96} <= set(ranks)
+
+
 def test_the_exact_condition_is_checked():
     x, dy, up, down, s = R.exact_data(1, 64, 8, 4096 + 64, 2, seed=0)
     x, down = x.abs().clamp_min(4), down.abs().clamp_min(4)          # |T| = 16 K >= 2^16
