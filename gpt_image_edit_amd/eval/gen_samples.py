@@ -124,9 +124,10 @@ def build_parser():
                    help="mxfp8 only: let the long-K block GEMMs run as split-K pairs (FK_MX_SPLITK=1; default off)")
     p.add_argument("--mx_fused_attn", action="store_true",
                    help="mxfp8 with FK_MX_FUSED_QUANT=1 only: the attention emits MXFP8 itself (FK_MX_FUSED_ATTN=1; default off)")
-    from ..serve.cli import add_solver_argument, add_step_cache_arguments
+    from ..serve.cli import add_resample_argument, add_solver_argument, add_step_cache_arguments
     add_step_cache_arguments(p)
     add_solver_argument(p)
+    add_resample_argument(p)
     from ..lora import add_cli_arguments
     add_cli_arguments(p)
     return p
@@ -205,7 +206,7 @@ def main(args):
                        pooled_prompt_embeds=pooled, height=gen_h, width=gen_w, num_inference_steps=args.num_inference_steps,
                        guidance_scale=args.guidance_scale, num_images_per_prompt=args.num_images_per_prompt,
                        **cli.step_cache_kwargs(args), **cli.lora_kwargs(args),
-                       **cli.latent_state_kwargs(args))
+                       **cli.latent_state_kwargs(args), **cli.resample_kwargs(args))
             return out.images[0], out.latents[:1]
     res = run(args, edit_fn, rank, world)
     print(f"[rank {rank}/{world}] edited {len(res['done'])}, skipped {len(res['skipped'])} existing", flush=True)

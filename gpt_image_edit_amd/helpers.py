@@ -84,6 +84,82 @@ def gaussian_taps(sigma):
     return torch.tensor([v / total for v in w], dtype=torch.float64).to(torch.float32)
 
 
+FK_RESAMPLE_MAX_KSIZE = 513     # include/fk.h: lanczos down to 1/85, bicubic to 1/128, bilinear to 1/256
+RESAMPLE_PRECISION_BITS = 22    # coefficients are fixed point with 22 fractional bits; 2^21 rounds the shifted sum
+
+
+def _sinc(x):
+    return 1.0 if x == 0.0 else math.sin(x * math.pi) / (x * math.pi)
+
+
+def _bilinear_filter(x):
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _bicubic_filter(x):
+    a, x = -0.5, abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _lanczos_filter(x):
+    return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+RESAMPLE_FILTERS = {"bilinear": (_bilinear_filter, 1.0), "bicubic": (_bicubic_filter, 2.0), "lanczos": (_lanczos_filter, 3.0)}
+_resample_cache = {}
+
+
+def resample_coeffs(n_in, n_out, filter):
+    """The tables of one pass of Pillow's 8-bit antialiased resize along an axis of ``n_in`` samples resized to ``n_out``
+    (include/fk.h: fk_resample_pass_u8 states the rule): ``(bounds, kk, ksize)`` with ``bounds`` int32 [n_out, 2] holding
+    ``(xmin, xmax)`` of each output's source window and ``kk`` int32 [n_out, ksize] its fixed-point weights (2^22 = 1), zero past
+    ``xmax - xmin``.  Float64 on the host, operation by operation in the rule's order (the sum of the weights in ascending tap
+    order; ``math.sin``, not a vector library's); cached, so the tensors are shared: do not write to them.  Raises when the window
+    is wider than ``FK_RESAMPLE_MAX_KSIZE`` or when a row's weights could overflow the kernels' int32 accumulator."""
+    n_in, n_out = int(n_in), int(n_out)
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"`filter` is one of {sorted(RESAMPLE_FILTERS)}, not {filter!r}")
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"cannot resample {n_in} samples to {n_out}")
+    key = (n_in, n_out, filter)
+    if key in _resample_cache:
+        return _resample_cache[key]
+    f, filter_support = RESAMPLE_FILTERS[filter]
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = filter_support * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    if ksize > FK_RESAMPLE_MAX_KSIZE:
+        raise ValueError(f"{filter} from {n_in} to {n_out} samples needs windows of {ksize} taps: more than "
+                         f"FK_RESAMPLE_MAX_KSIZE = {FK_RESAMPLE_MAX_KSIZE}")
+    ss = 1.0 / fs
+    one = 1 << RESAMPLE_PRECISION_BITS
+    bounds = torch.zeros((n_out, 2), dtype=torch.int32)
+    kk = torch.zeros((n_out, ksize), dtype=torch.int32)
+    for i in range(n_out):
+        center = (i + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), n_in)
+        w = [f((t + xmin - center + 0.5) * ss) for t in range(xmax - xmin)]
+        total = 0.0
+        for v in w:
+            total += v
+        if total != 0.0:
+            w = [v / total for v in w]
+        row = [int(v * one - 0.5) if v < 0 else int(v * one + 0.5) for v in w]
+        if 255 * sum(abs(v) for v in row) + (one >> 1) >= 1 << 31:
+            raise ValueError(f"{filter} from {n_in} to {n_out} samples: the weights of output {i} overflow an int32 sum")
+        bounds[i, 0], bounds[i, 1] = xmin, xmax
+        kk[i, :len(row)] = torch.tensor(row, dtype=torch.int32)
+    _resample_cache[key] = (bounds, kk, ksize)
+    return _resample_cache[key]
+
+
 def _grow(lo, hi, want, limit):
     """[lo, hi) grown to `want` samples about its centre (the odd one to the far side), shifted back inside [0, limit) and, if it
     is still larger, clamped to it."""

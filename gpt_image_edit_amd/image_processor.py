@@ -9,6 +9,10 @@ when the pixels are still uint8:
 * ``pixels_to_latent_input``: uint8 NHWC -> normalised, nearest-resized NHWC bf16 (``fk_pixels_u8_to_nhwc_bf16``),
   i.e. ``cli.prepare_condition_images`` + ``resize`` + ``preprocess`` + ``.to(bf16)`` in one gather;
 * ``postprocess(..., "pil" | "np_uint8")``: decoder output -> uint8 NHWC (``fk_image_to_u8_nhwc``).
+
+The gather is nearest, as the reference's tensor route is.  ``config.resample`` ("lanczos") names what diffusers does for PIL inputs;
+the pipeline honours a filter when its call names one (``resample=``): ``ops.resample_u8`` -- Pillow's antialiased byte resize,
+byte for byte -- runs first and ``pixels_to_latent_input`` then gathers at equal size.
 """
 import numpy as np
 import torch

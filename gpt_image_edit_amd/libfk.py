@@ -144,6 +144,7 @@ class LoraTerm(ctypes.Structure):              # fk_lora_term
 
 
 FK_LORA_MAX_TERMS, FK_LORA_MAX_RANK = 4, 128
+FK_RESAMPLE_MAX_KSIZE = 513               # include/fk.h: widest window of fk_resample_pass_u8
 
 # symbol -> (restype, argtypes); must list every entry point of include/fk.h
 SIGNATURES = {
@@ -248,6 +249,8 @@ SIGNATURES = {
     "fk_mask_blur_u8": (c_i32, [c_vp] * 4 + [c_i32] * 4 + [c_vp]),
     "fk_pixels_u8_box_to_nhwc_bf16": (c_i32, [c_vp, c_vp] + [c_i32] * 11 + [c_vp]),
     "fk_image_overlay_u8": (c_i32, [c_vp] + [c_i32] * 3 + [c_vp, c_i32, c_vp, c_i32, c_vp] + [c_i32] * 7 + [c_vp]),
+    "fk_resample_pass_u8": (c_i32, [c_vp, c_i64, c_i64, c_vp] + [c_i32] * 6 + [c_vp, c_vp, c_i32, c_vp]),
+    "fk_bytes_overlay_u8": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp] + [c_i32] * 7 + [c_vp]),
     "fk_double_block_fwd": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(DoubleBlockWeights), c_vp, c_i64, c_vp]),
     "fk_single_block_fwd": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(SingleBlockWeights), c_vp, c_i64, c_vp]),
     "fk_single_block_bwd": (c_i32, [ctypes.POINTER(BwdWs), ctypes.POINTER(BlockSaved), ctypes.POINTER(SingleBlockWeights),

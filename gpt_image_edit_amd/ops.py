@@ -1601,6 +1601,92 @@ def image_overlay(img, orig_u8, alpha_u8, box, out=None):
     return out
 
 
+# ---- antialiased byte resize and byte paste-back (include/fk.h: fk_resample_pass_u8, fk_bytes_overlay_u8) ---------------------------
+_resample_tables = {}       # (n_in, n_out, filter, device, axis) -> (bounds, kk) on the device, kk tap-major for axis 1
+
+
+def _resample_device_tables(n_in, n_out, filter, device, axis):
+    key = (n_in, n_out, filter, str(device), axis)
+    if key not in _resample_tables:
+        bounds, kk, ksize = helpers.resample_coeffs(n_in, n_out, filter)
+        kk = kk.t().contiguous() if axis == 1 else kk
+        _resample_tables[key] = (bounds.to(device), kk.to(device), ksize)
+    return _resample_tables[key]
+
+
+def resample_pass_u8(src_view, axis, n_out, filter, out=None):
+    """One pass of :func:`resample_u8` along ``axis`` (1: horizontal, 0: vertical) of a uint8 view [B, H, W, C]."""
+    _need_cuda(src_view, out)
+    if (src_view.dtype != torch.uint8 or src_view.dim() != 4 or src_view.shape[3] not in (1, 3) or src_view.stride(3) != 1
+            or src_view.stride(2) != src_view.shape[3]):
+        raise TypeError("resample_u8 takes a uint8 [B, H, W, C] view, C 1 or 3, whose pixels are contiguous within a row")
+    if axis not in (0, 1):
+        raise ValueError(f"axis is 0 (vertical) or 1 (horizontal), not {axis!r}")
+    B, H, W, C = src_view.shape
+    shape = (B, H, n_out, C) if axis == 1 else (B, n_out, W, C)
+    if out is None:
+        out = torch.empty(shape, device=src_view.device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 {shape} tensor")
+    bounds, kk, ksize = _resample_device_tables(W if axis == 1 else H, n_out, filter, src_view.device, axis)
+    libfk.check(libfk.load().fk_resample_pass_u8(_ptr(src_view), src_view.stride(0), src_view.stride(1), _ptr(out), B, H, W, C, axis,
+                                                 n_out, _ptr(bounds), _ptr(kk), ksize, _stream()), "fk_resample_pass_u8")
+    return out
+
+
+def resample_u8(src_view, out_h, out_w, filter, out=None):
+    """Pillow's 8-bit antialiased resize (``filter``: "bilinear" | "bicubic" | "lanczos"), byte for byte: uint8 view [B, H, W, C]
+    (C 1 or 3; any row and batch stride, so a crop is the slice ``pic[:, y0:y1, x0:x1]``) -> contiguous uint8 [B, out_h, out_w, C].
+    Horizontal pass into a uint8 intermediate, then the vertical pass; a pass whose axis keeps its size is skipped.  With both
+    skipped and a contiguous source the source itself is returned (copied into ``out`` when one is given) and nothing is launched."""
+    if filter not in helpers.RESAMPLE_FILTERS:
+        raise ValueError(f"`filter` is one of {sorted(helpers.RESAMPLE_FILTERS)}, not {filter!r}")
+    _need_cuda(src_view, out)
+    if src_view.dtype != torch.uint8 or src_view.dim() != 4:
+        raise TypeError("resample_u8 takes a uint8 [B, H, W, C] view, C 1 or 3, whose pixels are contiguous within a row")
+    B, H, W, C = src_view.shape
+    out_h, out_w = int(out_h), int(out_w)
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (B, out_h, out_w, C) or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 {(B, out_h, out_w, C)} tensor")
+    if (out_h, out_w) == (H, W):
+        if out is not None:
+            return out.copy_(src_view)
+        return src_view if src_view.is_contiguous() else src_view.contiguous()
+    x = src_view
+    if out_w != W:
+        x = resample_pass_u8(x, 1, out_w, filter, out=out if out_h == H else None)
+    if out_h != H:
+        x = resample_pass_u8(x, 0, out_h, filter, out=out)
+    return x
+
+
+def bytes_overlay(res, orig_u8, alpha_u8, box, out=None):
+    """:func:`image_overlay` on bytes: ``res`` uint8 [B, y1-y0, x1-x0, 3] (the result already at the box's size) blended over the
+    original picture uint8 [1 or B, H, W, 3] with ``alpha_u8`` (uint8 [1 or B, H, W], None = 255 everywhere) -> uint8 [B, H, W, 3]."""
+    _need_cuda(res, orig_u8, alpha_u8, out)
+    x0, y0, x1, y1 = _box(box)
+    if res.dtype != torch.uint8 or res.dim() != 4 or res.shape[3] != 3 or not res.is_contiguous():
+        raise TypeError("bytes_overlay takes the result as a contiguous uint8 [B, h, w, 3] tensor")
+    if orig_u8.dtype != torch.uint8 or orig_u8.dim() != 4 or orig_u8.shape[3] != 3 or not orig_u8.is_contiguous():
+        raise TypeError("bytes_overlay takes the original as a contiguous uint8 [1 or B, H, W, 3] tensor")
+    B = res.shape[0]
+    N, H, W, _ = orig_u8.shape
+    if tuple(res.shape[1:3]) != (y1 - y0, x1 - x0):
+        raise ValueError(f"the result is {res.shape[1]} x {res.shape[2]}, the box {y1 - y0} x {x1 - x0}")
+    Bm = 0
+    if alpha_u8 is not None:
+        Bm, Ha, Wa = _mask_u8(alpha_u8, "bytes_overlay")
+        if (Ha, Wa) != (H, W):
+            raise ValueError(f"alpha is {Ha} x {Wa}, the original {H} x {W}")
+    if out is None:
+        out = torch.empty((B, H, W, 3), device=res.device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, 3) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 [B, H, W, 3] tensor")
+    libfk.check(libfk.load().fk_bytes_overlay_u8(_ptr(res), _ptr(orig_u8), N, _ptr(alpha_u8), Bm, _ptr(out), B, H, W, x0, y0, x1, y1,
+                                                 _stream()), "fk_bytes_overlay_u8")
+    return out
+
+
 # ---- optimisation step of the denoiser (include/fk.h; reference train_denoiser.py:935-1181) ------------------------
 def _reduce_ws(device):
     return torch.empty(libfk.load().fk_reduce_ws_doubles(), dtype=torch.float64, device=device)

@@ -15,7 +15,8 @@ scalars prepared before the loop so the 28 steps enqueue without a host sync.
 
 Pixels either side of the path: ``image_processor.VaeImageProcessor`` restates the
 diffusers helper the reference pipeline calls; uint8 pixels (PIL / numpy / uint8 tensors) take two fused HIP kernels
-(normalise + nearest resize + cast in front of the VAE encoder, clamp + quantise behind the decoder).
+(normalise + nearest resize + cast in front of the VAE encoder, clamp + quantise behind the decoder); ``resample=`` puts Pillow's
+antialiased byte resize (``fk_resample_pass_u8``) in front of the first and behind the second.
 """
 import os
 from types import SimpleNamespace
@@ -302,7 +303,8 @@ class FluxKontextPipeline:
                 raise ValueError("`mask_image` is empty: `padding_mask_crop` has no box to crop to")
             x0, y0, x1, y1 = edit.box = helpers.mask_crop_box(bbox, Wm, Hm, edit.pad, width, height)
             # the existing quirk, stated for the box: a second normalisation iff no normalised value of it is negative
-            edit.renorm = bool(edit.pic[:, y0:y1, x0:x1].min() >= 128)
+            # (with `resample` the resized bytes decide instead: _crop_pixels)
+            edit.renorm = edit.resample is None and bool(edit.pic[:, y0:y1, x0:x1].min() >= 128)
             a = a[:, y0:y1, x0:x1]
         if edit.pic is not None:
             edit.pic = edit.pic.to(device).contiguous()
@@ -332,18 +334,21 @@ class FluxKontextPipeline:
                 raise ValueError("`padding_mask_crop` / `overlay` need the preserved picture as uint8 pixels (PIL / numpy / uint8 "
                                  "tensor [N,H,W,3]): a float tensor or latents have no bytes to keep")
         return SimpleNamespace(sigma=sigma, pad=None if not crop else int(padding_mask_crop), crop=crop, overlay=bool(overlay),
-                               pic=pic, alpha=None, box=None, renorm=False)
+                               pic=pic, alpha=None, box=None, renorm=False, resample=None)
 
-    def _encode_init_image(self, init_image, batch_size, num_channels_latents, height, width, device, edit=None):
+    def _encode_init_image(self, init_image, batch_size, num_channels_latents, height, width, device, edit=None, resample=None):
         """Packed latents [B, S_tgt, 64] of the picture a masked edit preserves, at the target size: the condition image's
         own routes (uint8 pixels through the fused gather, float tensors through resize + preprocess) without the
         preferred-resolution snap; pre-encoded latents must already have the target's latent size.  A cropped edit
-        (``edit.crop``) samples the picture's box instead (``fk_pixels_u8_box_to_nhwc_bf16``, bilinear)."""
+        (``edit.crop``) samples the picture's box instead (``fk_pixels_u8_box_to_nhwc_bf16``, bilinear).  ``resample`` (a filter
+        name): uint8 pixels are resized with ``ops.resample_u8`` first, and the gather is an identity."""
         h_lat, w_lat = height // self.vae_scale_factor, width // self.vae_scale_factor
         u8 = image_processor.as_uint8_nhwc(init_image)
         if edit is not None and edit.crop:
             lat = self._encode_vae_image(self._crop_pixels(edit, height, width).tensor, nhwc=True)
         elif u8 is not None:
+            if resample is not None:
+                u8 = ops.resample_u8(u8.to(device), height, width, resample)
             px = image_processor.pixels_to_latent_input(u8, height, width, device)
             lat = self._encode_vae_image(px.tensor, nhwc=True)
         elif isinstance(init_image, torch.Tensor) and init_image.dim() == 4 and init_image.size(1) == self.latent_channels:
@@ -367,7 +372,13 @@ class FluxKontextPipeline:
 
     @staticmethod
     def _crop_pixels(edit, height, width):
-        """The preserved picture's box at height x width, as the VAE encoder's input."""
+        """The preserved picture's box at height x width, as the VAE encoder's input: point-sampled bilinear, or with
+        ``edit.resample`` the box's view resized byte for byte and passed through the whole-picture gather at equal size (which
+        decides the second normalisation on the resized bytes)."""
+        if edit.resample is not None:
+            x0, y0, x1, y1 = edit.box
+            resized = ops.resample_u8(edit.pic[:, y0:y1, x0:x1], height, width, edit.resample)
+            return image_processor.pixels_to_latent_input(resized, height, width, resized.device)
         return image_processor.NhwcPixels(ops.pixels_box_to_nhwc(edit.pic, edit.box, height, width, 32, edit.renorm))
 
     @torch.no_grad()
@@ -378,7 +389,7 @@ class FluxKontextPipeline:
                  output_type="pil", return_dict=True, joint_attention_kwargs=None, callback_on_step_end=None,
                  callback_on_step_end_tensor_inputs=("latents",), max_sequence_length=512,
                  max_area=1024 ** 2, _auto_resize=True, mask_image=None, strength=1.0, init_image=None, step_cache=None,
-                 padding_mask_crop=None, mask_blur=0.0, overlay=None, latent_state="bf16"):
+                 padding_mask_crop=None, mask_blur=0.0, overlay=None, resample=None, latent_state="bf16"):
         """``mask_image`` / ``strength`` / ``init_image`` (diffusers' ``FluxKontextInpaintPipeline``): repaint only where the
         mask is 1 and keep ``init_image`` (default: ``image``, resized to the target size) elsewhere; ``strength`` < 1 starts
         the loop inside the schedule from the re-noised ``init_image`` instead of from noise.  ``image`` stays the Kontext
@@ -396,7 +407,7 @@ class FluxKontextPipeline:
         bf16 token rows, which receive the state's one rounding per step, and the returned latents are those rows.
 
         ``padding_mask_crop`` / ``mask_blur`` / ``overlay`` (diffusers' ``padding_mask_crop`` + ``apply_overlay``; parity with PIL's
-        GaussianBlur and lanczos resize unpinned): work on the masked box and paste the result back.  They need ``mask_image``;
+        GaussianBlur unpinned): work on the masked box and paste the result back.  They need ``mask_image``;
         a crop or an overlay also needs the preserved picture (``init_image``, else ``image``) as uint8 pixels of the mask's size.
         ``mask_blur`` (sigma in pixels of the mask image, at most 64) feathers the mask, which from then on is the mask everywhere.
         ``padding_mask_crop`` (int >= 0): one box per call -- the bounding box over the mask batch of alpha >= 1, padded and grown
@@ -405,7 +416,20 @@ class FluxKontextPipeline:
         for ``output_type="latent"``, which returns the crop's latents): the returned image has the preserved picture's size and
         its own bytes outside the box and wherever alpha is 0, the alpha blend of the resampled result elsewhere; without a crop
         the box is the whole picture.  The output carries ``crop_box``.  With all three at their defaults the call is today's
-        call, launch for launch.  Not built: antialiased resampling.
+        call, launch for launch.  Without ``resample`` the box is point-sampled in both directions.
+
+        ``resample`` (None | "nearest" | "bilinear" | "bicubic" | "lanczos"): how pictures that arrive as bytes (PIL / numpy uint8 /
+        uint8 tensor) are resized.  ``None`` and ``"nearest"`` are today's call, launch for launch.  A filter name is Pillow's
+        antialiased 8-bit ``Image.resize`` with that filter, byte for byte (``ops.resample_u8``; diffusers resizes PIL inputs with
+        lanczos): the condition image is resized to its snapped size and ``init_image`` to the target's, then each takes today's
+        gather at equal size, whose second-normalisation rule therefore reads the resized bytes.  With ``padding_mask_crop`` the
+        box ``pic[:, y0:y1, x0:x1]`` is resized the same way (crop, then resize: windows clamp at the box), and the second
+        normalisation is decided on the RESIZED bytes -- a lanczos or bicubic overshoot can take a byte below 128 where every byte
+        of the box is >= 128, so this can differ from the point-sampled crop's decision; the token mask stays the binarised nearest
+        one.  With ``overlay`` the decoded result becomes bytes (``fk_image_to_u8_nhwc``), is resized to the box's size and blended
+        over the picture's bytes in integers (``fk_bytes_overlay_u8``); at equal size with alpha in {0, 255} these are today's
+        overlay bytes.  A filter name with a float-tensor or latent picture is a ``ValueError`` (there are no bytes to filter), and
+        so is an unknown name.  All of it is in front of the first step or behind the decode.
 
         ``joint_attention_kwargs["scale"]`` (default 1.0): the call scale of the loaded LoRA adapters (``load_lora_weights``)."""
         device = self.device
@@ -420,6 +444,14 @@ class FluxKontextPipeline:
                 self.transformer.set_lora_scale(1.0 if scale is None else scale)
         elif getattr(self.transformer, "lora_loaded", None) is not None and self.transformer.lora_loaded():
             self.transformer.set_lora_scale(1.0)
+        if resample is not None and resample != "nearest" and resample not in helpers.RESAMPLE_FILTERS:
+            raise ValueError(f'`resample` is None, "nearest", "bilinear", "bicubic" or "lanczos", not {resample!r}')
+        resample = None if resample == "nearest" else resample
+        if resample is not None:
+            for name, pic in (("image", image), ("init_image", init_image)):
+                if pic is not None and image_processor.as_uint8_nhwc(pic) is None:
+                    raise ValueError(f'`resample="{resample}"` filters bytes: `{name}` is a float tensor or latents, which have none '
+                                     "(pass PIL / numpy uint8 / a uint8 tensor [N,H,W,3], or leave `resample` out)")
         helpers.strength_t_start(num_inference_steps, strength)     # validates strength before any work
         if step_cache is not None:                                  # ... and the schedule against the executed step count
             n_all = num_inference_steps if sigmas is None else len(sigmas)
@@ -430,6 +462,7 @@ class FluxKontextPipeline:
         edit = None
         if padding_mask_crop is not None or mask_blur or overlay:
             edit = self._check_pixel_edit(image, init_image, mask_image, padding_mask_crop, mask_blur, overlay, output_type)
+            edit.resample = resample
         if prompt is not None and prompt_embeds is not None:
             raise ValueError(f"Cannot forward both `prompt`: {prompt} and `prompt_embeds`: {prompt_embeds}. Please make "
                              "sure to only forward one of the two.")   # :510-514
@@ -501,6 +534,8 @@ class FluxKontextPipeline:
             # uint8 pixels: cli.prepare_condition_images + resize + preprocess + .to(bf16) as ONE HIP gather
             ih, iw = self.image_processor.get_default_height_width(u8.permute(0, 3, 1, 2))
             ih, iw = helpers.preferred_condition_size(ih, iw, multiple_of, _auto_resize)
+            if resample is not None:                # antialiased to the snapped size; the gather below is then an identity
+                u8 = ops.resample_u8(u8.to(device), ih, iw, resample)
             image = image_processor.pixels_to_latent_input(u8, ih, iw, device)
             cond_hw = (ih, iw)
         elif image is not None and not (isinstance(image, torch.Tensor) and image.size(1) == self.latent_channels):
@@ -532,7 +567,7 @@ class FluxKontextPipeline:
                 x0 = image_latents
             else:
                 x0 = self._encode_init_image(image_in if init_image is None else init_image, batch_size,
-                                             num_channels_latents, height, width, device, edit)
+                                             num_channels_latents, height, width, device, edit, resample)
             noise = latents.contiguous()            # a caller-supplied `latents` serves as the noise, as in diffusers
 
         # 5. timesteps (host float32 arithmetic, like diffusers' numpy path)
@@ -596,7 +631,12 @@ class FluxKontextPipeline:
             img = self.vae.decode(z, return_dict=False, pre_div=vcfg.scaling_factor, pre_add=vcfg.shift_factor)[0]
             if edit is not None and edit.overlay:
                 # the result resampled into the box and blended over the picture's own bytes: they are kept, not decoded
-                image_out = ops.image_overlay(img.contiguous(), edit.pic, edit.alpha, edit.box).cpu().numpy()
+                if edit.resample is not None:       # decode -> bytes -> antialiased to the box's size -> integer blend
+                    x0, y0, x1, y1 = edit.box
+                    res = ops.resample_u8(ops.image_to_u8(img.contiguous()), y1 - y0, x1 - x0, edit.resample)
+                    image_out = ops.bytes_overlay(res, edit.pic, edit.alpha, edit.box).cpu().numpy()
+                else:
+                    image_out = ops.image_overlay(img.contiguous(), edit.pic, edit.alpha, edit.box).cpu().numpy()
                 if output_type == "pil":
                     from PIL import Image
                     image_out = [Image.fromarray(a) for a in image_out]

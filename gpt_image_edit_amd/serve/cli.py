@@ -53,6 +53,23 @@ def latent_state_kwargs(args):
     return {} if state == "bf16" else {"latent_state": state}
 
 
+RESAMPLE_CHOICES = ("nearest", "bilinear", "bicubic", "lanczos")
+
+
+def add_resample_argument(parser):
+    parser.add_argument("--resample", choices=RESAMPLE_CHOICES, default="nearest",
+                        help="how input images (and, with --mask_crop_padding / --overlay, the result on its way back) are "
+                             "resized: nearest -- the reference's tensor resize, point-sampled; bilinear / bicubic / lanczos -- "
+                             "Pillow's antialiased 8-bit resize with that filter, byte for byte, in HIP (diffusers resizes PIL "
+                             "inputs with lanczos)")
+
+
+def resample_kwargs(args):
+    """``--resample`` as the pipeline's ``resample`` (nothing for the default: the call the pipeline always got)."""
+    name = getattr(args, "resample", None) or "nearest"
+    return {} if name == "nearest" else {"resample": name}
+
+
 def load_pipe(denoiser, flux_path, device, weight_format="bf16", solver="euler"):
     """``FluxKontextPipeline.from_pretrained(flux_path, transformer=denoiser, torch_dtype=bf16).to(device)``.
 
@@ -191,6 +208,7 @@ def generate_image(pipe, prompt_embeds, pooled_prompt_embeds, history_image_path
         **step_cache_kwargs(args),
         **lora_kwargs(args),
         **latent_state_kwargs(args),
+        **resample_kwargs(args),
     ).images[0]
 
 
@@ -223,6 +241,7 @@ def run_t5_only(pipe, text_encoders, tokenizers, text, image1=None, image2=None,
         **step_cache_kwargs(args),
         **lora_kwargs(args),
         **latent_state_kwargs(args),
+        **resample_kwargs(args),
     ).images
 
 
@@ -264,6 +283,7 @@ def build_parser():
     parser.add_argument("--overlay", action="store_true",
                         help="with --mask: return the input image's own bytes wherever the mask is black (implied by "
                              "--mask_crop_padding)")
+    add_resample_argument(parser)
     add_step_cache_arguments(parser)
     add_solver_argument(parser)
     lora.add_cli_arguments(parser)

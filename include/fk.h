@@ -882,10 +882,10 @@ int fk_image_to_u8_nhwc(const void* src, int32_t src_is_fp32, void* dst, int32_t
 
 /* ---- Masked edits on the masked box (pipeline.py: padding_mask_crop / mask_blur / overlay; csrc/mask_ops.hip).  The rules are
  * written from the description of diffusers' VaeImageProcessor.get_crop_region / .blur / .apply_overlay; parity with PIL's
- * GaussianBlur and lanczos resize is unpinned.  Every product, sum and division below is one fp32 operation (the file is built
+ * GaussianBlur is unpinned (its lanczos / bicubic / bilinear resize is pinned byte for byte: fk_resample_pass_u8 below).  Every product, sum and division below is one fp32 operation (the file is built
  * without contraction) -- except in K3, where each is one fp64 operation; every index is clamped before its load; no atomics.  A refused call returns FK_EINVAL with a message and
- * writes nothing.  Not built: antialiased downsampling (a box smaller than the model resolution on the way out, larger on the
- * way in, is point-sampled bilinear).
+ * writes nothing.  K3 and K4 point-sample: a box smaller than the model resolution on the way out, larger on the way in, aliases.
+ * The antialiased route is fk_resample_pass_u8 + fk_bytes_overlay_u8 below (pipeline.py: resample=).
  *
  * The bilinear rule (K3, K4), per axis, output position X of n_out over a source of n_in samples:
  *   s = clamp((X + 0.5) * (n_in / n_out) - 0.5, 0, n_in - 1),  i0 = floor(s),  i1 = min(i0 + 1, n_in - 1),  f = s - i0
@@ -924,6 +924,46 @@ int fk_pixels_u8_box_to_nhwc_bf16(const void* src, void* dst, int32_t B, int32_t
 int fk_image_overlay_u8(const void* img, int32_t img_is_fp32, int32_t h, int32_t w, const void* orig, int32_t orig_batch,
                         const void* alpha, int32_t alpha_batch, void* dst, int32_t B, int32_t H, int32_t W, int32_t x0, int32_t y0,
                         int32_t x1, int32_t y1, fk_stream_t stream);
+
+/* ---- Antialiased byte resize and byte paste-back (pipeline.py: resample=; csrc/resample.hip).  Pillow's 8-bit resize, written from
+ * its behaviour: integer arithmetic on tables made on the host (helpers.resample_coeffs, float64), so the kernels are held to
+ * EQUALITY with Pillow's bytes (tests/test_resample_ref.py, tests/test_hip_resample_kernels.py), not to a tolerance.
+ *
+ * Filters (float64): bilinear 1 - |x| on |x| < 1, support 1;  bicubic with a = -0.5, support 2;  lanczos sinc(x) sinc(x / 3) on
+ * -3 <= x < 3 with sinc(x) = sin(pi x) / (pi x), support 3.  Per axis, n_in -> n_out:
+ *   scale = n_in / n_out,  fs = max(scale, 1),  support = filter_support * fs,  ksize = ceil(support) * 2 + 1
+ * and per output index i:
+ *   center = (i + 0.5) * scale,  xmin = max(int(center - support + 0.5), 0),  xmax = min(int(center + support + 0.5), n_in)
+ *   w_t = filter((t + xmin - center + 0.5) * (1 / fs)) for t < xmax - xmin, summed in ascending t, each divided by the sum when
+ *   the sum is nonzero;  kk_t = int(w_t * 2^22 + 0.5) for w_t >= 0, int(w_t * 2^22 - 0.5) otherwise (int truncates).
+ * One pass over an axis, per channel, int32 accumulator, arithmetic shift:
+ *   out = clip((2^21 + sum_t kk_t * src[xmin + t]) >> 22, 0, 255)
+ * The window is clamped BEFORE the weights are made, so the weights of a cut window are renormalised.  A resize is the horizontal
+ * pass into a uint8 intermediate [B, Hin, Wout, C] -- that rounding is part of the rule -- then the vertical pass; a pass whose axis
+ * keeps its size is skipped, not run with a one-tap table (ops.resample_u8).  A crop is crop-then-resize: the box is an integer
+ * sub-view of the source and windows clamp at the box, so the entry takes a strided view and no box.
+ *
+ * fk_resample_pass_u8: src is a view of uint8 pixels [B, Hin, Win, C], C 1 or 3, pixels of a row contiguous, rows src_row_stride
+ * and samples src_batch_stride bytes apart; dst is contiguous, [B, Hin, n_out, C] for axis 1 (horizontal) and [B, n_out, Win, C] for
+ * axis 0 (vertical).  bounds: device int32 [n_out, 2] = (xmin, xmax).  kk: device int32, [n_out, ksize] for axis 0 and TAP-MAJOR
+ * [ksize, n_out] for axis 1 (adjacent lanes are adjacent outputs), zero past xmax - xmin.  The caller guarantees
+ * 255 * sum_t |kk_t| + 2^21 < 2^31 per output (helpers.resample_coeffs checks it).  Whatever the tables hold, every window is
+ * clamped to [0, n_in] and to ksize taps before a load.  Refused with FK_EINVAL and a message, nothing written: a null pointer, C
+ * not 1 or 3, a size that is not positive, an axis that is not 0 or 1, ksize < 1 or > FK_RESAMPLE_MAX_KSIZE (lanczos down to 1/85,
+ * bilinear to 1/256), rows that overlap, tables that are not 4-byte aligned, dst == src. */
+#define FK_RESAMPLE_MAX_KSIZE 513
+int fk_resample_pass_u8(const void* src, int64_t src_batch_stride, int64_t src_row_stride, void* dst, int32_t B, int32_t Hin,
+                        int32_t Win, int32_t C, int32_t axis, int32_t n_out, const int32_t* bounds, const int32_t* kk,
+                        int32_t ksize, fk_stream_t stream);
+/* fk_image_overlay_u8 on bytes.  res: uint8 [B, y1 - y0, x1 - x0, 3], the result already at the box's size; orig: uint8
+ * [orig_batch, H, W, 3], orig_batch 1 or B; alpha: uint8 [alpha_batch, H, W], alpha_batch 1 or B, or NULL (alpha_batch 0) meaning
+ * 255 everywhere; dst: uint8 [B, H, W, 3], a buffer of its own.  Outside the box [x0, x1) x [y0, y1): the original's bytes.  Inside,
+ * with o the original's byte, r the result's and a the alpha:
+ *   a == 0: o, taken;   a == 255: r, taken;   otherwise (2 * (a * r + (255 - a) * o) + 255) / 510 in integers
+ * -- the exact quotient (a r + (255 - a) o) / 255 rounded to nearest; a tie cannot occur.  Parity with PIL's compositing is not
+ * claimed. */
+int fk_bytes_overlay_u8(const void* res, const void* orig, int32_t orig_batch, const void* alpha, int32_t alpha_batch, void* dst,
+                        int32_t B, int32_t H, int32_t W, int32_t x0, int32_t y0, int32_t x1, int32_t y1, fk_stream_t stream);
 
 /* ---- LoRA merge (transformer.py: load_lora_adapter / set_adapters / set_lora_scale; the reference's pipeline is a
  * FluxLoraLoaderMixin, univa/utils/flux_pipeline.py:195).  Adapters become part of a bf16 weight [N, K]:

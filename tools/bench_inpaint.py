@@ -14,6 +14,10 @@
 ``fk_mask_blur_u8`` (sigma 4), ``fk_pixels_u8_box_to_nhwc_bf16`` and ``fk_image_overlay_u8`` at a 1024^2 picture with a 512^2 box,
 beside ``fk_pixels_u8_to_nhwc_bf16`` and ``fk_image_to_u8_nhwc`` at 512^2 in the same run, and images per second of a crop +
 overlay edit beside the plain masked edit (both return uint8 pixels).
+
+``--resample`` (``python tools/bench_inpaint.py --resample [--out profiles/resample.json]``): per-launch time of the two passes of
+``fk_resample_pass_u8`` and of ``ops.resample_u8`` as a whole, three filters, 3000 x 4000 -> 768 x 1024 and 1024^2 -> 512^2, beside
+``fk_pixels_u8_to_nhwc_bf16`` at the same sizes and Pillow's own time for the same call on the host CPU.
 """
 import argparse
 import json
@@ -150,15 +154,67 @@ def overlay_edit_timing(reps=3):
                     seconds=v, graph=bool(pipe.use_graph)) for k, v in secs.items()}
 
 
+def resample_timing(launches=50, windows=5):
+    """Per launch: the horizontal pass, the vertical pass and ``resample_u8`` as a whole (both launches, the intermediate's
+    allocation, the cached tables) for the three filters at 3000 x 4000 -> 768 x 1024 and 1024^2 -> 512^2, beside the nearest
+    gather ``fk_pixels_u8_to_nhwc_bf16`` at the same sizes, and Pillow's time for the same call on this host's CPU (one thread)."""
+    import numpy as np
+    res = []
+    for (Hin, Win), (Hout, Wout) in (((3000, 4000), (768, 1024)), ((1024, 1024), (512, 512))):
+        g = torch.Generator(device="cuda").manual_seed(Hin)
+        pic = torch.randint(0, 256, (1, Hin, Win, 3), generator=g, device="cuda", dtype=torch.uint8)
+        mid = torch.empty(1, Hin, Wout, 3, device="cuda", dtype=torch.uint8)
+        out = torch.empty(1, Hout, Wout, 3, device="cuda", dtype=torch.uint8)
+        fns = {"fk_pixels_u8_to_nhwc_bf16": lambda: ops.pixels_to_nhwc(pic, Hout, Wout, 32, False)}
+        for f in ("bilinear", "bicubic", "lanczos"):
+            ops.resample_pass_u8(pic, 1, Wout, f, out=mid)
+            fns[f"fk_resample_pass_u8(horizontal, {f})"] = lambda f=f: ops.resample_pass_u8(pic, 1, Wout, f, out=mid)
+            fns[f"fk_resample_pass_u8(vertical, {f})"] = lambda f=f: ops.resample_pass_u8(mid, 0, Hout, f, out=out)
+            fns[f"resample_u8({f})"] = lambda f=f: ops.resample_u8(pic, Hout, Wout, f)
+        for fn in fns.values():
+            window(fn, 5)
+        samples = {k: [] for k in fns}
+        for _ in range(windows):
+            for k, fn in fns.items():
+                samples[k].append(window(fn, launches))
+        entry = {k: dict(us_per_launch_median=statistics.median(v), us_per_launch_min=min(v), us_per_launch_max=max(v),
+                         launches_per_window=launches, windows=windows) for k, v in samples.items()}
+        try:
+            from PIL import Image
+            im = Image.fromarray(pic[0].cpu().numpy())
+            for f, flt in (("bilinear", Image.BILINEAR), ("bicubic", Image.BICUBIC), ("lanczos", Image.LANCZOS)):
+                secs = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    ref = im.resize((Wout, Hout), flt)
+                    secs.append(time.perf_counter() - t0)
+                same = bool(np.array_equal(np.asarray(ref), ops.resample_u8(pic, Hout, Wout, f)[0].cpu().numpy()))
+                entry[f"PIL.Image.resize({f}) on the host CPU"] = dict(us_per_call_median=statistics.median(secs) * 1e6,
+                                                                        equal_to_the_kernel=same)
+        except ImportError:
+            entry["PIL.Image.resize"] = "Pillow is not installed"
+        res.append(dict(source=[Hin, Win], target=[Hout, Wout], channels=3, timings=entry))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-edit", action="store_true")
     ap.add_argument("--overlay", action="store_true", help="time the crop / feather / overlay kernels and edits instead")
+    ap.add_argument("--resample", action="store_true", help="time the antialiased byte resize (fk_resample_pass_u8) instead")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or ("profiles/inpaint_overlay.json" if args.overlay else "profiles/inpaint_timing.json")
+    args.out = args.out or ("profiles/resample.json" if args.resample else
+                            "profiles/inpaint_overlay.json" if args.overlay else "profiles/inpaint_timing.json")
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU: a timing from anything else says nothing")
+    if args.resample:
+        res = {"resample": resample_timing()}
+        print(json.dumps(res, indent=1), flush=True)
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if args.overlay:
         res = {"kernels": overlay_kernel_timing()}
         print(json.dumps(res["kernels"], indent=1), flush=True)
