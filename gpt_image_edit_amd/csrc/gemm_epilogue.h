@@ -105,15 +105,24 @@ FK_DEV void quad_set(f32x16_t& v, int q, const f32x4_t& c) {
 // UB: chunks per batch of the output loop (gemm_mxfp8.hip's split-K pairs take 4: their accumulators stay allocated beside it).
 // flat: bit 1 / 2 / 3 (gemm_tile_map.h: TM_C_FLAT, TM_R_FLAT, TM_G_FLAT) -- the launcher found the rows of C / the residual at
 // m * ld / every gate row to be row 0: the per-tile divisions of their addressing are skipped.  0: fk_rows addressing throughout.
-template <int EPI, int BN, class C, int HALF = -1, int UB = 8>
+// WALK (the tile walk of gemm_pingpong_bf16.hip): the next tile's first K-tile is in flight into the front of the ring while
+// this runs.  The C (half-)tile therefore lies WALK_CT_OFF bytes into LDS, the barriers wait for LDS traffic only (a
+// __syncthreads() would wait for the requests in flight and for this tile's stores), the bias quads come from the caller
+// (`bias_in`, loaded in front of those requests: a wait for them is then no wait for the requests), and a half-tile pass
+// (HALF >= 0) adds nothing (`other` is unused); the first pass waits for those requests before it stores (below).  The arithmetic and the rounding points are those of the other forms.
+constexpr int WALK_CT_OFF = 65536;
+FK_DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+template <int EPI, int BN, class C, int HALF = -1, int UB = 8, bool WALK = false>
 FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& p, char* smem, int m0, int n0,
-                       int wm, int wn, const u32x4_t* other = nullptr, int flat = 0) {
+                       int wm, int wn, const u32x4_t* other = nullptr, int flat = 0, const u32x2_t (*bias_in)[4] = nullptr) {
+  constexpr bool ADD_OTHER = HALF >= 0 && !WALK;
   constexpr int MF0 = HALF > 0 ? C::MF / 2 : 0, MF1 = HALF == 0 ? C::MF / 2 : C::MF;   // m-blocks stored
   constexpr int row0 = HALF > 0 ? BM / 2 : 0;                                           // first tile row stored
   int tid = threadIdx.x;
   // gemm10 (the only 256-thread caller) may run this inside a per-CU tile loop around an asm statement that leaves 36 free
   // VGPRs: an opaque copy keeps hipcc from hoisting the 32 per-lane row indices below out of that loop and spilling them
-  if constexpr (C::NTHREADS == 256) asm volatile("" : "+v"(tid));
+  // (so may the tile walk, whose loop holds the K loop as well)
+  if constexpr (C::NTHREADS == 256 || WALK) asm volatile("" : "+v"(tid));
   const int lane = tid & 63;
   using FM = FragMap<C::M16>;
   // bias of this lane's 4-column quads (all loads in flight before the barrier below)
@@ -122,7 +131,12 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
   for (int nf = 0; nf < C::NF; ++nf)
 #pragma unroll
     for (int q = 0; q < 4; ++q) bw[nf][q] = u32x2_t{0u, 0u};
-  if constexpr (EPI != FK_EPI_SCALE) {
+  if constexpr (WALK) {
+#pragma unroll
+    for (int nf = 0; nf < C::NF; ++nf)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) bw[nf][q] = bias_in[nf][q];
+  } else if constexpr (EPI != FK_EPI_SCALE) {
     if (p.bias) {
 #pragma unroll
       for (int nf = 0; nf < C::NF; ++nf)
@@ -155,8 +169,10 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
       }
     return;
   }
-  __syncthreads();  // every wave is done reading the last stage before the C tile aliases it
-  bf16_t* ct = (bf16_t*)smem;
+  // every wave is done reading the last stage before the C tile aliases it
+  if constexpr (WALK) lds_barrier(); else __syncthreads();
+  // (WALK: row `row0` of the tile is the first row of the C half-tile)
+  bf16_t* ct = WALK ? (bf16_t*)(smem + WALK_CT_OFF) - row0 * C::CT_LD : (bf16_t*)smem;
 #pragma unroll
   for (int nf = 0; nf < C::NF; ++nf) {
 #pragma unroll
@@ -169,7 +185,7 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           float x = acc[nf][mf][q * 4 + j];
-          if constexpr (HALF >= 0) x += __uint_as_float(other[nf * 2 * C::MF + (mf - MF0) * 4 + q][j]);
+          if constexpr (ADD_OTHER) x += __uint_as_float(other[nf * 2 * C::MF + (mf - MF0) * 4 + q][j]);
           if constexpr (EPI == FK_EPI_SCALE) v[j] = x * p.alpha;
           else v[j] = x + b[j];
         }
@@ -188,7 +204,11 @@ FK_DEV void store_tile(const f32x16_t (&acc)[C::NF][C::MF], const fk_gemm_args& 
       }
     }
   }
-  __syncthreads();
+  if constexpr (WALK) lds_barrier(); else __syncthreads();
+  // WALK, first pass: the last point of the epilogue with no store in flight -- the next tile's K-tile 0 (requested in front of
+  // the epilogue; nothing else is outstanding) has landed before the first store is issued, so that no later wait for it has
+  // to count past the stores
+  if constexpr (WALK && HALF <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   constexpr int CPR = BN / 8;  // 16-byte chunks per tile row
   constexpr int ITERS = (HALF >= 0 ? BM / 2 : BM) * CPR / C::NTHREADS;
   // chunks per batch; the fused QKV epilogue keeps 16 table registers per chunk, so the 4-wave kernel (32 chunks per

@@ -543,7 +543,8 @@ extern "C" int fk_gemm_mxfp8_grouped(const fk_gemm_mxfp8_args* args, int32_t n, 
   // plan: as fk_gemm_bf16 validates it (explicit bit, allow bits, at most one exchange bit); only bit 1 and the exchange matter here
   constexpr int SK_BITS = FK_GEMM_PLAN_SPLITK_WHOLE | FK_GEMM_PLAN_SPLITK_SYMMETRIC | FK_GEMM_PLAN_SPLITK_UNANNOUNCED;
   const int sk_bits = c0.plan & SK_BITS;
-  if ((c0.plan != 0 && ((c0.plan & ~(15 | SK_BITS)) != 0 || !(c0.plan & FK_GEMM_PLAN_EXPLICIT))) || (sk_bits & (sk_bits - 1)) != 0) {
+  // (the tile-walk bits travel with a block's plan and mean nothing to these kernels)
+  if ((c0.plan != 0 && ((c0.plan & ~(15 | SK_BITS | FK_GEMM_PLAN_WALK_BITS)) != 0 || !(c0.plan & FK_GEMM_PLAN_EXPLICIT))) || (sk_bits & (sk_bits - 1)) != 0) {
     fk_set_error("fk_gemm_mxfp8: plan %d is not 0 (default) or FK_GEMM_PLAN_EXPLICIT | allow bits 0..2 | at most one "
                  "FK_GEMM_PLAN_SPLITK_* exchange", c0.plan);
     return FK_EINVAL;

@@ -65,6 +65,7 @@ struct GroupArgs {
   unsigned* sk_ctl;
   int sk_mode;         // split-K pairs' exchange (SK_* below): whole tile one way, or each workgroup finishes a 128-row half
   int sk_min_part;     // stream-K launch (gemm8_streamk_kernel): the shortest part (in K-tiles) a cut may leave
+  int walk_grid;       // tile walk (gemm_walk_kernel): workgroups of the launch; e.grid stays the number of places (tiles)
 };
 
 
@@ -127,6 +128,7 @@ FK_DEV void wait_vmcnt() {
   else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
   else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+  else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");     // the tile walk's 256 x 128 tile, first wait
   else static_assert(N == 0, "add the vmcnt literal");
 }
 
@@ -1208,14 +1210,7 @@ int launch_mix(GroupArgs& ga, const fk_gemm_args* probs, int n, int big_cols, hi
   const int ts = tm_fill_class(ga.e.cls[1], Ms, n, ncols128, big_cols * 256, ga.e.group_m);
   if (tb < 0 || ts < 0) return FK_E2BIG_STRIDES;
   const int W = tb + ts;
-  int bs = 0, ss = 0;
-  for (int x = 0; x < 8; ++x) {
-    const int wx = W / 8 + (x < W % 8 ? 1 : 0), bx = tb / 8 + (x < tb % 8 ? 1 : 0);
-    if (wx < bx) return FK_E2BIG_STRIDES;   // cannot happen for the grids the planner proposes (ts >= 8); caller falls back
-    ga.e.xcd[x] = {bs, bx, ss, 0};
-    bs += bx;
-    ss += wx - bx;
-  }
+  if (!tm_fill_mix(ga.e, tb, ts)) return FK_E2BIG_STRIDES;   // cannot happen for the grids the planner proposes (ts >= 8); caller falls back
   tm_fill_grid(ga.e, (uint32_t)W);
   auto kern = gemm_mix_kernel<EPI, M16>;
   FK_ENSURE_MAX_LDS(kern, MIX_SMEM, "fk_gemm_bf16 (mixed 256 x 256 / 256 x 128 tiles)");
@@ -1224,10 +1219,450 @@ int launch_mix(GroupArgs& ga, const fk_gemm_args* probs, int n, int big_cols, hi
   return FK_OK;
 }
 
+// ---- tile walk: one workgroup per CU, the next tile's first K-tile requested in front of the epilogue ----------------------
+// A grid of 256 x 256 tiles, or a mixed one, with more tiles than CUs, as G = #CUs workgroups: workgroup g works off the
+// places g, g + G, ... of the launch (gemm_tile_map.h: a CU gets the tiles list scheduling gives it today, in that order).
+// What a CU does between the last MFMA of one tile and the first of the next -- drain the stores, leave, be handed a
+// workgroup, fetch its arguments, compute its addresses, wait for the first touch of its operands -- has the matrix pipe
+// idle (15 % of a K = 3072 tile).  Here, behind tile i's K loop:
+//     bias quads of tile i (loads, in front of everything below: waiting for them waits for nothing younger)
+//     tile i + 1: place -> (problem, m0, n0), request offsets, descriptors; LDS-DMA requests of its K-tile 0 into the FRONT of
+//       the ring -- buffer 0 = [0, 64 KiB) (A0 | A1 | W0 | W1) for a 256 x 256 tile, stage 0 = [0, 48 KiB) for a 256 x 128 one
+//     epilogue of tile i from a C tile at byte 65 536: two half-tile passes of 128 x 264 x 2 B = 67 584 B (to 133 120) for a
+//       256 x 256 tile, one pass of 256 x 136 x 2 B = 69 632 B (to 135 168) for a 256 x 128 one; LDS-only barriers
+//     LDS barrier (the C tile is read), the rest of tile i + 1's prologue (K-tile 1 ...), its K loop
+// vmcnt retires in order, loads and stores alike, so once the epilogue has issued stores a wait for K-tile 0 would have to
+// count past them -- and how many a thread issues is hipcc's business.  The epilogue (store_tile<.., WALK>) therefore waits for
+// ALL requests at its last point without a store in flight: behind the second barrier of its first pass, where the bias has
+// been consumed and K-tile 0 has had the C tile's arithmetic, its LDS writes and two barriers to land.  A continued tile so
+// starts with its K-tile 0 landed (every wave's, behind the hand-over's LDS barrier): no first wait, none in the first two
+// phases of a 256 x 256 tile; its third phase needs W0(1), which is younger than the stores -- that is where they are
+// waited for, two phases into the tile (a 256 x 128 tile needs W_0(1) in its first phase already).
+// Who may write which LDS bytes (the invariant of the hand-over).  A K loop ends with requests in flight whose K-tile is
+// clamped (never read), some of them into the front of the ring, and behind the loop every wave waits for ITS OWN requests
+// only (vmcnt(0)).  That orders them against the next tile's K-tile 0 exactly where both come from the same wave: a wave's
+// requests always target the same bytes of a buffer for one tile shape (pieces 2 w, 2 w + 1 of every half-tile; its piece of
+// W_j), and the A halves lie alike in both shapes, so between tiles of ONE shape no wave ever requests into bytes another wave
+// has a request in flight for.  The two shapes cut [32 KiB, 48 KiB) differently (256 x 256: wave w owns 2 KiB of W0; 256 x 128:
+// 1 KiB of W_0 and of W_1), so where a mixed grid's next tile has the other shape a workgroup barrier stands between the waits
+// and the requests.  Everything behind K-tile 0 (C tile, K-tile 1 ...) is ordered by the epilogue's barriers: its first one
+// stands behind every wave's vmcnt(0), its last one (lds_barrier in the tile loop) behind every wave's reads of the C tile.
+// No workspace, no flag, no wait for another workgroup.  Same LDS image, fragment mapping and K order as gemm8_body /
+// gemm9_body (layout 0): the bits of every epilogue are those of the one-workgroup-per-tile launch.
+struct WalkTile {
+  int pi, m0, n0, small;            // small: a 256 x 128 tile (the mixed grid's second class)
+  int flags;                        // ProbEntry.flags
+  int a_voff[2][2], w_voff[2][2];   // request offsets as in gemm8_body; small: w_voff[0][j] = part W_j as in gemm9_body
+  __amdgpu_buffer_rsrc_t rs_a, rs_w;
+};
+
+// The lane's addresses are derived from an opaque copy of threadIdx.x wherever the walk needs them: hipcc would otherwise hoist
+// every one of them out of the tile loop, where they live across the K loop and the epilogue and spill (gemm10_body's remedy).
+FK_DEV int walk_tid() {
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  return tid;
+}
+
+template <bool MIX>
+FK_DEV WalkTile walk_tile(const GroupArgs& ga, const Hot& x, const TmHot& hs, int place) {
+  WalkTile w;
+  if constexpr (MIX) {
+    const TileEntry::Xcd tab = ga.e.xcd[place & 7];
+    int t;
+    w.small = tm_mix_place(tab.big_start, tab.big_cnt, tab.small_start, (uint32_t)place, t);
+    if (w.small) tm_tile_hot(hs, 128, t, w.pi, w.m0, w.n0);
+    else tm_tile_hot(x.h, 256, t, w.pi, w.m0, w.n0);
+  } else {
+    w.small = 0;
+    select_tile<256>(x, tm_xcd_chunk(x.xq, x.xr, (uint32_t)place), w.pi, w.m0, w.n0);
+  }
+  const int tid = walk_tid();
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const ProbEntry q = load_prob(ga, w.pi);
+  w.flags = q.flags;
+  const int lrow = lane >> 3, slot = lane & 7;
+  const int ldw2 = q.ldw * 2;
+  int rls[4], aoff[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) rls[i] = (i >> 1) * 128 + (wave * 2 + (i & 1)) * 8 + lrow;   // row inside the 256-row tile
+  const int64_t a_first = tile_a_rows<4>(ga, w.pi, q, w.m0, rls, aoff);
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int rl = rls[h * 2 + j];
+      w.a_voff[h][j] = aoff[h * 2 + j] * 2 + ((slot ^ ((rl >> 1) & 7)) << 4);
+      w.w_voff[h][j] = min(rl, q.N - 1 - w.n0) * ldw2 + ((slot ^ ((rl >> 1) & 7)) << 4);
+    }
+  if (MIX && w.small) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int sr = wave * 8 + lrow;                      // row inside the 64-row part W_j
+      const int rl = (sr >> 5) * 64 + j * 32 + (sr & 31);  // row inside the 128-row W tile
+      w.w_voff[0][j] = min(rl, q.N - 1 - w.n0) * ldw2 + ((slot ^ ((sr >> 1) & 7)) << 4);
+    }
+  }
+  w.rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)((const bf16_t*)q.A + a_first), 0, 0x7fffffff, 0x00020000);
+  w.rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)((const bf16_t*)q.W + (int64_t)w.n0 * q.ldw), 0, 0x7fffffff, 0x00020000);
+  return w;
+}
+
+// 256 x 256 tile: half-tile `which` (0 = A0, 1 = A1, 2 = W0, 3 = W1) of K-tile kt (clamped) into ring buffer buf
+FK_DEV void walk_dma8(char* smem, const WalkTile& w, int wave, int nk, int which, int buf, int kt) {
+  using C = Cfg8<256>;
+  const int koff = min(kt, nk - 1) * (C::BK * 2);
+  char* dst = smem + buf * C::BUF_BYTES + which * C::HALF_BYTES + wave * 2048;
+  if (which < 2) {
+    buffer_lds16(w.rs_a, dst, w.a_voff[which][0], koff);
+    buffer_lds16(w.rs_a, dst + 1024, w.a_voff[which][1], koff);
+  } else {
+    buffer_lds16(w.rs_w, dst, w.w_voff[which - 2][0], koff);
+    buffer_lds16(w.rs_w, dst + 1024, w.w_voff[which - 2][1], koff);
+  }
+}
+// 256 x 128 tile: both halves of the A tile (4 requests) / part W_j (1 request) of K-tile kt (clamped) into `stage`
+FK_DEV void walk_dma9_a(char* smem, const WalkTile& w, int wave, int nk, int stage, int kt) {
+  using C = Cfg9<128>;
+  const int koff = min(kt, nk - 1) * (C::BK * 2);
+  char* dst = smem + stage * C::STAGE_BYTES + wave * 2048;
+  buffer_lds16(w.rs_a, dst, w.a_voff[0][0], koff);
+  buffer_lds16(w.rs_a, dst + 1024, w.a_voff[0][1], koff);
+  buffer_lds16(w.rs_a, dst + C::A_HALF, w.a_voff[1][0], koff);
+  buffer_lds16(w.rs_a, dst + C::A_HALF + 1024, w.a_voff[1][1], koff);
+}
+FK_DEV void walk_dma9_w(char* smem, const WalkTile& w, int wave, int nk, int j, int stage, int kt) {
+  using C = Cfg9<128>;
+  const int koff = min(kt, nk - 1) * (C::BK * 2);
+  buffer_lds16(w.rs_w, smem + stage * C::STAGE_BYTES + 2 * C::A_HALF + j * C::W_PART + wave * 1024, w.w_voff[0][j], koff);
+}
+
+// The requests of a tile's K-tile 0: 8 per wave, ONE instruction sequence for both tile shapes.  The A tile has the same image
+// in both (two 128-row halves at 0 and 16 KiB); the W requests differ in target and offset only.  256 x 256: gemm8_body's
+// prologue order W0(0), A0(0), W1(0), A1(0).  256 x 128: W_0(0), W_1(0), A_lo(0), W_0(0), W_1(0) once more (the same bytes to
+// the same place), A_hi(0).  Were the two shapes two branches, hipcc's waits behind them (for the bias quads, loaded in front)
+// would have to hold on the path that runs neither: waits for all but 3, 2, 1, 0 requests, i.e. for these.
+FK_DEV void walk_request_first(char* smem, const WalkTile& w) {
+  using C8 = Cfg8<256>;
+  using C9 = Cfg9<128>;
+  static_assert(C9::A_HALF == C8::HALF_BYTES, "both tile shapes keep the A halves at 0 and 16 KiB");
+  const int wave = __builtin_amdgcn_readfirstlane(walk_tid() >> 6);
+  char* const a_dst = smem + wave * 2048;
+  auto w_request = [&](int k) {   // k = 0 .. 3
+    char* const dst = w.small ? smem + 2 * C9::A_HALF + (k & 1) * C9::W_PART + wave * 1024
+                              : smem + (2 + (k >> 1)) * C8::HALF_BYTES + wave * 2048 + (k & 1) * 1024;
+    buffer_lds16(w.rs_w, dst, w.small ? w.w_voff[0][k & 1] : w.w_voff[k >> 1][k & 1], 0);
+  };
+  w_request(0);
+  w_request(1);
+  buffer_lds16(w.rs_a, a_dst, w.a_voff[0][0], 0);
+  buffer_lds16(w.rs_a, a_dst + 1024, w.a_voff[0][1], 0);
+  w_request(2);
+  w_request(3);
+  buffer_lds16(w.rs_a, a_dst + C8::HALF_BYTES, w.a_voff[1][0], 0);
+  buffer_lds16(w.rs_a, a_dst + C8::HALF_BYTES + 1024, w.a_voff[1][1], 0);
+}
+
+// fragment addressing shared by both tile shapes (gemm8_body / gemm9_body)
+template <bool M16>
+struct WalkFrag {
+  static constexpr int NKS = M16 ? 2 : 4, ASUB = M16 ? 4 : 2, WSUB = M16 ? 2 : 1, SUB_BYTES = (M16 ? 16 : 32) * 128;
+  int frow, koffs[NKS];
+  FK_DEV WalkFrag(int lane) {
+    frow = M16 ? (lane & 15) : (lane & 31);
+    const int fhalf = M16 ? (lane >> 4) : (lane >> 5), fsw = (frow >> 1) & 7;
+#pragma unroll
+    for (int kk = 0; kk < NKS; ++kk) koffs[kk] = ((kk * (M16 ? 4 : 2) + fhalf) ^ fsw) << 4;
+  }
+};
+
+// K loop of a 256 x 256 tile whose K-tile 0 has been requested: the rest of gemm8_body's prologue, then its loop.
+// cont: a continued tile, whose K-tile 0 has landed (above); otherwise it was requested just now (the workgroup's first tile).
+template <bool M16>
+FK_DEV void walk_run8(char* smem, const WalkTile& w, int nk, bool cont, f32x16_t (&acc)[2][4]) {
+  using C = Cfg8<256, M16>;
+  using F = WalkFrag<M16>;
+  const int tid = walk_tid();
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  walk_dma8(smem, w, wave, nk, 2, 1, 1);   // W0(1)   P4
+  walk_dma8(smem, w, wave, nk, 0, 1, 1);   // A0(1)   P1 of tile 1
+  walk_dma8(smem, w, wave, nk, 3, 1, 1);   // W1(1)   P2 of tile 1
+  const F f(lane);
+  const int a_rd = (wm * 64 + f.frow) * C::ROW_BYTES, w_rd = (wn * 32 + f.frow) * C::ROW_BYTES;
+#pragma unroll
+  for (int i = 0; i < C::NF; ++i)
+#pragma unroll
+    for (int j = 0; j < C::MF; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  bf16x8_t af[F::ASUB][F::NKS], wf[2][F::WSUB][F::NKS];
+  auto read_a = [&](int buf, int h) {
+    const char* b = smem + buf * C::BUF_BYTES + h * C::HALF_BYTES;
+#pragma unroll
+    for (int sub = 0; sub < F::ASUB; ++sub)
+#pragma unroll
+      for (int kk = 0; kk < F::NKS; ++kk) af[sub][kk] = *(const bf16x8_t*)(b + a_rd + sub * F::SUB_BYTES + f.koffs[kk]);
+  };
+  auto read_w = [&](int buf, int j) {
+    const char* b = smem + buf * C::BUF_BYTES + (2 + j) * C::HALF_BYTES;
+#pragma unroll
+    for (int sub = 0; sub < F::WSUB; ++sub)
+#pragma unroll
+      for (int kk = 0; kk < F::NKS; ++kk) wf[j][sub][kk] = *(const bf16x8_t*)(b + w_rd + sub * F::SUB_BYTES + f.koffs[kk]);
+  };
+  auto mma = [&](int i, int j) {
+#pragma unroll
+    for (int kk = 0; kk < F::NKS; ++kk)
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub) {
+        if constexpr (M16) mma16_block(acc[j][2 * i + sub], wf[j][0][kk], wf[j][1][kk], af[2 * sub][kk], af[2 * sub + 1][kk]);
+        else acc[j][2 * i + sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][0][kk], af[sub][kk], acc[j][2 * i + sub], 0, 0, 0);
+      }
+  };
+  auto phase_sync_mma = [&](int i, int j, bool landed) {
+    if (!landed) wait_vmcnt<10>();
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+    mma(i, j);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  if (!cont) wait_vmcnt<10>();   // W0(0), A0(0) landed (14 requests, 10 younger)
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  read_w(0, 0);
+  if (wm == 1) __builtin_amdgcn_s_barrier();   // the stagger: group 1 runs one barrier behind group 0
+  __builtin_amdgcn_sched_barrier(0);
+  auto tile_body = [&](auto bc, int kt, bool landed) {
+    constexpr int b = decltype(bc)::value;
+    read_a(b, 0);            walk_dma8(smem, w, wave, nk, 1, b ^ 1, kt + 1);  phase_sync_mma(0, 0, landed);
+    read_w(b, 1);            walk_dma8(smem, w, wave, nk, 2, b, kt + 2);      phase_sync_mma(0, 1, landed);
+    read_a(b, 1);            walk_dma8(smem, w, wave, nk, 0, b, kt + 2);      phase_sync_mma(1, 0, false);
+    read_w(b ^ 1, 0);        walk_dma8(smem, w, wave, nk, 3, b, kt + 2);      phase_sync_mma(1, 1, false);
+  };
+  for (int kt = 0; kt < nk; kt += 2) {
+    tile_body(std::integral_constant<int, 0>{}, kt, cont && kt == 0);
+    if (kt + 1 < nk) tile_body(std::integral_constant<int, 1>{}, kt + 1, false);
+  }
+  if (wm == 0) __builtin_amdgcn_s_barrier();   // balance the stagger
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // surplus (clamped) requests must not land under the next tile's or in the C tile
+}
+
+// the same for a 256 x 128 tile (gemm9_body): its phase P2(0) already needs W_0(1), so only the first wait differs
+template <bool M16>
+FK_DEV void walk_run9(char* smem, const WalkTile& w, int nk, bool cont, f32x16_t (&acc)[2][2]) {
+  using C = Cfg9<128, M16>;
+  using F = WalkFrag<M16>;
+  const int tid = walk_tid();
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave & 3, wn = wave >> 2;
+  walk_dma9_w(smem, w, wave, nk, 0, 1, 1);   // W_0(1)   P2(0)
+  walk_dma9_a(smem, w, wave, nk, 1, 1);      // A(1)     P1(1)
+  walk_dma9_w(smem, w, wave, nk, 1, 1, 1);   // W_1(1)   P2(1)
+  walk_dma9_w(smem, w, wave, nk, 0, 2, 2);   // W_0(2)   P2(1)
+  const F f(lane);
+  const int a_rd = (wm * 64 + f.frow) * C::ROW_BYTES, w_rd = 2 * C::A_HALF + (wn * 32 + f.frow) * C::ROW_BYTES;
+#pragma unroll
+  for (int i = 0; i < C::NF; ++i)
+#pragma unroll
+    for (int j = 0; j < C::MF; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  bf16x8_t af[F::ASUB][F::NKS], wf[2][F::WSUB][F::NKS];
+  auto read_a = [&](int stage) {
+    const char* b = smem + stage * C::STAGE_BYTES + a_rd;
+#pragma unroll
+    for (int sub = 0; sub < F::ASUB; ++sub)
+#pragma unroll
+      for (int kk = 0; kk < F::NKS; ++kk) af[sub][kk] = *(const bf16x8_t*)(b + sub * F::SUB_BYTES + f.koffs[kk]);
+  };
+  auto read_w = [&](int stage, int j) {
+    const char* b = smem + stage * C::STAGE_BYTES + w_rd + j * C::W_PART;
+#pragma unroll
+    for (int sub = 0; sub < F::WSUB; ++sub)
+#pragma unroll
+      for (int kk = 0; kk < F::NKS; ++kk) wf[j][sub][kk] = *(const bf16x8_t*)(b + sub * F::SUB_BYTES + f.koffs[kk]);
+  };
+  auto mma = [&](int j) {
+#pragma unroll
+    for (int kk = 0; kk < F::NKS; ++kk)
+#pragma unroll
+      for (int mf = 0; mf < 2; ++mf) {
+        if constexpr (M16) mma16_block(acc[j][mf], wf[j][0][kk], wf[j][1][kk], af[2 * mf][kk], af[2 * mf + 1][kk]);
+        else acc[j][mf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][0][kk], af[mf][kk], acc[j][mf], 0, 0, 0);
+      }
+  };
+  auto phase_sync_mma = [&](auto vm, int j) {
+    wait_vmcnt<decltype(vm)::value>();
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+    mma(j);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  using V10 = std::integral_constant<int, 10>;
+  using V8 = std::integral_constant<int, 8>;
+  if (!cont) wait_vmcnt<7>();   // all of K-tile 0 (its 8 requests end with A_hi(0)): the 7 requests above are younger
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  read_w(0, 0);
+  if (wn == 1) __builtin_amdgcn_s_barrier();   // the stagger
+  __builtin_amdgcn_sched_barrier(0);
+  auto tile_body = [&](auto sc, int kt) {
+    constexpr int st = decltype(sc)::value, st1 = (st + 1) % 3, st2 = (st + 2) % 3;
+    read_a(st);                        walk_dma9_a(smem, w, wave, nk, st2, kt + 2);                                              phase_sync_mma(V10{}, 0);
+    read_w(st, 1); read_w(st1, 0);     walk_dma9_w(smem, w, wave, nk, 0, st, kt + 3); walk_dma9_w(smem, w, wave, nk, 1, st2, kt + 2);    phase_sync_mma(V8{}, 1);
+  };
+  for (int kt = 0; kt < nk; kt += 3) {
+    tile_body(std::integral_constant<int, 0>{}, kt);
+    if (kt + 1 < nk) tile_body(std::integral_constant<int, 1>{}, kt + 1);
+    if (kt + 2 < nk) tile_body(std::integral_constant<int, 2>{}, kt + 2);
+  }
+  if (wn == 0) __builtin_amdgcn_s_barrier();   // balance the stagger
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// bias quads of a tile as store_tile loads them, for its WALK form
+template <class C>
+FK_DEV void walk_bias(bool have, const fk_gemm_args& p, int n0, int wn, u32x2_t (&bw)[2][4]) {
+  const int lane = walk_tid() & 63;
+  using FM = FragMap<C::M16>;
+#pragma unroll
+  for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bw[nf][q] = u32x2_t{0u, 0u};
+  if (have) {
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = n0 + C::tile_col(wn, nf) + FM::col(lane, q);
+        bw[nf][q] = *(const u32x2_t*)((const bf16_t*)p.bias + min(n, p.N - 4));   // columns >= N are never stored
+      }
+  }
+}
+
+template <int EPI, bool MIX, bool M16>
+__global__ __launch_bounds__(512, 2) void gemm_walk_kernel(const GroupArgs ga) {
+  static_assert(EPI != FK_EPI_F32DBG, "the fp32 parity epilogue keeps the one-workgroup-per-tile form");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  Hot x;
+  x.h = tm_hot(ga.e, ga.e.cls[0]);
+  TmHot hs = tm_hot(ga.e, ga.e.cls[MIX ? 1 : 0]);
+  x.xq = ga.e.xq; x.xr = ga.e.xr; x.grid = ga.e.grid; x.nk = ga.e.nk;
+  int G = ga.walk_grid;
+  if constexpr (MIX) {
+    asm volatile("" : FK_PIN_HEAD(x), "+s"(G), FK_PIN_CLASS(x.h), FK_PIN_CLASS(hs));
+    hs.n = x.h.n; hs.group_m = x.h.group_m;
+  } else {
+    asm volatile("" : FK_PIN_HEAD(x), "+s"(G), FK_PIN_CLASS(x.h));
+  }
+  const int nk = x.nk, places = (int)x.grid;
+  int place = blockIdx.x;
+  WalkTile w = walk_tile<MIX>(ga, x, hs, place);
+  walk_request_first(smem, w);
+  bool cont = false;
+  for (;;) {
+    const int next = place + G;
+    const bool more = next < places;
+    const fk_gemm_args& p = ga.p[w.pi];
+    const int wave = __builtin_amdgcn_readfirstlane(walk_tid() >> 6);
+    u32x2_t bw[2][4];
+    // behind the K loop: this tile's bias, the next tile's K-tile 0, then this tile's epilogue
+    auto hand_over = [&](auto cfg, int wn) {
+      using C = decltype(cfg);
+      walk_bias<C>(EPI != FK_EPI_SCALE && p.bias, p, w.n0, wn, bw);
+      // UNCONDITIONAL: with the requests under `if (more)` hipcc's wait for the bias quads must also hold on the path without
+      // them, where nothing is younger than the bias loads -- it becomes a wait for all but 3, 2, 1, 0 requests, i.e. for
+      // the next tile's operands.  A workgroup's last tile requests its own K-tile 0 once more (64 KiB out of L2, landing in
+      // the free front of the ring; waited for at the kernel's end).
+      const WalkTile nx = walk_tile<MIX>(ga, x, hs, more ? next : place);
+      // Mixed grid, the next tile of the other shape: the two shapes cut the W part of the ring's front differently (see the
+      // invariant above), so EVERY wave's surplus requests must have landed -- each wave has waited for its own -- before any
+      // wave requests into it.
+      if constexpr (MIX) {
+        if (nx.small != w.small) __builtin_amdgcn_s_barrier();
+      }
+      walk_request_first(smem, nx);
+    };
+    if (MIX && w.small) {
+      using C = Cfg9<128, M16>;
+      f32x16_t acc[2][2];
+      walk_run9<M16>(smem, w, nk, cont, acc);
+      hand_over(C{}, wave >> 2);
+      store_tile<EPI, 128, C, -1, 8, true>(acc, p, smem, w.m0, w.n0, wave & 3, wave >> 2, nullptr, w.flags, bw);
+    } else {
+      using C = Cfg8<256, M16>;
+      f32x16_t acc[2][4];
+      walk_run8<M16>(smem, w, nk, cont, acc);
+      hand_over(C{}, wave & 3);
+      store_tile<EPI, 256, C, 0, 8, true>(acc, p, smem, w.m0, w.n0, wave >> 2, wave & 3, nullptr, w.flags, bw);
+      store_tile<EPI, 256, C, 1, 8, true>(acc, p, smem, w.m0, w.n0, wave >> 2, wave & 3, nullptr, w.flags, bw);
+    }
+    if (!more) break;
+    cont = true;
+    lds_barrier();   // every wave is done reading the C tile: K-tile 1 may land on it
+    // the next tile's addressing once more, from a place the compiler cannot connect with the one above: nothing of it is
+    // kept across the epilogue, whose batches need the registers
+    place = next;
+    asm volatile("" : "+s"(place) :: "memory");
+    w = walk_tile<MIX>(ga, x, hs, place);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last tile's repeated requests land before the LDS is given back
+}
+
+template <int EPI, bool MIX, bool M16>
+int launch_walk(GroupArgs& ga, const fk_gemm_args* probs, int n, int big_cols, int G, hipStream_t stream) {
+  int places;
+  if constexpr (MIX) {
+    const int ncols128 = (probs[0].N - big_cols * 256 + 127) / 128;
+    int32_t Ms[FK_MAX_GROUP];
+    for (int i = 0; i < n; ++i) Ms[i] = probs[i].M;
+    const int tb = tm_fill_class(ga.e.cls[0], Ms, n, big_cols, 0, ga.e.group_m);
+    const int ts = tm_fill_class(ga.e.cls[1], Ms, n, ncols128, big_cols * 256, ga.e.group_m);
+    if (tb < 0 || ts < 0 || !tm_fill_mix(ga.e, tb, ts)) return FK_E2BIG_STRIDES;
+    places = tb + ts;
+    tm_fill_grid(ga.e, (uint32_t)places);
+  } else {
+    places = count_tiles<256>(ga, probs, n);
+    if (places < 0) return FK_E2BIG_STRIDES;
+  }
+  ga.walk_grid = G < places ? G : places;
+  constexpr int SMEM = MIX ? MIX_SMEM : Cfg8<256>::SMEM_BYTES;
+  static_assert(WALK_CT_OFF + Cfg8<256>::CT_BYTES / 2 <= Cfg8<256>::SMEM_BYTES && WALK_CT_OFF + Cfg9<128>::CT_BYTES <= MIX_SMEM &&
+                WALK_CT_OFF == Cfg8<256>::BUF_BYTES && Cfg9<128>::STAGE_BYTES <= WALK_CT_OFF, "tile walk: LDS plan");
+  auto kern = gemm_walk_kernel<EPI, MIX, M16>;
+  FK_ENSURE_MAX_LDS(kern, SMEM, "fk_gemm_bf16 (tile walk, one workgroup per CU)");
+  hipLaunchKernelGGL(kern, dim3(ga.walk_grid), dim3(512), SMEM, stream, ga);
+  FK_CHECK_LAUNCH("fk_gemm_bf16 (tile walk, one workgroup per CU)");
+  return FK_OK;
+}
+
 // variant: 128 -> gemm9_kernel (256 x 128), 256 -> gemm8_kernel (256 x 256), 384 -> mixed, 512 -> split-K pairs of 256 x 256,
 // 640 -> stream-K ranges over 256 x 256 tiles (big_cols carries the grid size)
+// walk > 0 (256 / 384 only): the tile walk with that many workgroups
 template <int EPI, bool M16>
-int launch_variant_m(GroupArgs& ga, const fk_gemm_args* probs, int n, int variant, int big_cols, hipStream_t stream) {
+int launch_variant_m(GroupArgs& ga, const fk_gemm_args* probs, int n, int variant, int big_cols, int walk, hipStream_t stream) {
+  if constexpr (EPI != FK_EPI_F32DBG) {
+    if (walk > 0 && variant == 256) return launch_walk<EPI, false, M16>(ga, probs, n, 0, walk, stream);
+    if (walk > 0 && variant == 384) return launch_walk<EPI, true, M16>(ga, probs, n, big_cols, walk, stream);
+  }
   switch (variant) {
     case 256: return launch8<EPI, 256, false, 0, M16>(ga, probs, n, stream);
     case 384: return launch_mix<EPI, M16>(ga, probs, n, big_cols, stream);
@@ -1238,9 +1673,9 @@ int launch_variant_m(GroupArgs& ga, const fk_gemm_args* probs, int n, int varian
   }
 }
 template <int EPI>
-int launch_variant(GroupArgs& ga, const fk_gemm_args* probs, int n, int variant, int big_cols, bool m16, hipStream_t stream) {
-  return m16 ? launch_variant_m<EPI, true>(ga, probs, n, variant, big_cols, stream)
-             : launch_variant_m<EPI, false>(ga, probs, n, variant, big_cols, stream);
+int launch_variant(GroupArgs& ga, const fk_gemm_args* probs, int n, int variant, int big_cols, int walk, bool m16, hipStream_t stream) {
+  return m16 ? launch_variant_m<EPI, true>(ga, probs, n, variant, big_cols, walk, stream)
+             : launch_variant_m<EPI, false>(ga, probs, n, variant, big_cols, walk, stream);
 }
 
 int cu_count() {
@@ -1288,6 +1723,14 @@ constexpr double SK_TAIL_WHOLE = 17.0e-6, SK_TAIL_SYM = 9.0e-6;
 #define FK_SPLITK_SYMMETRIC_DEFAULT 1
 #endif
 constexpr int SK_MODE_DEFAULT = FK_SPLITK_SYMMETRIC_DEFAULT ? SK_SYM : SK_WHOLE;
+// which grids with more tiles than CUs take the tile walk unasked: bit 0 the 256 x 256 ones, bit 1 the mixed ones.  1: inside the
+// 512^2 edit the MLP-up launch (256 x 256 grid) gains 3.6 %; the fused QKV launch (mixed grid) measured -0.7 % in one trace
+// whose untouched kernels drifted by -0.1 .. +1.5 %, i.e. not separable from noise (profiles/gemm_walk_kernel_stats.md), so
+// mixed grids walk only where the call's plan says FK_GEMM_PLAN_WALK
+#ifndef FK_GEMM_WALK_DEFAULT
+#define FK_GEMM_WALK_DEFAULT 1
+#endif
+constexpr int WALK_DEFAULT = FK_GEMM_WALK_DEFAULT;
 
 // nbm: row tiles summed over the problems of the launch; N, K shared.  allow: bit 0 mixed, bit 1 split-K.
 Plan plan_launch(long nbm, int N, int K, int G, int allow, bool have_ws, int ws_slots, int sk_mode) {
@@ -1362,10 +1805,12 @@ int fk_gemm2_launch(const fk_gemm_args* probs, int n, int variant_hint, hipStrea
   }
   constexpr int SK_BITS = FK_GEMM_PLAN_SPLITK_WHOLE | FK_GEMM_PLAN_SPLITK_SYMMETRIC | FK_GEMM_PLAN_SPLITK_UNANNOUNCED;
   const int sk_bits = ctl.plan & SK_BITS;
-  if (ctl.plan != 0 && (ctl.plan & ~(15 | SK_BITS)) != 0 || (ctl.plan != 0 && !(ctl.plan & FK_GEMM_PLAN_EXPLICIT)) ||
-      (sk_bits & (sk_bits - 1)) != 0) {
+  const int walk_cap = (ctl.plan & FK_GEMM_PLAN_WALK_BITS) >> FK_GEMM_PLAN_WALK_CAP_SHIFT;
+  const bool walk_never = ctl.plan & FK_GEMM_PLAN_TILE_PER_WG, walk_forced = (ctl.plan & FK_GEMM_PLAN_WALK) || walk_cap > 0;
+  if (ctl.plan != 0 && (ctl.plan & ~(15 | SK_BITS | FK_GEMM_PLAN_WALK_BITS)) != 0 || (ctl.plan != 0 && !(ctl.plan & FK_GEMM_PLAN_EXPLICIT)) ||
+      (sk_bits & (sk_bits - 1)) != 0 || (walk_never && walk_forced)) {
     fk_set_error("fk_gemm_bf16: plan %d is not 0 (default) or FK_GEMM_PLAN_EXPLICIT | allow bits 0..2 | at most one "
-                 "FK_GEMM_PLAN_SPLITK_* exchange", ctl.plan);
+                 "FK_GEMM_PLAN_SPLITK_* exchange | FK_GEMM_PLAN_TILE_PER_WG or FK_GEMM_PLAN_WALK / _WALK_CAP(G)", ctl.plan);
     return FK_EINVAL;
   }
   if (ctl.group_m < 0 || ctl.group_m > 4096 || !(ctl.mfma == 0 || ctl.mfma == 16 || ctl.mfma == 32)) {
@@ -1508,16 +1953,25 @@ int fk_gemm2_launch(const fk_gemm_args* probs, int n, int variant_hint, hipStrea
   static const bool g10_auto = !(getenv("FK_GEMM10") && atoi(getenv("FK_GEMM10")) == 0);
   if (plan.variant == 256 && variant_hint == 0 && m16 && g10_auto && K >= 6144 && t256 >= 4L * G) plan.variant = 1024;
   report_variant(probs, plan.variant);
+  // tile walk (launch_walk): a 256 x 256 or mixed grid with more tiles than workgroups as one workgroup per CU.  The built rule
+  // (WALK_DEFAULT: bit 0 the 256 x 256 grids, bit 1 the mixed ones) holds what the kernel traces showed to gain; the call's plan
+  // may force either form.  Same bits, so variant_used does not tell the two apart.
+  int walk = 0;
+  if ((plan.variant == 256 || plan.variant == 384) && !walk_never && probs[0].out_fp32 != 2) {
+    const long tiles = plan.variant == 256 ? t256 : nbm_total * (plan.big_cols + 2L * (N / 256 - plan.big_cols));
+    const int Gw = walk_cap > 0 ? walk_cap : G;
+    if (tiles > Gw && (walk_forced || (WALK_DEFAULT & (plan.variant == 256 ? 1 : 2)))) walk = Gw;
+  }
   int rc;
   switch (probs[0].out_fp32 == 2 ? FK_EPI_F32DBG : probs[0].epilogue) {
-    case FK_EPI_F32DBG: rc = launch_variant<FK_EPI_F32DBG>(ga, probs, n, plan.variant, plan.big_cols, m16, stream); break;
-    case FK_EPI_NONE: rc = launch_variant<FK_EPI_NONE>(ga, probs, n, plan.variant, plan.big_cols, m16, stream); break;
-    case FK_EPI_GELU_TANH: rc = launch_variant<FK_EPI_GELU_TANH>(ga, probs, n, plan.variant, plan.big_cols, m16, stream); break;
-    case FK_EPI_SILU: rc = launch_variant<FK_EPI_SILU>(ga, probs, n, plan.variant, plan.big_cols, m16, stream); break;
-    case FK_EPI_GATE_RES: rc = launch_variant<FK_EPI_GATE_RES>(ga, probs, n, plan.variant, plan.big_cols, m16, stream); break;
-    case FK_EPI_RES: rc = launch_variant<FK_EPI_RES>(ga, probs, n, plan.variant, plan.big_cols, m16, stream); break;
-    case FK_EPI_SCALE: rc = launch_variant<FK_EPI_SCALE>(ga, probs, n, plan.variant, plan.big_cols, m16, stream); break;
-    case FK_EPI_QKV: rc = launch_variant<FK_EPI_QKV>(ga, probs, n, plan.variant, plan.big_cols, m16, stream); break;
+    case FK_EPI_F32DBG: rc = launch_variant<FK_EPI_F32DBG>(ga, probs, n, plan.variant, plan.big_cols, walk, m16, stream); break;
+    case FK_EPI_NONE: rc = launch_variant<FK_EPI_NONE>(ga, probs, n, plan.variant, plan.big_cols, walk, m16, stream); break;
+    case FK_EPI_GELU_TANH: rc = launch_variant<FK_EPI_GELU_TANH>(ga, probs, n, plan.variant, plan.big_cols, walk, m16, stream); break;
+    case FK_EPI_SILU: rc = launch_variant<FK_EPI_SILU>(ga, probs, n, plan.variant, plan.big_cols, walk, m16, stream); break;
+    case FK_EPI_GATE_RES: rc = launch_variant<FK_EPI_GATE_RES>(ga, probs, n, plan.variant, plan.big_cols, walk, m16, stream); break;
+    case FK_EPI_RES: rc = launch_variant<FK_EPI_RES>(ga, probs, n, plan.variant, plan.big_cols, walk, m16, stream); break;
+    case FK_EPI_SCALE: rc = launch_variant<FK_EPI_SCALE>(ga, probs, n, plan.variant, plan.big_cols, walk, m16, stream); break;
+    case FK_EPI_QKV: rc = launch_variant<FK_EPI_QKV>(ga, probs, n, plan.variant, plan.big_cols, walk, m16, stream); break;
     default: fk_set_error("fk_gemm_bf16: unknown epilogue %d", probs[0].epilogue); return FK_EUNSUPPORTED;
   }
   // FK_E2BIG_STRIDES from a launcher: the strides were fine (checked above) but the tile count leaves the exact range of the

@@ -127,6 +127,38 @@ FK_TM_FN void tm_tile(const TileEntry& e, const TmClass& c, int bn, int t, int& 
   tm_tile_hot(tm_hot(e, c), bn, t, pi, m0, n0);
 }
 
+// ---- tile walk: G workgroups (one per CU) instead of one workgroup per tile -----------------------------------------------------
+// The launch keeps its `grid` PLACES (e.grid / xq / xr: a place is what the workgroup index is to the one-workgroup-per-tile launch) and workgroup
+// g takes the places g, g + G, g + 2 G, ... in turn.  The dispatcher hands place b to the CU that becomes free first, which on
+// a grid of equal tiles is the CU that ran place b - G: a CU sees the same tiles in the same order either way (and, G being a
+// multiple of 8 on the device, the same XCD chunk).
+FK_TM_FN int tm_walk_count(uint32_t places, uint32_t G, uint32_t g) { return g < places ? (int)((places - 1 - g) / G) + 1 : 0; }
+FK_TM_FN uint32_t tm_walk_place(uint32_t G, uint32_t g, uint32_t i) { return g + i * G; }
+// mixed grid: place b of the launch is tile `t` of class 0 (256 x 256; returns false) or of class 1 (256 x 128; true) -- every
+// XCD's chunk of the big tiles first, then its chunk of the small ones
+FK_TM_FN bool tm_mix_place(int32_t big_start, int32_t big_cnt, int32_t small_start, uint32_t b, int& t) {
+  const int idx = (int)(b >> 3);
+  const bool small = idx >= big_cnt;
+  t = small ? small_start + idx - big_cnt : big_start + idx;
+  return small;
+}
+FK_TM_FN bool tm_mix_place(const TileEntry& e, uint32_t b, int& t) {
+  return tm_mix_place(e.xcd[b & 7].big_start, e.xcd[b & 7].big_cnt, e.xcd[b & 7].small_start, b, t);
+}
+// the per-XCD table of a mixed grid of tb big and ts small tiles; false: an XCD would get fewer places than big tiles
+FK_TM_FN bool tm_fill_mix(TileEntry& e, int tb, int ts) {
+  const int W = tb + ts;
+  int bs = 0, ss = 0;
+  for (int x = 0; x < 8; ++x) {
+    const int wx = W / 8 + (x < W % 8 ? 1 : 0), bx = tb / 8 + (x < tb % 8 ? 1 : 0);
+    if (wx < bx) return false;
+    e.xcd[x] = {bs, bx, ss, 0};
+    bs += bx;
+    ss += wx - bx;
+  }
+  return true;
+}
+
 // ---- host: fill the records -----------------------------------------------------------------------------------------------
 // group_m of the launch: a depth beyond the deepest problem changes nothing (one group per problem either way), so it is
 // clamped there, which keeps every divisor of the order within the row-tile counts

@@ -212,6 +212,8 @@ def gemm(a, w, bias=None, out=None, epilogue=FK_EPI_NONE, res=None, gate=None, o
 # FK_ATTN_SPLIT, FK_ATTN_BWD of rounds 2-4 are read once, here.
 FK_GEMM_PLAN_EXPLICIT = 8
 FK_GEMM_PLAN_SPLITK = {"default": 0, "whole": 16, "symmetric": 32, "unannounced": 64}   # include/fk.h: FK_GEMM_PLAN_SPLITK_*
+FK_GEMM_PLAN_WALK = {"default": 0, "tile_per_wg": 128, "walk": 256}                       # include/fk.h: FK_GEMM_PLAN_TILE_PER_WG / _WALK
+FK_GEMM_PLAN_WALK_CAP_SHIFT = 16
 
 
 def _env_int(name, default):
@@ -223,6 +225,8 @@ LAUNCH = SimpleNamespace(
     gemm_variant=_env_int("FK_GEMM_BN", 0),         # 0 = launch plan; 128 / 256 / 384 / 512 / 640 force a form where it applies
     gemm_plan=(FK_GEMM_PLAN_EXPLICIT | (_env_int("FK_GEMM_PLAN", 3) & 7)) if os.environ.get("FK_GEMM_PLAN") else 0,
     gemm_splitk=0,                                  # exchange of the split-K pairs: 0 = built default, or a FK_GEMM_PLAN_SPLITK bit
+    # tile walk of the 256 x 256 / mixed grids (plan bits): FK_GEMM_WALK=0 never, 1 wherever tiles > CUs, unset = the built rule
+    gemm_walk={"0": 128, "1": 256}.get(os.environ.get("FK_GEMM_WALK", ""), 0),
     gemm_group_m=_env_int("FK_GEMM_GROUP_M", 0),
     gemm_mfma=_env_int("FK_GEMM_MFMA", 0),          # 0 = built default (16); 16 / 32
     attn_grid={0: -1, 1: 0}.get(_env_int("FK_ATTN_SPLIT", 1), _env_int("FK_ATTN_SPLIT", 1)),   # 0 default, -1 plain grid, >= 2 forced
@@ -267,11 +271,22 @@ def gemm_set_splitk_exchange(mode):
     _set_launch(gemm_splitk=FK_GEMM_PLAN_SPLITK[mode])
 
 
+def gemm_set_walk(form="default", cap=0):
+    """Tile walk of the large-tile GEMMs (fk_gemm_args.plan): a 256 x 256 or mixed grid with more tiles than workgroups runs as
+    one workgroup per CU, each walking its tiles with the next tile's first operands requested in front of the epilogue.
+    "default" = the library's built rule, "tile_per_wg" = never (one workgroup per tile), "walk" = wherever it applies;
+    ``cap`` > 0 (implies "walk"): at most that many workgroups (tests).  Same bits every way."""
+    if not 0 <= int(cap) <= 0x7fff or (cap and form == "tile_per_wg"):
+        raise ValueError(f"gemm_set_walk: cap {cap} is not in 0..32767, or given with 'tile_per_wg'")
+    _set_launch(gemm_walk=FK_GEMM_PLAN_WALK[form] | (int(cap) << FK_GEMM_PLAN_WALK_CAP_SHIFT))
+
+
 def launch_plan():
     """fk_gemm_args.plan / fk_block_ws.gemm_plan of this module's launch defaults."""
-    if not LAUNCH.gemm_splitk:
+    extra = LAUNCH.gemm_splitk | LAUNCH.gemm_walk
+    if not extra:
         return LAUNCH.gemm_plan
-    return (LAUNCH.gemm_plan or (FK_GEMM_PLAN_EXPLICIT | 3)) | LAUNCH.gemm_splitk
+    return (LAUNCH.gemm_plan or (FK_GEMM_PLAN_EXPLICIT | 3)) | extra
 
 
 def gemm_set_group_m(depth):

@@ -117,7 +117,8 @@ typedef struct fk_gemm_args {
    *             grids (bit-identical results), bit 1 split-K pairs (results differ in the last bits from the unsplit sum: with
    *             bit 1 clear a sample's result does not depend on the grid it runs in -- "batch-invariant"), bit 2 stream-K
    *             ranges for long-K launches with a poorly filled last round (measured slower inside the edits: off by default);
-   *             optionally one FK_GEMM_PLAN_SPLITK_* bit (below): the exchange of the split-K pairs.
+   *             optionally one FK_GEMM_PLAN_SPLITK_* bit (below): the exchange of the split-K pairs; optionally
+   *             FK_GEMM_PLAN_TILE_PER_WG / FK_GEMM_PLAN_WALK / FK_GEMM_PLAN_WALK_CAP(G) (below): the tile walk.
    *   group_m : 0 = default (8): depth in row tiles of the grouped tile order; >= the row-tile count: every XCD owns a column
    *             range.  Results do not depend on it.
    *   mfma    : 0 = default (16); 16 = v_mfma_f32_16x16x32_bf16, 32 = v_mfma_f32_32x32x16_bf16 (the two differ in the last
@@ -140,6 +141,17 @@ typedef struct fk_gemm_args {
 #define FK_GEMM_PLAN_SPLITK_WHOLE 16
 #define FK_GEMM_PLAN_SPLITK_SYMMETRIC 32
 #define FK_GEMM_PLAN_SPLITK_UNANNOUNCED 64
+/* Tile walk (with FK_GEMM_PLAN_EXPLICIT): a 256 x 256 or mixed grid with more tiles than workgroups may run as one workgroup
+ * per CU, each walking tiles g, g + G, ... of the launch's tile order with the next tile's first operands requested in front
+ * of the current tile's epilogue.  Same bits as one workgroup per tile; variant_used reports 256 / 384 either way.
+ *   TILE_PER_WG : never walk -- one workgroup per tile (A/B runs, the reference side of the tests).
+ *   WALK        : walk wherever the grid has more tiles than workgroups, also where the built rule would not.
+ *   WALK_CAP(G) : at most G workgroups (1 .. 32767; implies WALK); 0 = one per CU. */
+#define FK_GEMM_PLAN_TILE_PER_WG 128
+#define FK_GEMM_PLAN_WALK 256
+#define FK_GEMM_PLAN_WALK_CAP_SHIFT 16
+#define FK_GEMM_PLAN_WALK_CAP(G) ((int32_t)(G) << FK_GEMM_PLAN_WALK_CAP_SHIFT)
+#define FK_GEMM_PLAN_WALK_BITS (FK_GEMM_PLAN_TILE_PER_WG | FK_GEMM_PLAN_WALK | FK_GEMM_PLAN_WALK_CAP(0x7fff))
 #define FK_SPLITK_SLOT_BYTES (256 * 256 * 4 + 8)
 
 int fk_gemm_bf16(const fk_gemm_args* args, fk_stream_t stream);
