@@ -25,6 +25,11 @@ Data rules
 
 Launch forms: 128 = gemm9 (256 x 128), 256 = gemm8, 384 = gemm_mix, 512 = split-K pairs, 640 = stream-K ranges, 1024 = gemm10
 (16 x 16 x 32 MFMA only).  A case whose forced form does not apply is a mistake in these tables.
+
+Section W (tests/test_hip_gemm_walk_exact.py): forms 256 and 384 as the tile walk, every launch under the workgroup caps of
+`walk_caps`.  The same data rules through the same `case_problem`; what the launcher decides for a mixed grid (`mixed_big_cols`)
+and the order in which a workgroup meets big and small tiles (`mix_table`, `mix_place`, `walk_shapes`) are restated here and held
+against csrc/gemm_tile_map.h by tests/test_gemm_large_host.py.
 """
 import functools
 import math
@@ -73,6 +78,19 @@ F_KS = (2048, 3072, 6400)
 F_EPILOGUES = ("f32", "none_bias", "gate_res")
 G_KS = (64, 192)
 G_EPILOGUES = ("f32", "none_bias", "gate_res")
+# section W: the tile walk (gemm_walk_kernel) under workgroup caps, tests/test_hip_gemm_walk_exact.py.  It reuses the tables of
+# A .. D at forms 256 / 384 (bf16 output: the walk has no fp32-parity epilogue) and adds:
+W_FORMS = (256, 384)
+W_EPI_A = "none_bias"
+W_LONG_KS = (3072, 6144, 6400)                          # 48, 96 and 100 K-tiles: even and odd trip counts at production depth
+W_LONG_SHAPES = {256: (513, 768), 384: (513, 1024)}     # 9 tiles; 3 big + 18 small
+W_C_FORM = W_D_FORM = 256
+W_GM_BR = ((2, 150), (4, 130), (1, 257))                # the mixed form's grouped case: M = 300, 520, 257, 2 + 3 + 2 row tiles
+W_GM_N, W_GM_K = 768, 192
+W_GM_GROUP_M = (0, 2)
+W_H_BATCH, W_H_S_TXT, W_H_S_IMG, W_H_HEADS = 2, 70, 280, 2   # section H's shapes (its data is random, not from `problem`)
+W_H_THIRDS = (3, 2)
+FK_RATE_256 = 1.22        # csrc/gemm_pingpong_bf16.hip: rate of the 256 x 256 kernel over the 256 x 128 one in the launch plan
 
 
 def tiles256(M, N):
@@ -135,6 +153,130 @@ def persistent_grid(cus):
     B = 28 if M % 28 == 0 else 4
     assert tiles256(M, N) >= 4 * cus and M % 256 != 0 and M % B == 0
     return M, N, B, M // B
+
+
+# ---- section W: the caps, and the launcher's mixed grid and its place order restated ------------------------------------------
+
+def walk_caps(tiles):
+    """The caps (workgroups of the launch) a launch of `tiles` places runs under: 1 (one workgroup walks the whole launch, the
+    longest chain of hand-overs), 2, 3 and tiles - 1 (tiles == cap + 1: workgroup 0 alone is handed a second tile), each only
+    where tiles > cap -- at tiles <= cap the launcher keeps one workgroup per tile -- and once.  A one-tile launch gets none."""
+    out = []
+    for cap in (1, 2, 3, tiles - 1):
+        if 1 <= cap < tiles and cap not in out:
+            out.append(cap)
+    return out
+
+
+def makespan(nb, ns, cs, G):
+    """`makespan()` of csrc/gemm_pingpong_bf16.hip restated: nb tiles of cost 1, then ns of cost cs, list-scheduled on G CUs."""
+    full, rem = divmod(nb, G)
+    ta, tb = float(full), float(full) + 1.0
+    end = 0.0 if nb == 0 else (tb if rem else ta)
+    na = G - rem
+    while ns > 0:
+        if rem == 0 or ta <= tb:
+            ta, ns = ta + cs, ns - min(ns, na)
+            end = max(end, ta)
+        else:
+            tb, ns = tb + cs, ns - min(ns, rem)
+            end = max(end, tb)
+    return end
+
+
+def mixed_big_cols(nbm, N, cus=256):
+    """Column tiles of 256 in the mixed grid that the forced form 384 launches for `nbm` row tiles (summed over the problems)
+    of width N on `cus` CUs -- fk_gemm2_launch restated: the launch plan's own split where a mixed grid pays, else the split
+    of the shortest makespan (the first of equals) among those with at least 8 small tiles; 0: the form does not apply."""
+    if N % 256 != 0 or N < 512:
+        return 0
+    c128, nb256 = 0.5 * FK_RATE_256, N // 256
+    tbest = min(makespan(0, nbm * (N // 128), c128, cus), makespan(nbm * nb256, 0, c128, cus))
+    splits = [cb for cb in range(1, nb256) if nbm * 2 * (nb256 - cb) >= 8]
+    planned = 0
+    for cb in splits:
+        t = makespan(nbm * cb, nbm * 2 * (nb256 - cb), c128, cus)
+        if t < tbest * 0.97:
+            tbest, planned = t, cb
+    if planned:
+        return planned
+    forced, tb = 0, 1e30
+    for cb in splits:
+        t = makespan(nbm * cb, nbm * 2 * (nb256 - cb), c128, cus)
+        if t < tb:
+            tb, forced = t, cb
+    return forced
+
+
+def walk_grid(form, Ms, N, cus=256):
+    """(big tiles, small tiles) of the launch of problems with rows `Ms` and width N under form 256 (no small ones) / 384."""
+    nbm = sum(-(-M // 256) for M in Ms)
+    if form == 256:
+        return nbm * (N // 256), 0
+    cb = mixed_big_cols(nbm, N, cus)
+    assert form == 384 and cb > 0, f"the mixed form does not apply to Ms {Ms} N {N}"
+    return nbm * cb, nbm * 2 * (N // 256 - cb)
+
+
+def mix_table(tb, ts):
+    """`tm_fill_mix()` of csrc/gemm_tile_map.h restated: per XCD (first big tile, big tiles, first small tile); None where an
+    XCD would get fewer places than big tiles (the launcher then falls back to a plain grid)."""
+    W, table, bs, ss = tb + ts, [], 0, 0
+    for x in range(8):
+        wx, bx = W // 8 + (x < W % 8), tb // 8 + (x < tb % 8)
+        if wx < bx:
+            return None
+        table.append((bs, bx, ss))
+        bs, ss = bs + bx, ss + wx - bx
+    return table
+
+
+def mix_place(table, b):
+    """`tm_mix_place()` restated: place b of a mixed launch is (small, tile index inside its class)."""
+    big_start, big_cnt, small_start = table[b & 7]
+    idx = b >> 3
+    return (True, small_start + idx - big_cnt) if idx >= big_cnt else (False, big_start + idx)
+
+
+def walk_shapes(tb, ts, cap):
+    """The tile walk's place order restated (tm_walk_count / tm_walk_place): for each of the min(cap, places) workgroups the
+    shapes (True: 256 x 128) of its places g, g + cap, ... in turn.  A pure grid (ts == 0) has big tiles only."""
+    places = tb + ts
+    table = mix_table(tb, ts) if ts else None
+    assert not ts or table is not None
+    return [[bool(ts) and mix_place(table, b)[0] for b in range(g, places, cap)] for g in range(min(cap, places))]
+
+
+def shape_changes(tb, ts, cap):
+    """Hand-overs of a launch under `cap` that change the tile shape: (the most inside one workgroup's list, big -> small ones
+    in all, small -> big ones in all).  Each of them takes the workgroup barrier in `hand_over` of gemm_walk_kernel."""
+    most = to_small = to_big = 0
+    for shapes in walk_shapes(tb, ts, cap):
+        ch = [(a, b) for a, b in zip(shapes, shapes[1:]) if a != b]
+        most = max(most, len(ch))
+        to_small += sum(1 for a, b in ch if b)
+        to_big += sum(1 for a, b in ch if not b)
+    return most, to_small, to_big
+
+
+def w_h_problems():
+    """Rows of the two problems of section H's grouped launch (image rows of both batches, text rows) and its widths."""
+    return (W_H_BATCH * W_H_S_IMG, W_H_BATCH * W_H_S_TXT), [t * W_H_HEADS * 128 for t in W_H_THIRDS]
+
+
+def walk_launches():
+    """Sorted unique (part, form, rows of the problems, N, K) of every launch shape of section W, one-tile launches (which get
+    no cap) left out: what tests/test_hip_gemm_walk_exact.py runs under each cap of `walk_caps(sum(walk_grid(...)))`."""
+    out = set()
+    for form in W_FORMS:
+        out |= {("A", form, (M,), N, K) for M, N in A_SHAPES[form] for K in A_KS}
+        out |= {("A", form, (W_LONG_SHAPES[form][0],), W_LONG_SHAPES[form][1], K) for K in W_LONG_KS}
+        out |= {("B", form, (M,), N, K) for M, N in B_SHAPES[form] for K in B_KS}
+        out |= {("H", form, w_h_problems()[0], N, 192) for N in w_h_problems()[1]}
+    out |= {("C", W_C_FORM, (B * Rr,), C_N, C_K) for B, Rr in C_BR}
+    out.add(("D", W_D_FORM, tuple(B * Rr for B, Rr in D_BR), D_N, D_K))
+    out.add(("D", 384, tuple(B * Rr for B, Rr in W_GM_BR), W_GM_N, W_GM_K))
+    return sorted(c for c in out if sum(walk_grid(c[1], c[2], c[3])) > 1)
 
 
 # ---- data -----------------------------------------------------------------------------------------------------------------------
@@ -334,6 +476,15 @@ def host_cases(cus=256):
             for _, M, N, K in streamk_cases() for epi in F_EPILOGUES}
     M, N, B, Rr = persistent_grid(cus)
     out |= {("G", M, N, K, B, Rr, epi) for K in G_KS for epi in G_EPILOGUES}
+    # W: what tests/test_hip_gemm_walk_exact.py builds (its part H runs section H's random data against the unfused launch)
+    for part, form, Ms, N, K in walk_launches():
+        if part == "A":
+            out.add(("W", Ms[0], N, K, 1, 0, W_EPI_A))
+        elif part == "B":
+            out |= {("W", Ms[0], N, K, 1, Ms[0] if epi in GATED else 0, epi) for epi in EPILOGUES}
+    out |= {("W", B * Rr, C_N, C_K, B, Rr if epi in GATED else 0, epi) for B, Rr in C_BR for epi in C_EPILOGUES}
+    out |= {("W", B * Rr, D_N, D_K, B, Rr if epi in GATED else 0, epi) for B, Rr in D_BR for epi in D_EPILOGUES}
+    out |= {("W", B * Rr, W_GM_N, W_GM_K, B, Rr if epi in GATED else 0, epi) for B, Rr in W_GM_BR for epi in D_EPILOGUES}
     return sorted(out)
 
 

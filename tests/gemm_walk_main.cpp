@@ -6,8 +6,10 @@
 // names is the one blockIdx.x = place computes in that launch (tm_xcd_chunk + tm_tile; mixed grids: the per-XCD table).
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <set>
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -74,6 +76,14 @@ static void check_walk(const std::vector<int32_t>& Ms, int N, int group_m, int b
   tm_fill_grid(e, (uint32_t)places);
   const std::set<Tile> want = all_tiles(Ms, N, big_cols, mixed);
   CHECK((int)want.size() == places, "N %d big_cols %d: %d places for %d tiles", N, big_cols, places, (int)want.size());
+  // the place order of a mixed grid is big tiles first: no place behind a small tile names a big one.  A workgroup takes its
+  // places in rising order whatever G is, so its list changes shape at most once, from big to small
+  if (mixed) {
+    int ti;
+    for (int b = 0; b + 1 < places; ++b)
+      CHECK(!(tm_mix_place(e, (uint32_t)b, ti) && !tm_mix_place(e, (uint32_t)(b + 1), ti)), "N %d big_cols %d: place %d is big behind a small one",
+            N, big_cols, b + 1);
+  }
   for (int G : Gs) {
     std::vector<int> seen(places, 0);
     std::set<Tile> got;
@@ -108,8 +118,33 @@ static void check_walk(const std::vector<int32_t>& Ms, int N, int group_m, int b
   }
 }
 
-int main(int argc, char**) {
-  if (argc > 1) return 0;   // any argument: "can this build start here?" (the test falls back to the plain build if not)
+// --places N big_cols group_m M...: one line "small tile" per place of that mixed launch, from tm_fill_class / tm_fill_mix /
+// tm_mix_place themselves (tests/test_gemm_large_host.py holds the restatement in tests/gemm_large_cases.py against it)
+static int print_places(int argc, char** argv) {
+  if (argc < 6) return 2;
+  const int N = atoi(argv[2]), big_cols = atoi(argv[3]), group_m = atoi(argv[4]);
+  std::vector<int32_t> Ms;
+  for (int i = 5; i < argc; ++i) Ms.push_back(atoi(argv[i]));
+  const int n = (int)Ms.size();
+  if (n > TM_MAX_GROUP || big_cols < 1 || big_cols * 256 >= N) return 2;
+  TileEntry e = {};
+  e.n = n;
+  e.group_m = tm_group_m(Ms.data(), n, group_m);
+  const int tb = tm_fill_class(e.cls[0], Ms.data(), n, big_cols, 0, e.group_m);
+  const int ts = tm_fill_class(e.cls[1], Ms.data(), n, (N - big_cols * 256 + 127) / 128, big_cols * 256, e.group_m);
+  if (tb < 0 || ts < 0 || !tm_fill_mix(e, tb, ts)) return 3;
+  printf("%d %d\n", tb, ts);
+  for (int b = 0; b < tb + ts; ++b) {
+    int ti;
+    const bool small = tm_mix_place(e, (uint32_t)b, ti);
+    printf("%d %d\n", small ? 1 : 0, ti);
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "--places") return print_places(argc, argv);
+  if (argc > 1) return 0;   // any other argument: "can this build start here?" (the test falls back to the plain build if not)
   const std::vector<int> Gs = {1, 2, 3, 4, 5, 7, 8, 16, 24, 31, 32, 64, 104, 256, 304, 1000};
   // pure 256 x 256 grids: the walk tests' own (9 tiles), the flagship MLP-up grid (480), ragged and grouped ones
   check_walk({768}, 768, 8, 0, Gs);

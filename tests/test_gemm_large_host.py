@@ -1,7 +1,9 @@
 """CPU checks of the reference side of tests/test_hip_gemm_large_exact.py: the data rules of tests/gemm_large_cases.py hold for
 every case the GPU file builds (one shared `host_cases()` list), every forced launch form applies to its shapes, the
 comparison functions see each planted mistake, the stream-K cases contain every move of `cut()`, and every (B, R) of the
-batch-boundary section puts a boundary inside a tile."""
+batch-boundary section puts a boundary inside a tile.  Section W (tests/test_hip_gemm_walk_exact.py, the tile walk under
+workgroup caps) goes through the same `host_cases()`; for it, too: every (launch, cap) has more tiles than workgroups, and the
+mixed grid's place order, restated in gemm_large_cases.py, is that of csrc/gemm_tile_map.h."""
 import pytest
 import torch
 
@@ -13,7 +15,7 @@ CASES = L.host_cases()
 
 
 def test_the_case_list_covers_the_sections():
-    assert {c[0] for c in CASES} == set("ABCDEFG")
+    assert {c[0] for c in CASES} == set("ABCDEFGW")
     assert {c[3] for c in CASES if c[0] == "A"} == {64, 128, 192, 256, 320}
     assert {c[6] for c in CASES if c[0] == "B"} == set(L.EPILOGUES)
     assert {(c[4], c[5]) for c in CASES if c[0] == "C" and c[6] in L.GATED} == set(L.C_BR)
@@ -236,3 +238,133 @@ def test_a_batch_boundary_lies_inside_a_tile(B, Rr):
     # joint buffers: the batch stride exceeds R x ld, so no operand of the slice run is flat
     S = L.C_S_TXT + Rr
     assert S * (L.C_K + L.PAD) > Rr * (L.C_K + L.PAD)
+
+
+# ---- section W: the tile walk under caps ------------------------------------------------------------------------------------------
+
+WALK = L.walk_launches()
+
+
+def test_walk_caps():
+    assert L.walk_caps(1) == [] and L.walk_caps(2) == [1] and L.walk_caps(3) == [1, 2] and L.walk_caps(4) == [1, 2, 3]
+    assert L.walk_caps(9) == [1, 2, 3, 8] and L.walk_caps(28) == [1, 2, 3, 27]
+    for tiles in range(2, 40):
+        caps = L.walk_caps(tiles)
+        assert 1 in caps and tiles - 1 in caps and len(set(caps)) == len(caps) and all(1 <= c < tiles for c in caps)
+        assert {2, 3} & set(range(1, tiles)) <= set(caps)
+
+
+def test_the_walk_tables_cover_their_parts():
+    assert {c[0] for c in WALK} == set("ABCDH") and {c[1] for c in WALK} == set(L.W_FORMS)
+    for form in L.W_FORMS:
+        assert {c[4] for c in WALK if c[:2] == ("A", form)} == set(L.A_KS) | set(L.W_LONG_KS)
+        assert {c[2][0] for c in WALK if c[:2] == ("A", form) and c[4] == 64} >= {257, 300, 513}      # ragged row tiles
+        assert {(c[2][0], c[3]) for c in WALK if c[:2] == ("B", form)} == set(L.B_SHAPES[form])
+    assert {c[6] for c in CASES if c[0] == "W" and c[3] in L.B_KS} >= set(L.EPILOGUES)
+    assert {(c[4], c[5]) for c in CASES if c[0] == "W" and c[2] == L.C_N and c[3] == L.C_K and c[6] in L.GATED} == set(L.C_BR)
+    assert all(c[6] == L.W_EPI_A for c in CASES if c[0] == "W" and c[3] in L.W_LONG_KS)
+    # shapes: at most 2100 x 1024, the long-K ones 513 x 1024 x 6400 at most
+    assert all(max(Ms) <= 2100 and N <= 1024 for _, _, Ms, N, _ in WALK)
+    assert all(Ms[0] <= 513 for _, _, Ms, N, K in WALK if K > 320)
+
+
+def test_every_walk_launch_has_more_tiles_than_its_cap():
+    """The launcher walks only where tiles > cap; at tiles <= cap it silently keeps one workgroup per tile, and a GPU case there
+    would pass without having run gemm_walk_kernel.  Every (launch, cap) of section W really walks, on any number of CUs."""
+    pairs = 0
+    for part, form, Ms, N, K in WALK:
+        assert N % 256 == 0 and K % 64 == 0 and (len(Ms) > 1 or Ms[0] >= 192)
+        assert form == 256 or L.mixed_big_cols(sum(-(-M // 256) for M in Ms), N) > 0, "the forced mixed form does not apply"
+        for cus in (256, 304, 64):
+            tiles = sum(L.walk_grid(form, Ms, N, cus))
+            caps = L.walk_caps(tiles)
+            assert tiles >= 2 and caps[0] == 1 and caps[-1] == tiles - 1
+            assert all(tiles > cap >= 1 for cap in caps)
+            pairs += cus == 256 and len(caps)
+    assert pairs > 300
+    # the hand-over patterns of the issue: one workgroup for the whole launch, tiles == cap + 1, and (the GPU file's extra
+    # tests) a cap of at least the tile count, where the rule declines
+    assert L.walk_grid(256, (513,), 768) == (9, 0) and L.walk_grid(384, (513,), 1024) == (3, 18)
+    assert L.walk_grid(256, tuple(B * Rr for B, Rr in L.D_BR), L.D_N) == (28, 0)
+    assert L.walk_grid(384, tuple(B * Rr for B, Rr in L.W_GM_BR), L.W_GM_N) == (7, 28)
+
+
+def test_makespan_and_the_forced_mixed_split():
+    """The launcher's plan restated: on 256 CUs every small grid of these tables ends with its one round of big tiles, so the
+    first split with at least 8 small tiles is taken -- one column of 256 x 256 tiles (what tests/test_hip_gemm_walk.py's
+    docstring states for 768 x 1024: 3 big + 18 small)."""
+    assert L.makespan(3, 18, 0.61, 256) == 1.0 and L.makespan(0, 600, 0.61, 256) == pytest.approx(1.83)
+    assert L.makespan(300, 0, 0.61, 256) == 2.0 and L.makespan(300, 300, 0.61, 256) == pytest.approx(2.22)
+    for nbm in (2, 3, 4, 7):
+        assert L.mixed_big_cols(nbm, 768) == 1 and L.mixed_big_cols(nbm, 1024) == 1
+    assert L.mixed_big_cols(4, 512) == 1 and L.mixed_big_cols(3, 512) == 0 and L.mixed_big_cols(3, 1000) == 0
+    cb = L.mixed_big_cols(10, 9216)      # the flagship fused-QKV grid: the plan's own mixed grid, more than one round of big tiles
+    assert 1 < cb < 36 and L.walk_grid(384, (2560,), 9216) == (10 * cb, 20 * (36 - cb))
+
+
+def test_mixed_place_order_is_the_tile_maps(tmp_path):
+    """`mix_table` / `mix_place` against tm_fill_mix / tm_mix_place of csrc/gemm_tile_map.h, through tests/gemm_walk_main.cpp
+    (--places), for every mixed launch of section W and the flagship fused-QKV grid."""
+    import subprocess
+    from test_gemm_tile_map import _compiler
+    from test_gemm_walk_map import _build
+    cxx = _compiler()
+    assert cxx, "no host C++ compiler found (g++ / clang++ / $CXX)"
+    exe = str(tmp_path / "gemm_walk_places")
+    r = _build(cxx, exe, sanitize=False)
+    assert r.returncode == 0, r.stderr[-4000:]
+    grids = {(Ms, N) for _, form, Ms, N, _ in WALK if form == 384} | {((2560,), 9216), ((2048, 512), 1024)}
+    for Ms, N in sorted(grids):
+        cb = L.mixed_big_cols(sum(-(-M // 256) for M in Ms), N)
+        for group_m in (1, 8):
+            run = subprocess.run([exe, "--places", str(N), str(cb), str(group_m), *map(str, Ms)], capture_output=True, text=True, timeout=60)
+            assert run.returncode == 0, run.stdout + run.stderr
+            lines = [tuple(map(int, ln.split())) for ln in run.stdout.split("\n") if ln]
+            tb, ts = L.walk_grid(384, Ms, N)
+            assert lines[0] == (tb, ts) and len(lines) == 1 + tb + ts
+            table = L.mix_table(tb, ts)
+            assert [(int(s), t) for s, t in (L.mix_place(table, b) for b in range(tb + ts))] == lines[1:], f"Ms {Ms} N {N}"
+
+
+def test_shape_changes_of_the_mixed_walk():
+    """How many hand-overs of section W change the tile shape (the workgroup barrier in `hand_over`).
+
+    The mixed grid's place order is big tiles first: place b = xcd + 8 idx is big iff idx < big_cnt[xcd], and big_cnt falls with
+    the XCD (tb / 8 + (xcd < tb % 8)), so no place behind a small tile names a big one (tests/gemm_walk_main.cpp checks exactly
+    this for every grid of its sweep).  A workgroup takes its places g, g + G, ... in rising order, whatever G is.  So NO grid
+    permits a small -> big hand-over, and a workgroup's list changes shape at most ONCE: "alternating" lists do not exist, the
+    barrier is reached by big -> small hand-overs alone.  Asserted: that bound for every (launch, cap); that EVERY mixed
+    (launch, cap) of section W has at least one such hand-over (workgroup 0 starts big and, tiles > cap, ends small), so every
+    mixed launch of the GPU file passes the barrier; and that the tables reach several of them in one launch, in several
+    workgroups, behind one, two and three big tiles of the same workgroup."""
+    mixed = [(part, Ms, N, K) for part, form, Ms, N, K in WALK if form == 384]
+    assert len(mixed) >= 30
+    behind = set()
+    for part, Ms, N, K in mixed:
+        tb, ts = L.walk_grid(384, Ms, N)
+        for cap in L.walk_caps(tb + ts):
+            most, to_small, to_big = L.shape_changes(tb, ts, cap)
+            assert most == 1 and to_big == 0 and 1 <= to_small <= min(cap, tb)
+            assert to_small == min(cap, tb) or cap == tb + ts - 1       # every workgroup that starts big ends small
+            lists = L.walk_shapes(tb, ts, cap)
+            assert sum(map(len, lists)) == tb + ts and lists[0][0] is False and lists[0][-1] is True
+            behind |= {ls.index(True) for ls in lists if not ls[0] and ls[-1]}
+    assert behind >= {1, 2, 3}, behind
+    for tb, ts, cap in ((260, 200, 256), (260, 200, 7), (9, 24, 5), (17, 8, 3), (3, 18, 20)):      # any grid, any G
+        most, to_small, to_big = L.shape_changes(tb, ts, cap)
+        assert most <= 1 and to_big == 0
+    for part, form, Ms, N, K in WALK:
+        if form == 256:
+            assert all(L.shape_changes(*L.walk_grid(256, Ms, N), cap) == (0, 0, 0) for cap in L.walk_caps(sum(L.walk_grid(256, Ms, N))))
+
+
+def test_the_problems_of_the_mixed_grouped_launch_share_nothing():
+    for epi in L.D_EPILOGUES:
+        ps = [L.case_problem(B * Rr, L.W_GM_N, L.W_GM_K, B, epi) for B, Rr in L.W_GM_BR]
+        for i, p in enumerate(ps):
+            for q in ps[i + 1:]:
+                assert (p.bias != q.bias).float().mean() > 0.5 and not (p.w == q.w).all(dim=1).any()
+                nb = min(p.B, q.B)
+                assert (p.gate[:nb] != q.gate[:nb]).all(), "two problems of the group share a gate value at (batch, column)"
+    assert len({L.gate_seed(B * Rr, L.W_GM_K) % len(L.GATE_VALUES) for B, Rr in L.W_GM_BR}) == len(L.W_GM_BR)
+    assert len({-(-B * Rr // 256) for B, Rr in L.W_GM_BR}) > 1 and all((B * Rr) % 256 for B, Rr in L.W_GM_BR)      # ragged M

@@ -6,7 +6,9 @@ fused-QKV grids, the small grids of tests/test_hip_gemm_walk.py, ragged and grou
 multiples of 8 and not -- the lists of the G workgroups together hold every place of the launch exactly once, place b is entry
 b / G of workgroup b % G (the order list scheduling gives a CU on the one-workgroup-per-tile launch), every place names the
 tile that launch computes from blockIdx.x = place, the tiles named are all tiles of the problems, each once, and on a mixed
-grid a workgroup whose places stay on one XCD never meets a 256 x 256 tile behind a 256 x 128 one.
+grid a workgroup whose places stay on one XCD never meets a 256 x 256 tile behind a 256 x 128 one -- nor does any other: no place
+behind a small tile names a big one, so for every G a workgroup's list changes shape at most once.
+`--places` prints a mixed launch's places for tests/test_gemm_large_host.py.
 Built with -fsanitize=address,undefined where the host compiler links them.
 """
 import os

@@ -397,6 +397,13 @@ def test_h_fused_qkv_epilogue(ops, form, mfma, thirds):
     """FK_EPI_QKV at H = 2 (a 256-wide tile spans two heads), N = 3 H 128 and N = 2 H 128, B = 2 with the image rows of a batch
     (280) ending inside a tile, text + image in one grouped launch: bit for bit the projection followed by fk_qkv_post_bf16;
     q / k start sentinel-filled, and of C only the v third is stored."""
+    _h_fused_qkv(ops, form, mfma, thirds)
+    _seen("H", f"N = {thirds} H 128 forced {form} mfma {mfma}", form)
+
+
+def _h_fused_qkv(ops, form, mfma, thirds, plain_launch=contextlib.nullcontext, fused_launches=(contextlib.nullcontext,)):
+    """Section H's case.  plain_launch / fused_launches: context managers around the unfused reference launch and around each
+    fused launch under test (tests/test_hip_gemm_walk_exact.py sets the tile walk's controls there)."""
     from oracle import mmdit
     from oracle.helpers import prepare_latent_image_ids
     B, H, S_txt, hh, ww, K = 2, 2, 70, 14, 20, 192
@@ -409,31 +416,35 @@ def test_h_fused_qkv_epilogue(ops, form, mfma, thirds):
     ids = torch.cat([torch.zeros(S_txt, 3), prepare_latent_image_ids(hh, ww)])
     cos, sin = (t.cuda() for t in mmdit.rope_tables(ids))
     Nf = thirds * D
+    assert (B, S_txt, hh * ww, H) == (L.W_H_BATCH, L.W_H_S_TXT, L.W_H_S_IMG, L.W_H_HEADS)
     with forced(ops, form, mfma):
         plain = torch.empty(B, S, 3 * D, dtype=BF, device="cuda")
-        ops.gemm_grouped([dict(a=x[:, S_txt:], w=w_i, bias=b_i, out=plain[:, S_txt:]),
-                          dict(a=x[:, :S_txt], w=w_t, bias=b_t, out=plain[:, :S_txt])])
+        with plain_launch():
+            ops.gemm_grouped([dict(a=x[:, S_txt:], w=w_i, bias=b_i, out=plain[:, S_txt:]),
+                              dict(a=x[:, :S_txt], w=w_t, bias=b_t, out=plain[:, :S_txt])])
         assert ops.gemm_last_variant() == form
         q_ref = torch.empty(B, H, S, 128, dtype=BF, device="cuda")
         k_ref = torch.empty_like(q_ref)
         ops.qkv_post(plain, q_ref, k_ref, nw[0], nw[1], nw[2], nw[3], cos, sin, S_txt)
-        q, k = torch.full_like(q_ref, SENTINEL), torch.full_like(q_ref, SENTINEL)
-        fused = torch.full((B, S + 1, Nf + 2 * GUARD_COLS), SENTINEL, dtype=BF, device="cuda")
-        fv = fused[:, :S, GUARD_COLS:GUARD_COLS + Nf]
-        ops.gemm_grouped([dict(a=x[:, S_txt:], w=w_i[:Nf], bias=b_i[:Nf], out=fv[:, S_txt:],
-                               qkv=dict(q_out=q, k_out=k, wq=nw[0], wk=nw[1], cos=cos, sin=sin, s_offset=S_txt)),
-                          dict(a=x[:, :S_txt], w=w_t[:Nf], bias=b_t[:Nf], out=fv[:, :S_txt],
-                               qkv=dict(q_out=q, k_out=k, wq=nw[2], wk=nw[3], cos=cos, sin=sin, s_offset=0))],
-                         epilogue=ops.FK_EPI_QKV)
-        assert ops.gemm_last_variant() == form
-    torch.cuda.synchronize()
-    assert torch.equal(q, q_ref), f"{(q != q_ref).sum().item()} elements of q differ"
-    assert torch.equal(k, k_ref), f"{(k != k_ref).sum().item()} elements of k differ"
-    want = torch.full_like(fused, SENTINEL)
-    if thirds == 3:
-        want[:, :S, GUARD_COLS + 2 * D:GUARD_COLS + 3 * D] = plain[:, :, 2 * D:]
-    assert torch.equal(fused, want), "C: only the v third is stored by the fused epilogue, the guard band stays"
-    _seen("H", f"N = {thirds} H 128 forced {form} mfma {mfma}", form)
+        for fused_launch in fused_launches:
+            q, k = torch.full_like(q_ref, SENTINEL), torch.full_like(q_ref, SENTINEL)
+            fused = torch.full((B, S + 1, Nf + 2 * GUARD_COLS), SENTINEL, dtype=BF, device="cuda")
+            fv = fused[:, :S, GUARD_COLS:GUARD_COLS + Nf]
+            with fused_launch():
+                ops.gemm_grouped([dict(a=x[:, S_txt:], w=w_i[:Nf], bias=b_i[:Nf], out=fv[:, S_txt:],
+                                       qkv=dict(q_out=q, k_out=k, wq=nw[0], wk=nw[1], cos=cos, sin=sin, s_offset=S_txt)),
+                                  dict(a=x[:, :S_txt], w=w_t[:Nf], bias=b_t[:Nf], out=fv[:, :S_txt],
+                                       qkv=dict(q_out=q, k_out=k, wq=nw[2], wk=nw[3], cos=cos, sin=sin, s_offset=0))],
+                                 epilogue=ops.FK_EPI_QKV)
+            assert ops.gemm_last_variant() == form
+            torch.cuda.synchronize()
+            what = getattr(fused_launch, "what", "")
+            assert torch.equal(q, q_ref), f"{what}{(q != q_ref).sum().item()} elements of q differ"
+            assert torch.equal(k, k_ref), f"{what}{(k != k_ref).sum().item()} elements of k differ"
+            want = torch.full_like(fused, SENTINEL)
+            if thirds == 3:
+                want[:, :S, GUARD_COLS + 2 * D:GUARD_COLS + 3 * D] = plain[:, :, 2 * D:]
+            assert torch.equal(fused, want), f"{what}C: only the v third is stored by the fused epilogue, the guard band stays"
 
 
 # ---- the wrapper's keyword --------------------------------------------------------------------------------------------------------
