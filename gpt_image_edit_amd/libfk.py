@@ -251,6 +251,13 @@ SIGNATURES = {
     "fk_image_overlay_u8": (c_i32, [c_vp] + [c_i32] * 3 + [c_vp, c_i32, c_vp, c_i32, c_vp] + [c_i32] * 7 + [c_vp]),
     "fk_resample_pass_u8": (c_i32, [c_vp, c_i64, c_i64, c_vp] + [c_i32] * 6 + [c_vp, c_vp, c_i32, c_vp]),
     "fk_bytes_overlay_u8": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp] + [c_i32] * 7 + [c_vp]),
+    "fk_edit_diff_mask_u8": (c_i32, [c_vp, c_i64, c_vp, c_vp] + [c_i32] * 4 + [c_vp]),
+    "fk_mask_close5_u8": (c_i32, [c_vp, c_vp] + [c_i32] * 3 + [c_vp]),
+    "fk_mask_components_ws_bytes": (c_i64, [c_i32] * 3),
+    "fk_mask_filter_components_u8": (c_i32, [c_vp, c_vp] + [c_i32] * 5 + [c_vp, c_i64, c_vp]),
+    "fk_mask_components_status": (c_i32, [c_vp, c_vp]),
+    "fk_mask_and_pool8_u8": (c_i32, [c_vp] + [c_i32] * 4 + [c_vp] * 5),
+    "fk_mask_weight_fill_f32": (c_i32, [c_vp] * 3 + [c_i32] * 3 + [c_vp]),
     "fk_double_block_fwd": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(DoubleBlockWeights), c_vp, c_i64, c_vp]),
     "fk_single_block_fwd": (c_i32, [ctypes.POINTER(BlockWs), ctypes.POINTER(SingleBlockWeights), c_vp, c_i64, c_vp]),
     "fk_single_block_bwd": (c_i32, [ctypes.POINTER(BwdWs), ctypes.POINTER(BlockSaved), ctypes.POINTER(SingleBlockWeights),

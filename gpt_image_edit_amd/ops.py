@@ -1616,6 +1616,108 @@ def image_overlay(img, orig_u8, alpha_u8, box, out=None):
     return out
 
 
+# ---- edit-region loss weights (include/fk.h: fk_edit_diff_mask_u8 .. fk_mask_weight_fill_f32; edit_weights.py) -----------------------
+def edit_diff_mask(ref_u8, tgt_u8, threshold=18, out=None):
+    """255 where Pillow's grey of |ref - tgt| is >= ``threshold``: uint8 NHWC RGB [N, H, W, 3] twice -> uint8 [N, H, W].  The
+    reference may be a view whose pictures are contiguous and lie any number of bytes apart (``refs[:, r]`` of [B, R, H, W, 3])."""
+    _need_cuda(ref_u8, tgt_u8, out)
+    for t in (ref_u8, tgt_u8):
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or not (t.is_contiguous() or (t is ref_u8 and t[0].is_contiguous())):
+            raise TypeError("edit_diff_mask takes contiguous uint8 [N, H, W, 3] tensors (the reference: contiguous pictures)")
+    if ref_u8.shape != tgt_u8.shape:
+        raise ValueError(f"edit_diff_mask: the reference is {tuple(ref_u8.shape)}, the target {tuple(tgt_u8.shape)}")
+    N, H, W, _ = ref_u8.shape
+    if out is None:
+        out = torch.empty((N, H, W), device=ref_u8.device, dtype=torch.uint8)
+    _mask_u8(out, "edit_diff_mask")
+    if tuple(out.shape) != (N, H, W):
+        raise ValueError("out must have the pictures' [N, H, W]")
+    ref_bs = ref_u8.stride(0) if N > 1 else H * W * 3
+    libfk.check(libfk.load().fk_edit_diff_mask_u8(_ptr(ref_u8), ref_bs, _ptr(tgt_u8), _ptr(out), N, H, W, int(threshold), _stream()),
+                "fk_edit_diff_mask_u8")
+    return out
+
+
+def mask_close5(mask, out=None):
+    """Closing (dilation, then erosion) with the 5 x 5 ellipse; the outside of the plane is never counted."""
+    N, H, W = _mask_u8(mask, "mask_close5")
+    if out is None:
+        out = torch.empty_like(mask)
+    _mask_u8(out, "mask_close5")
+    if out.shape != mask.shape:
+        raise ValueError("out must have the mask's shape")
+    libfk.check(libfk.load().fk_mask_close5_u8(_ptr(mask), _ptr(out), N, H, W, _stream()), "fk_mask_close5_u8")
+    return out
+
+
+def mask_components_ws(N, H, W, device):
+    """The labelling workspace of :func:`mask_filter_components` (int32; word 0 is its status)."""
+    nbytes = libfk.load().fk_mask_components_ws_bytes(N, H, W)
+    return torch.empty(max(nbytes, 4) // 4, device=device, dtype=torch.int32)
+
+
+def mask_filter_components(mask, keep_num=3, keep_den=10, out=None, ws=None, check=True):
+    """Keeps the 8-connected components with ``keep_den * area >= keep_num * white pixels of the plane``.  ``check``: wait for the
+    stream and raise when a labelling loop reached its bound (FK_EBOUND); without it the caller hands ``ws`` to
+    :func:`mask_and_pool8`, whose counts carry the status."""
+    N, H, W = _mask_u8(mask, "mask_filter_components")
+    lib = libfk.load()
+    if out is None:
+        out = torch.empty_like(mask)
+    _mask_u8(out, "mask_filter_components")
+    if out.shape != mask.shape:
+        raise ValueError("out must have the mask's shape")
+    if ws is None:
+        ws = mask_components_ws(N, H, W, mask.device)
+    _need_cuda(ws)
+    if ws.dtype != torch.int32 or not ws.is_contiguous():
+        raise ValueError("ws must be a contiguous int32 workspace")
+    libfk.check(lib.fk_mask_filter_components_u8(_ptr(mask), _ptr(out), N, H, W, int(keep_num), int(keep_den), _ptr(ws),
+                                                 ws.numel() * 4, _stream()), "fk_mask_filter_components_u8")
+    if check:
+        libfk.check(lib.fk_mask_components_status(_ptr(ws), _stream()), "fk_mask_components_status")
+    return out
+
+
+def mask_and_pool8(masks, status=None, out=None):
+    """uint8 [B, R, H, W] -> (mask_ds uint8 [B, H // 8, W // 8], counts int32 [B, 2]): AND over R, counts[:, 0] its white pixels,
+    the all-white plane where that is 0, 8 x 8 max pool, :func:`mask_close5`, counts[:, 1] the white pixels of mask_ds.
+    ``status``: the workspace of :func:`mask_filter_components`; a labelling that reached a bound turns every count into -1.
+    ``out``: (pooled, mask_ds, counts), the three buffers the stage writes (allocated per call when None)."""
+    _need_cuda(masks, status)
+    if masks.dtype != torch.uint8 or masks.dim() != 4 or not masks.is_contiguous():
+        raise TypeError("mask_and_pool8 takes a contiguous uint8 [B, R, H, W] tensor")
+    B, R, H, W = masks.shape
+    if out is None:
+        out = (torch.empty((B, H // 8, W // 8), device=masks.device, dtype=torch.uint8),
+               torch.empty((B, H // 8, W // 8), device=masks.device, dtype=torch.uint8),
+               torch.empty((B, 2), device=masks.device, dtype=torch.int32))
+    pooled, mask_ds, counts = out
+    _need_cuda(pooled, mask_ds, counts)
+    for t, shape, dtype in ((pooled, (B, H // 8, W // 8), torch.uint8), (mask_ds, (B, H // 8, W // 8), torch.uint8),
+                            (counts, (B, 2), torch.int32)):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"out must be (pooled, mask_ds, counts): contiguous uint8 {(B, H // 8, W // 8)} twice and int32 {(B, 2)}")
+    libfk.check(libfk.load().fk_mask_and_pool8_u8(_ptr(masks), B, R, H, W, _ptr(pooled), _ptr(mask_ds), _ptr(counts), _ptr(status),
+                                                  _stream()), "fk_mask_and_pool8_u8")
+    return mask_ds, counts
+
+
+def mask_weight_fill(mask_ds, w, out=None):
+    """fp32 [B, 1, h, w]: ``w[b]`` where ``mask_ds`` [B, h, w] is white, 1.0 elsewhere."""
+    B, h, wd = _mask_u8(mask_ds, "mask_weight_fill")
+    _need_cuda(w, out)
+    if w.dtype != torch.float32 or tuple(w.shape) != (B,) or not w.is_contiguous():
+        raise TypeError("mask_weight_fill takes the weights as a contiguous fp32 [B] tensor")
+    if out is None:
+        out = torch.empty((B, 1, h, wd), device=mask_ds.device, dtype=torch.float32)
+    if out.dtype != torch.float32 or tuple(out.shape) != (B, 1, h, wd) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous fp32 [B, 1, h, w] tensor")
+    libfk.check(libfk.load().fk_mask_weight_fill_f32(_ptr(mask_ds), _ptr(w), _ptr(out), B, h, wd, _stream()),
+                "fk_mask_weight_fill_f32")
+    return out
+
+
 # ---- antialiased byte resize and byte paste-back (include/fk.h: fk_resample_pass_u8, fk_bytes_overlay_u8) ---------------------------
 _resample_tables = {}       # (n_in, n_out, filter, device, axis) -> (bounds, kk) on the device, kk tap-major for axis 1
 

@@ -275,7 +275,8 @@ class DenoiserTrainStep:
         Either ``prompt_embeds`` (projector frozen / absent) or ``vlm_hidden`` [B,L,3584] (+ optional T5 prefix).
         The loss as the stage-2 config sets it up (``mask_weight_type: 'log'``; train_denoiser.py:1106-1166): ``weighting``
         fp32 [B] (``compute_loss_weighting_for_sd3`` / ``sigmas_as_weight``; None = ones), ``area_mask_weights`` [B,1,H,W]
-        (the dataset's per-pixel area weights), ``weight_mask`` [B,1,H,W] (1 inside a padded sample's true extent; with it
+        (the dataset's per-pixel area weights; ``edit_weights.edit_region_weights`` makes them on the device from the reference
+        and target bytes), ``weight_mask`` [B,1,H,W] (1 inside a padded sample's true extent; with it
         the sum is divided by ``weight_mask.sum() * C`` instead of the element count).  ``attention_mask``: bool / 0-1
         [B, S_img] or [B, C, S_img] over the image tokens (target tokens, then condition tokens), non-zero = a real token
         -- the attention then runs under that key mask; None: unmasked."""

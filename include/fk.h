@@ -33,6 +33,7 @@ enum {
   FK_EINVAL = -1,  /* bad shape / alignment / null pointer */
   FK_EUNSUPPORTED = -2,
   FK_ELAUNCH = -3, /* hipLaunch / runtime error */
+  FK_EBOUND = -4,  /* a device loop reached the bound its plane size gives it (fk_mask_components_status) */
 };
 
 /* Epilogues of fk_gemm_bf16 (applied in this order; every stage rounds to bf16 exactly where the
@@ -976,6 +977,60 @@ int fk_resample_pass_u8(const void* src, int64_t src_batch_stride, int64_t src_r
  * claimed. */
 int fk_bytes_overlay_u8(const void* res, const void* orig, int32_t orig_batch, const void* alpha, int32_t alpha_batch, void* dst,
                         int32_t B, int32_t H, int32_t W, int32_t x0, int32_t y0, int32_t x1, int32_t y1, fk_stream_t stream);
+
+/* ---- Edit-region loss weights (edit_weights.py: edit_region_weights; csrc/edit_weights.hip).  The per-pixel loss map of the
+ * reference's `mask_weight_type` configs (univa/utils/get_mask.py: get_weight_mask), from the (reference, target) bytes on the device.
+ * Integer arithmetic only, so every stage is held to EQUALITY with its numpy restatement (tests/edit_weights_ref.py,
+ * tests/test_hip_edit_weights_kernels.py).  Parity: the grey conversion is pinned to the installed Pillow; the closing and the
+ * labelling are written from OpenCV's documented behaviour (ellipse table, default morphology border, connectivity 8) and
+ * cross-checked against scipy; OpenCV itself is not available to the tests, so parity with OpenCV is unpinned.
+ *
+ * Masks are uint8 planes [N, H, W]; the entries write 0 or 255 and read a byte as white iff it is >= 128.  Sizes: 1 <= H, W <=
+ * FK_EDIT_MASK_MAX_SIDE and N * H * W < 2^31 (E4: 8 <= H, W and B <= 65535 as well).  A refused call returns FK_EINVAL with the
+ * entry's name in the message and writes nothing. ---- */
+#define FK_EDIT_MASK_MAX_SIDE 4096
+#define FK_MASK_CLOSE_TILE 32
+
+/* E1.  ref, tgt: uint8 NHWC RGB [N, H, W, 3] (rows need no alignment); the reference pictures lie ref_batch_stride >= H * W * 3
+ * bytes apart, so a slice [:, r] of [B, R, H, W, 3] is read in place; dst: uint8 [N, H, W], a buffer of its own.  Per pixel
+ *   d_c = |ref_c - tgt_c|,  grey = (19595 d_R + 38470 d_G + 7471 d_B + 32768) >> 16,  dst = 255 iff grey >= threshold (0..256)
+ * which is ImageChops.difference(ref, tgt).convert("L").point(lambda v: 255 if v >= threshold else 0), byte for byte. */
+int fk_edit_diff_mask_u8(const void* ref, int64_t ref_batch_stride, const void* tgt, void* dst, int32_t N, int32_t H, int32_t W,
+                         int32_t threshold, fk_stream_t stream);
+/* E2.  Closing with the 5 x 5 ellipse whose rows are 00100 / 11111 / 11111 / 11111 / 00100 (OpenCV's MORPH_ELLIPSE (5, 5)):
+ * dilation first (white iff any pixel under the element is white), then erosion (white iff every pixel under it is).  Positions
+ * outside the plane are not counted in either pass: a border never dilates and never erodes.  One block closes one
+ * FK_MASK_CLOSE_TILE-square tile at a time from LDS; dst is a buffer of its own. */
+int fk_mask_close5_u8(const void* src, void* dst, int32_t N, int32_t H, int32_t W, fk_stream_t stream);
+/* E3.  The white pixels of each plane are labelled by 8-connectivity (planes never connect); a component survives iff
+ *   keep_den * area >= keep_num * (white pixels of its plane)        (int64 products; keep_num >= 0, keep_den >= 1)
+ * -- the denominator is the plane's WHITE count, not H * W.  For keep 3 / 10 this is the reference's float64 test
+ * area >= 0.3 * total: at a tie 0.3 * total rounds to the integer itself and the component is kept (tests/test_edit_weights_ref.py).
+ * dst may be src.  ws: fk_mask_components_ws_bytes(N, H, W) bytes, caller-owned, 4-byte aligned, one per stream of ordered
+ * launches: int32 [0] the status word, [1, 1 + N) the planes' white counts, then the labels and the areas, N * H * W each.
+ * Labelling: the first pixel of every horizontal run labels the run with its own index in [N, H, W]; every white pixel then joins
+ * the run above it (straight above, else the two diagonals) by pointing the larger root at the smaller with atomicMin; a pass takes
+ * every pixel to its root, which is the least index of its component whatever order the atomics took; areas and white counts are
+ * atomicAdd sums of run lengths.  Two launches give the same bytes.  Every loop has a bound from the plane's size: a run W steps,
+ * a chain of parents (strictly decreasing inside one plane) H * W, the retries of a union (the larger index in hand falls with each)
+ * H * W.  A loop that reaches its bound, or meets a label that is none, sets the status word and stops: never a hang; the loops of
+ * the other lanes look at the word (a chase every 256 steps, a union before each try) and give up too.  The entry
+ * itself reads nothing back; fk_mask_components_status(ws) waits for the stream, reads the word and returns FK_EBOUND when it is
+ * set, and E4 carries it to the host inside its counts. */
+int64_t fk_mask_components_ws_bytes(int32_t N, int32_t H, int32_t W);   /* 0 for sizes the entry refuses */
+int fk_mask_filter_components_u8(const void* src, void* dst, int32_t N, int32_t H, int32_t W, int32_t keep_num, int32_t keep_den,
+                                 int32_t* ws, int64_t ws_bytes, fk_stream_t stream);
+int fk_mask_components_status(const int32_t* ws, fk_stream_t stream);
+/* E4.  masks: uint8 [B, R, H, W], R >= 1.  Per sample b: the AND over its R planes; counts[b, 0] = its white pixels; when that is
+ * 0 the all-white plane takes its place (the reference's "reconstruction data" rule, decided on the device); 8 x 8 / stride-8 max
+ * pool with floor sizes (F.max_pool2d) into pooled [B, H / 8, W / 8]; E2 of pooled into mask_ds; counts[b, 1] = the white pixels
+ * of mask_ds.  counts: device int32 [B, 2], cleared here.  status: NULL, or E3's workspace: when its status word is set every
+ * count is written as -1, so the caller's one read-back of counts shows a labelling that reached a bound.  pooled and mask_ds are
+ * caller-owned buffers of their own. */
+int fk_mask_and_pool8_u8(const void* masks, int32_t B, int32_t R, int32_t H, int32_t W, void* pooled, void* mask_ds, int32_t* counts,
+                         const int32_t* status, fk_stream_t stream);
+/* E5.  dst fp32 [B, 1, h, w] = w[b] where mask_ds [B, h, w] is white, 1.0f elsewhere.  w: device fp32 [B]. */
+int fk_mask_weight_fill_f32(const void* mask_ds, const float* w, float* dst, int32_t B, int32_t h, int32_t wd, fk_stream_t stream);
 
 /* ---- LoRA merge (transformer.py: load_lora_adapter / set_adapters / set_lora_scale; the reference's pipeline is a
  * FluxLoraLoaderMixin, univa/utils/flux_pipeline.py:195).  Adapters become part of a bf16 weight [N, K]:
